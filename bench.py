@@ -10,12 +10,19 @@ per-rank statistics are merged once at the end.
 
 The LAST stdout line of rank 0 is the bench line of the driver contract: compact (<= 4 KB), plain ASCII, with
   roofline      HBM roofline of the dominant kernel, measured with hipEvents on the launch stream
-  cpu_baseline  the reference's own fastq_info -r (oracle/_ref) timed on this box's host cores
-  host_fed      the configs[1] placement (reads in host RAM, fed over PCIe): C-ABI and program rates
-  extras        a few numbers per untimed extra; extras_ok = every comparison in them held
-The same line (marked "final": false, without host_fed/extras) is printed once before the untimed extras start, so a
-crash in an extra cannot take the measured numbers with it; each extra then goes out as ONE line of its own
+  cpu_baseline  the reference's own fastq_info -r (oracle/_ref) timed on the host's cores    (--full)
+  host_fed      the configs[1] placement (reads in host RAM, fed over PCIe): C-ABI and program rates   (--full)
+  extras        a few numbers per untimed extra; extras_ok = every comparison in them held    (--full)
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints that line: nothing else.  With
+--full the same line (marked "final": false, without host_fed/extras) is printed once before the untimed extras start,
+so a crash in an extra cannot take the measured numbers with it; each extra then goes out as ONE line of its own
 ({"extra": name, ...}), and all of them are written to --extras-out as one JSON document.
+
+--dump-outputs DIR writes what a caller of the timed path holds after the last timed step, as float64 .npy files:
+  validate_result.npy   the last validate call's result (DUMP_RESULT_FIELDS)
+  stats.npy             the accumulator it feeds (reset after the warm-up): DUMP_STATS_FIELDS
+  read_length_hist.npy  that accumulator's read-length histogram, one (length, count) row per length seen
+The synthetic reads come from a fixed seed, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -33,6 +40,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 ALGO_BYTES_PER_READ_EXTRA = 32  # descriptor bytes per record
 
 HEADLINE_MAX_BYTES = 4096  # the driver keeps a bounded tail of stdout: the last line must fit in it with room to spare
+
+# what --dump-outputs writes (the result's `path` says which kernels ran, not what they computed: it is left out)
+DUMP_RESULT_FIELDS = ("n_records", "n_lines", "consumed", "record", "aux0", "aux1", "code", "stopped", "tail_lines")
+DUMP_STATS_FIELDS = ("num_rds", "min_rl", "max_rl", "min_qual", "max_qual", "median_rl")
 
 
 def _plain(v, sig=6):
@@ -200,6 +211,11 @@ def parse():
     ap.add_argument("--extras-out", default=None, metavar="PATH",
                     help="also write every untimed extra as one JSON document here (default: gpurun_out/bench_extras.json "
                          "when gpurun_out/ exists)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the cross-rank extra, every "
+                         "untimed extra (the --no-* options above pick among them) and --extras-out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float64)")
     ap.add_argument("--bgzf-helper", nargs=2, metavar=("SRC", "DST"), help=argparse.SUPPRESS)
     ap.add_argument("--gz-helper", nargs=3, metavar=("SRC", "DST", "NBYTES"), help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -1455,6 +1471,18 @@ def committed_traffic(kernel, n_reads, read_len, record_bytes):
     return total, rel
 
 
+def dump_outputs(path, res, acc):
+    """--dump-outputs: the last timed validate call's result and the accumulator of the timed steps (module docstring)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    stats = dict(acc.read(), median_rl=acc.median())
+    hist = sorted(acc.hist().items())
+    np.save(os.path.join(path, "validate_result.npy"), np.array([res[k] for k in DUMP_RESULT_FIELDS], dtype=np.float64))
+    np.save(os.path.join(path, "stats.npy"), np.array([stats[k] for k in DUMP_STATS_FIELDS], dtype=np.float64))
+    np.save(os.path.join(path, "read_length_hist.npy"), np.array(hist, dtype=np.float64).reshape(-1, 2))
+
+
 def flush_c_stdio():
     """A library's printf into a pipe sits in libc's buffer until the process leaves through exit(): flushed now, it
     cannot land behind the bench line (which must be the last line of stdout)."""
@@ -1463,14 +1491,6 @@ def flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except (OSError, AttributeError):
         pass
-
-
-def under_a_profiler():
-    """rocprofv3 preloads its tool library and writes its output when the process leaves through exit()"""
-    if os.environ.get("FQGPU_BENCH_PLAIN_EXIT"):
-        return True
-    pre = os.environ.get("LD_PRELOAD", "") + os.environ.get("ROCP_TOOL_LIBRARIES", "")
-    return "rocprof" in pre or any(k.startswith(("ROCPROF", "ROCPROFILER_")) for k in os.environ)
 
 
 def launch_ranks(n_gpus):
@@ -1654,12 +1674,17 @@ def main():
                 "kernels_ms_per_step": {k: v[1] / a.steps for k, v in kernels.items()},
             },
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res, acc)
+        if a.full and world == 1 and not a.no_cpu_baseline:
             m = min(n, a.cpu_sample_reads)
             out["cpu_baseline"] = cpu_baseline(bytes(image[: m * R].cpu().numpy()), m)
         # the measured numbers go out before any untimed extra runs (marked "final": false); the line is printed again,
         # complete, as the last line of stdout
-        print(headline_line(out, final=False), flush=True)
+        if a.full:
+            print(headline_line(out, final=False), flush=True)
+        else:
+            print(headline_line(out), flush=True)  # a plain run: this is its one and last line
     # The extra below is the only part of a --gpus N run with collectives in the data path (RCCL all-to-all).
     # If it should hang on some topology, the line above must still come out: a watchdog prints it and ends
     # every rank.
@@ -1672,12 +1697,12 @@ def main():
         os._exit(3)  # the headline line is out, but the run did not complete: not a success
 
     watchdog = None
-    if not a.no_dedup_extra and world > 1:
+    if a.full and not a.no_dedup_extra and world > 1:
         watchdog = threading.Timer(float(os.environ.get("FQGPU_BENCH_EXTRA_TIMEOUT", "240")), give_up)
         watchdog.daemon = True
         watchdog.start()
     dedup = None
-    if not a.no_dedup_extra and (world > 1 or a.dedup_extra):
+    if a.full and not a.no_dedup_extra and (world > 1 or a.dedup_extra):
         # untimed extra on every rank: the unique-name test of fastq_info's index mode over the names of
         # ALL ranks: 16-byte (fingerprint, global index) pairs, one all-to-all over RCCL, owner
         # sets, candidates confirmed on the name bytes.  Names are unique by construction -> no finding.
@@ -1759,7 +1784,7 @@ def main():
 
     if watchdog is not None:
         watchdog.cancel()
-    if rank == 0:
+    if rank == 0 and a.full:
         extras = {}
 
         def extra(name, fn):
@@ -1912,13 +1937,8 @@ def main():
         os._exit(4 if (dedup is not None and "error" in dedup) else 0)
     acc.close()
     ctx.close()
-    # (the line is out and everything is closed: leave without the interpreter's and the HIP runtime's tear-down - a
-    # drop-in program that left through exit() ended with a segmentation fault once in a few hundred runs)
-    sys.stdout.flush()
-    sys.stderr.flush()
-    if under_a_profiler():
-        return  # (rocprofv3 writes its files from an exit hook: leave the ordinary way)
-    os._exit(0)
+    # (the line is out and everything is closed: leave the ordinary way, through exit(), whose hooks a preloaded tool
+    # such as rocprofv3 writes its files from; the library quiesces its own threads from an atexit handler)
 
 
 if __name__ == "__main__":

@@ -84,15 +84,12 @@ def test_compat_library_exports_the_reference_api():
 
 
 def test_compat_header_layouts_match_the_reference_headers(tmp_path):
-    """Same struct layouts as the reference's own headers (only where the reference checkout exists: the
-    build container).  Two tiny programs print sizeof / offsetof under each header set."""
+    """Same struct layouts as the reference's own headers: a tiny program prints sizeof / offsetof under our header,
+    and must print what the same program printed under the reference's fastq.h + range_list.h
+    (tests/golden/compat_header_layouts.txt, recorded with gcc on x86-64 Linux)."""
     import os
     import subprocess
 
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        import pytest
-        pytest.skip("no reference checkout here")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     body = r'''
 #include <stdio.h>
@@ -111,15 +108,13 @@ int main(void) {
   return 0;
 }
 '''
-    outs = []
-    for tag, inc, hdr in (("ours", os.path.join(repo, "include"), '#include "fastq_gpu_compat.h"'),
-                          ("ref", ref, '#include "fastq.h"\n#include "range_list.h"')):
-        src = tmp_path / (tag + ".c")
-        src.write_text(hdr + body)
-        exe = tmp_path / tag
-        subprocess.run(["gcc", "-w", "-I", inc, "-o", str(exe), str(src)], check=True)
-        outs.append(subprocess.run([str(exe)], capture_output=True, check=True).stdout)
-    assert outs[0] == outs[1]
+    src = tmp_path / "ours.c"
+    src.write_text('#include "fastq_gpu_compat.h"' + body)
+    exe = tmp_path / "ours"
+    subprocess.run(["gcc", "-w", "-I", os.path.join(repo, "include"), "-o", str(exe), str(src)], check=True)
+    ours = subprocess.run([str(exe)], capture_output=True, check=True).stdout
+    with open(os.path.join(repo, "tests", "golden", "compat_header_layouts.txt"), "rb") as f:
+        assert ours == f.read()
 
 
 def test_reference_unit_test_program_runs_on_the_compat_library():

@@ -21,7 +21,7 @@ def test_two_ranks_on_one_device(ranks):
     reads = 1000000 if ranks == 8 else 2000000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--reads", str(reads)]
+           "--reads", str(reads), "--full"]
     check_line(run_group(cmd, 900, cwd=REPO, env=env), ranks, reads)
 
 
@@ -31,7 +31,7 @@ def test_bench_starts_its_own_ranks():
     env = dict(os.environ, FQGPU_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "2000000"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "2000000", "--full"]
     check_line(run_group(cmd, 600, cwd=REPO, env=env), 2)
 
 

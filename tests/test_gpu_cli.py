@@ -12,7 +12,7 @@ import pytest
 
 from oracle import loader as orc
 from tests import fuzz
-from tests.util import GOLD, REPO, SideBySide, load_fastq_info_golden, strip_progress, thinned
+from tests.util import GOLD, GPU_PROGRAMS, GPU_PROGRAMS_ANY_INPUT, REPO, SideBySide, load_fastq_info_golden, strip_progress, thinned
 
 pytestmark = pytest.mark.gpu
 BIN = os.path.join(REPO, "bin", "fastq_info")
@@ -31,7 +31,7 @@ def test_binary_exists():
     assert os.path.exists(BIN), "run __graft_entry__.build() first"
 
 
-POOL = 12  # programs started side by side: a process start + HIP initialisation is 0.34 s alone, and the driver takes
+POOL = GPU_PROGRAMS  # golden invocations started side by side: a process start + HIP initialisation is 0.34 s alone, and the driver takes
 # about 15 of them a second however many wait (tools/golden_concurrency.py) - one at a time the suite does not fit its slot
 CHUNKED = {"FQGPU_PGZIP_MIN": "0", "FQGPU_PGZIP_CHUNK": "4096", "FQGPU_HOST_THREADS": "3"}
 
@@ -109,7 +109,7 @@ def compare_all(jobs):
             return None
         return (os.path.basename(cwd), args, env, rc, want["exit"], err[-500:], want["stderr"][-500:])
 
-    with ThreadPoolExecutor(POOL) as ex:
+    with ThreadPoolExecutor(GPU_PROGRAMS_ANY_INPUT) as ex:
         bad = [b for b in ex.map(one, jobs) if b]
     assert not bad, f"{len(bad)} of {len(jobs)} differ; first: {bad[:2]}"
 
@@ -266,7 +266,8 @@ def _long_line_run(key):
 # (the programs of all cases start side by side the first time one is asked for: tests/util.py)
 LONG_RUNS = SideBySide(_long_line_run, [(w, h, a) for w in sorted(_overlong()) for h in LONG_HOW for a in range(len(LONG_ARGS))],
                        select=lambda ks: [k for k in ks if k[1] == list(LONG_HOW)[0]] +
-                       [k for k in ks if k[1] != list(LONG_HOW)[0] and (k[0], k[1]) in set(thinned({(w, h) for w, h, _ in ks if h != list(LONG_HOW)[0]}, key="-".join))])
+                       [k for k in ks if k[1] != list(LONG_HOW)[0] and (k[0], k[1]) in set(thinned({(w, h) for w, h, _ in ks if h != list(LONG_HOW)[0]}, key="-".join))],
+                       workers=GPU_PROGRAMS_ANY_INPUT)
 
 
 @pytest.mark.parametrize("how", list(LONG_HOW))
@@ -336,7 +337,7 @@ def test_bgzipped_input_and_json_metrics():
             rc, out, err = run_cli(args, tmp, {"FQGPU_CHUNK_MB": "1"})
             return (rc, out, strip_progress(err).replace(stem + ext, "F"))
 
-        with ThreadPoolExecutor(POOL) as ex:
+        with ThreadPoolExecutor(GPU_PROGRAMS_ANY_INPUT) as ex:
             got = list(ex.map(one, runs))
         for k in range(0, len(runs), 3):  # the three containers of one (file, mode)
             assert got[k] == got[k + 1] == got[k + 2], (runs[k], got[k][2][-300:], got[k + 1][2][-300:], got[k + 2][2][-300:])

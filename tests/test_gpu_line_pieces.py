@@ -18,7 +18,7 @@ import tempfile
 import pytest
 
 from tests.test_oracle_vs_ref_fuzz import overlong_images
-from tests.util import REPO, SideBySide, strip_progress, thinned
+from tests.util import GPU_PROGRAMS_ANY_INPUT, REPO, SideBySide, strip_progress, thinned
 
 pytestmark = pytest.mark.gpu
 REF = os.path.join(REPO, "oracle", "_ref")
@@ -87,7 +87,7 @@ KEYS = [(prog, which, how) for prog in PROGRAMS for which in sorted(IMAGES) for 
         and not (how == "small_pieces" and which.startswith("nul_"))]               # (the NUL images are a few hundred bytes)
 # (the programs of all cases start side by side the first time one is asked for: tests/util.py)
 # (on a box that starts programs slowly the ways other than the plain file are thinned out: tests/util.py)
-OURS = SideBySide(lambda k: one_run(ROOT.name, BIN, *k), KEYS,
+OURS = SideBySide(lambda k: one_run(ROOT.name, BIN, *k), KEYS, workers=GPU_PROGRAMS_ANY_INPUT,
                   select=lambda ks: [k for k in ks if k[2] == "plain_file"] + thinned([k for k in ks if k[2] != "plain_file"], key="-".join))
 
 

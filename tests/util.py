@@ -40,6 +40,14 @@ def free_port():
         return s.getsockname()[1]
 
 
+# Programs started side by side, at most: no more than 16 processes may hold the GPU at once, the test process among
+# them.  A program that meets a line beyond the reference's gzgets limits in a plain file starts itself again as a
+# child while it holds the GPU (host/fq_respawn.h).  The committed golden inputs hold no such line (gzip input is cut
+# while it is inflated): GPU_PROGRAMS of them.  Any other input: GPU_PROGRAMS_ANY_INPUT (7 * 2 + 1).
+GPU_PROGRAMS = 12
+GPU_PROGRAMS_ANY_INPUT = 7
+
+
 def run_group(cmd, timeout, **kw):
     """subprocess.run(capture_output=True) for a launcher that starts ranks of its own: the launcher runs in its
     own process group, and on a timeout the WHOLE group is killed (a hung rank must not outlive the test)."""
@@ -66,7 +74,7 @@ class SideBySide:
     (tools/golden_concurrency.py) - every test still compares its own case, it only does not wait alone.
     An exception inside fn(key) is raised in the test that asks for that key."""
 
-    def __init__(self, fn, keys, workers=12, select=None):
+    def __init__(self, fn, keys, workers=GPU_PROGRAMS, select=None):
         # select(keys) -> the keys that are run on this box (asked when the first key is: `thinned` below measures the
         # box); a test whose key is not among them is skipped, and says so
         self.fn, self.keys, self.workers, self.results, self.select = fn, list(keys), workers, None, select

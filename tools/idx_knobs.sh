@@ -2,7 +2,7 @@
 # name kernels under ablations / launch shapes (measurement only): tools/idx_knobs.sh
 run() {
   echo "== $*"
-  env "$@" timeout 150 python bench.py --steps 2 --reads ${READS:-100000000} --no-cpu-baseline --no-e2e --no-barcodes-extra --no-filters-extra --no-umi-extra --no-tags-extra --no-filterpair-extra --no-shapes-extra 2>&1 | python -c "
+  env "$@" timeout 150 python bench.py --full --steps 2 --reads ${READS:-100000000} --no-cpu-baseline --no-e2e --no-barcodes-extra --no-filters-extra --no-umi-extra --no-tags-extra --no-filterpair-extra --no-shapes-extra 2>&1 | python -c "
 import json,sys
 txt=sys.stdin.read()
 try:

@@ -20,12 +20,12 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 ONLY_HEADLINE="--no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-barcodes-extra --no-filters-extra --no-umi-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
-ONLY_UMI="--reads 4000000 --steps 2 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-barcodes-extra --no-filters-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
+ONLY_UMI="--full --reads 4000000 --steps 2 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-barcodes-extra --no-filters-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
 for w in $WHAT; do
   case $w in
   bench)
-    python3 $R/bench.py --extras-out $O/bench.json > $O/bench_stdout.txt 2> $O/bench.err  # bench.json: headline + every extra as one document; the last line of bench_stdout.txt is the judged line
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o stats -- python3 $R/bench.py --no-cpu-baseline --no-e2e > $O/under_rocprof.json 2> $O/under_rocprof.err
+    python3 $R/bench.py --full --extras-out $O/bench.json > $O/bench_stdout.txt 2> $O/bench.err  # bench.json: headline + every extra as one document; the last line of bench_stdout.txt is the judged line
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o stats -- python3 $R/bench.py --full --no-cpu-baseline --no-e2e > $O/under_rocprof.json 2> $O/under_rocprof.err
     find $O/stats -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats.csv \;
     find $O/stats -name '*kernel_trace.csv' -delete
     # the headline workload alone (what bench.py's roofline block times): its average launch durations are the ones to
@@ -45,7 +45,7 @@ for w in $WHAT; do
     ;;
   index)
     # HBM bytes of the name kernels (default mode: validate + k_index_insert over 100 M unique names)
-    ONLY_INDEX="--steps 2 --no-cpu-baseline --no-e2e --no-dedup-extra --no-barcodes-extra --no-filters-extra --no-umi-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
+    ONLY_INDEX="--full --steps 2 --no-cpu-baseline --no-e2e --no-dedup-extra --no-barcodes-extra --no-filters-extra --no-umi-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
     for c in FETCH_SIZE WRITE_SIZE; do
       rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/idx_pmc_$c -o pmc -- python3 $R/bench.py $ONLY_INDEX > $O/idx_pmc_$c.json 2> $O/idx_pmc_$c.err
       find $O/idx_pmc_$c -name '*kernel_trace.csv' -delete
@@ -71,7 +71,7 @@ for w in $WHAT; do
     (cd $R/tools/kbench && timeout 120 ./decbench) > $O/decbench.txt 2>&1
     ;;
   tilessq)
-    ONLY_BC="--reads 4000000 --steps 2 --barcode-pairs 50000000 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-umi-extra --no-filters-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
+    ONLY_BC="--full --reads 4000000 --steps 2 --barcode-pairs 50000000 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-umi-extra --no-filters-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
     i=0
     for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
                "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT"; do
@@ -83,7 +83,7 @@ for w in $WHAT; do
     find $O/bcsq -name '*counter_collection.csv' -delete
     ;;
   tiles)
-    ONLY_TILES="--steps 2 --barcode-pairs 50000000 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-umi-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
+    ONLY_TILES="--full --steps 2 --barcode-pairs 50000000 --no-cpu-baseline --no-e2e --no-index-extra --no-dedup-extra --no-umi-extra --no-shapes-extra --no-tags-extra --no-filterpair-extra"
     for c in FETCH_SIZE WRITE_SIZE; do
       rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/tiles_pmc_$c -o pmc -- python3 $R/bench.py $ONLY_TILES > $O/tiles_pmc_$c.json 2> $O/tiles_pmc_$c.err
       find $O/tiles_pmc_$c -name '*kernel_trace.csv' -delete
