@@ -9,6 +9,7 @@
 #include <cmath>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -696,6 +697,14 @@ void init_call_state(fqg_ctx* c) {
   *c->h_cs = init;
 }
 
+// "call state back to the host and wait" - `also`: eight more bytes (of the line index) in the same wait
+int read_call_state(fqg_ctx* c, const uint64_t* also = nullptr, uint64_t* also_to = nullptr) {
+  HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
+  if (also) HIP_TRY(c, hipMemcpyAsync(also_to, also, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // Two passes over the image: newline census per chunk, prefix over the counts, then the line
 // index (with or without the byte-class checks).  Sizes every buffer exactly.
 int frame_two_pass(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n_chunks, bool final,
@@ -719,8 +728,7 @@ int frame_two_pass(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n
     hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->span_sums.p,
                        n_spans, d_img, nbytes, c->d_cs);
   }
-  HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = read_call_state(c))) return rc;
   out->n_newlines = c->h_cs->n_newlines;
   out->last_nl = c->h_cs->last_byte_is_nl != 0;
   out->img_flags = c->h_cs->flags;
@@ -731,27 +739,22 @@ int frame_two_pass(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n
   const bool checks = want_checks && !(out->img_flags & (kFlagNul | kFlagCr));
   const unsigned grid = (unsigned)std::min<uint64_t>((n_chunks + 3) / 4, (uint64_t)c->cu_count * 8);
   ProfScope ps(c, checks ? "k_frame_fast" : "k_lines");
-  if (checks)
-    hipLaunchKernelGGL(k_frame_fast_t<0u>, dim3(grid), dim3(kBlock), 0, c->stream, d_img, nbytes, n_chunks,
+  // one argument list for both: with the checks (and the records they cover: `limit`) or the line index alone
+  auto launch = [&](auto kernel, uint64_t limit) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, c->stream, d_img, nbytes, n_chunks,
                        (const uint32_t*)c->tile_local.p, (const unsigned long long*)c->span_sums.p,
-                       (uint64_t*)c->line_end.p, line_cap, 4 * (usable / 4), sm, c->d_cs, (const uint32_t*)nullptr,
+                       (uint64_t*)c->line_end.p, line_cap, limit, sm, c->d_cs, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr);
-  else
-    hipLaunchKernelGGL(k_frame_fast_t<7u>, dim3(grid), dim3(kBlock), 0, c->stream, d_img, nbytes, n_chunks,
-                       (const uint32_t*)c->tile_local.p, (const unsigned long long*)c->span_sums.p,
-                       (uint64_t*)c->line_end.p, line_cap, (uint64_t)0, sm, c->d_cs, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr);
+  };
+  if (checks) launch(k_frame_fast_t<0u>, 4 * (usable / 4));
+  else launch(k_frame_fast_t<7u>, (uint64_t)0);
   out->checks_done = checks;
   return 0;
 }
 
-
 constexpr uint32_t kStreamBootBytes = kBootMax;   // prefix whose quality range seeds the range test (64 KiB: LDS of k_stream_boot)
 constexpr uint64_t kStreamQueueCap = 1ull << 20;
 
-// One pass over the image (see fqg_stream_kernels.hip).  Returns 1 when the image is not eligible
-// (NUL / CR bytes, bytes >= 0x80, more newlines per chunk than the staging area holds): the caller
-// then runs frame_two_pass, which also decides about the exact path.
 struct RecordDuties {  // what k_stream_lines needs from the caller of frame_stream
   int space;
   uint32_t weight;
@@ -760,110 +763,41 @@ struct RecordDuties {  // what k_stream_lines needs from the caller of frame_str
   int fmt, is_pe;  // name digests are made under the caller's file state
 };
 
-int frame_stream(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n_chunks, bool final, SuspectMap sm,
-                 const RecordDuties& rd, int want_names /* 0, 1 = records, 2 = digests */, bool want_index, Framed* out) {
-  int rc;
-  c->names_img = nullptr;
-  const uint32_t n_spans = (n_chunks + kScanSpan - 1) / kScanSpan;
-  if ((rc = ensure(c, c->tile_counts, (size_t)n_chunks * 4))) return rc;
-  if ((rc = ensure(c, c->tile_local, (size_t)n_chunks * 4))) return rc;
-  if ((rc = ensure(c, c->span_sums, (size_t)n_spans * 8))) return rc;
-  if ((rc = ensure(c, c->cinfo, (size_t)n_chunks * 4))) return rc;
-  if ((rc = ensure(c, c->redo, (size_t)n_chunks * 4))) return rc;
-  if ((rc = ensure(c, c->stage, (size_t)n_chunks * kStageCap * 2))) return rc;
-  if ((rc = ensure(c, c->queue, (size_t)kStreamQueueCap * 8))) return rc;
-  init_call_state(c);
-  HIP_TRY(c, hipMemcpyAsync(c->d_cs, c->h_cs, sizeof(CallState), hipMemcpyHostToDevice, c->stream));
-  StreamOut so;
-  so.counts = (uint32_t*)c->tile_counts.p;
-  so.cinfo = (uint32_t*)c->cinfo.p;
-  so.stage = (uint16_t*)c->stage.p;
-  so.queue = (unsigned long long*)c->queue.p;
-  so.queue_cap = kStreamQueueCap;
-  {
-    ProfScope ps(c, "k_stream_boot");
-    const uint32_t span = (uint32_t)std::min<uint64_t>(kStreamBootBytes, nbytes & ~255ull);
-    hipLaunchKernelGGL(k_stream_boot, dim3(1), dim3(kBootBlock), 0, c->stream, d_img, span, c->d_cs);
-  }
+// how a run of the line kernels treats the line index: its room, and whether only the tail from `keep_from` is
+// stored (LinesArgs::no_index)
+struct IndexMode {
+  uint64_t* line_end;
+  uint64_t line_cap;
+  bool no_index;
+  uint64_t keep_from;
+};
+
+// What the phases of one frame_stream call share: the image and what the caller wants, then what each phase settles
+// for the ones behind it.  Lives for the call.
+struct StreamCall {
+  const uint8_t* img;
+  uint64_t nbytes;
+  uint32_t n_chunks, n_spans;
+  bool final;
+  SuspectMap sm;
+  RecordDuties rd;
+  int want_names;  // 0, 1 = records, 2 = digests
+  bool want_index;
+  StreamOut so{};
   NameCapture nc{};
-  if (want_names) {
-    // record slots per chunk from the mean record of the boot window: a power of two with a quarter of headroom
-    // (a chunk that sees more headers is read through the line index instead)
-    HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const uint32_t span = (uint32_t)std::min<uint64_t>(kStreamBootBytes, nbytes & ~255ull);
-    const double per_chunk = (double)(c->h_cs->boot_lines / 4 + 1) * (double)kChunkBytes / (double)std::max<uint32_t>(span, 1);
-    uint32_t shift = 3;
-    while (shift < 7 && (double)(1u << shift) < 1.25 * per_chunk + 1.0) ++shift;
-    nc.K = 1u << shift;
-    nc.fmt = rd.fmt;
-    nc.is_pe = rd.is_pe;
-    if ((rc = ensure(c, c->name_recs, ((size_t)n_chunks << shift) * (want_names == 2 ? kDigestWords : kNameRecWords) * 8))) return rc;
-    if ((rc = ensure(c, c->name_hcount, (size_t)n_chunks * 2))) return rc;
-    nc.recs = (unsigned long long*)c->name_recs.p;
-    nc.hcount = (uint16_t*)c->name_hcount.p;
-    c->names.k_shift = shift;
-  }
-  // Large images that only want to be validated take the pass in PARTS: pass 1 of part p shares its launch with the line
-  // workers of part p - 1 (k_stream_pass1_lines), whose statistics wait in accumulators of the context until the whole
-  // image has passed without a flag that sends it to the two-pass path.  FQGPU_STREAM_PARTS=1: one launch, as before.
-  // (read per call: tests and A/B runs switch them inside one process)
-  const int parts_env = env_int_early("FQGPU_STREAM_PARTS", 4);
-  const int workers_env = env_int_early("FQGPU_STREAM_LINE_WORKERS", 1);  // line-worker workgroups per CU
-  const uint32_t parts_min_spans = (uint32_t)std::max(env_int_early("FQGPU_STREAM_PARTS_MIN_SPANS", 24), 1);  // (16 MiB each)
-  static const bool old_pass2_early = getenv("FQGPU_STREAM_PASS2_OLD") != nullptr;
-  // (with the index wanted - the name modes - the line workers store it as they go, into room sized from the boot window)
-  uint32_t n_parts = ((want_names || !want_index) && !old_pass2_early && rd.acc && n_spans >= parts_min_spans)
-                         ? (uint32_t)std::min(std::max(parts_env, 1), 4) : 1u;
-  n_parts = std::min(n_parts, n_spans);
-  uint64_t early_line_cap = 0;
-  if (n_parts > 1 && want_index) {
-    // lines of the image from the lines of the boot window (the name modes have waited for it above), a quarter more
-    const uint32_t span = (uint32_t)std::min<uint64_t>(kStreamBootBytes, nbytes & ~255ull);
-    const double per_byte = (double)(c->h_cs->boot_lines + 4) / (double)std::max<uint32_t>(span, 1);
-    early_line_cap = (uint64_t)(per_byte * 1.25 * (double)nbytes) + 4096;
-    if ((rc = ensure(c, c->line_end, (size_t)early_line_cap * 8))) return rc;
-  }
+  ChunkRanks cr{};
+  // the plan of the parts
+  uint32_t n_parts = 1;
+  int last_pct = 16;
+  uint64_t early_line_cap = 0;  // room of the line index sized from the boot window (the line workers store into it)
+  uint64_t todo_steps_cap = 0;  // marks of the general line kernel made ready in front of the pass
   LinesArgs PA{};  // what the line workers inside the pass-1 launches go by (the rest comes from the call state)
-  uint64_t todo_steps_cap = 0;
-  if (n_parts > 1) {
-    if (!c->pipe_hist) {
-      if (!c->pipe_acc) HIP_TRY(c, hipMalloc((void**)&c->pipe_acc, sizeof(AccState)));
-      HIP_TRY(c, hipMalloc((void**)&c->pipe_hist, sizeof(unsigned long long) * FQG_MAX_READ_LENGTH));
-      HIP_TRY(c, hipMemsetAsync(c->pipe_hist, 0, sizeof(unsigned long long) * FQG_MAX_READ_LENGTH, c->stream));
-      hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
-      c->pipe_dirty = false;
-    }
-    if (c->pipe_dirty) {
-      hipLaunchKernelGGL(k_acc_merge, dim3(64), dim3(kBlock), 0, c->stream, c->pipe_acc, c->pipe_hist, (AccState*)nullptr,
-                         (unsigned long long*)nullptr, 1);
-      hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
-    }
-    c->pipe_dirty = true;
-    // one mark per step for the general line kernel: every line has a byte, 512 lines a step
-    todo_steps_cap = nbytes / (uint64_t)(4 * kWave * kLinesPer) + 8;
-    if ((rc = ensure(c, c->lines_slow, (size_t)todo_steps_cap + 4))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->lines_slow.p, 0, (size_t)todo_steps_cap, c->stream));
-    PA.img = d_img;
-    PA.n = nbytes;
-    PA.cr.counts = (const uint32_t*)c->tile_counts.p;
-    PA.cr.local = (const uint32_t*)c->tile_local.p;
-    PA.cr.span_excl = (const unsigned long long*)c->span_sums.p;
-    PA.stage = (const uint16_t*)c->stage.p;
-    PA.line_end = want_index ? (uint64_t*)c->line_end.p : nullptr;
-    PA.line_cap = want_index ? early_line_cap : ~0ull;
-    PA.suspect_bits = sm.bits;
-    PA.suspect_cap = sm.cap;
-    PA.flags = sm.flags;
-    PA.space = rd.space;
-    PA.weight = rd.weight;
-    PA.acc = c->pipe_acc;
-    PA.hist = c->pipe_hist;
-    PA.ablate = 0;
-    PA.no_index = want_index ? 0u : 1u;
-    PA.index_only = 0u;
-    PA.keep_from = ~0ull;
-  }
+  // known once the pass is through
+  uint64_t n_newlines = 0, n_lines_all = 0, line_cap = 0, limit = 0;
+  bool index_lost = false;
+
+  // the boot window: what k_stream_boot reads, and what the estimates from its line count go by
+  uint32_t boot_span() const { return (uint32_t)std::min<uint64_t>(kStreamBootBytes, nbytes & ~255ull); }
   // The LAST part is the small one: its line work has no pass-1 launch behind it to hide in - it is what runs alone
   // at the end of the call - while the line work of the parts before it runs inside the next part's launch at next to no
   // cost.  FQGPU_STREAM_LAST_PART_PCT (default 16: parts of 28 / 28 / 28 / 16 % of the image; 25: equal parts, as this was
@@ -872,203 +806,277 @@ int frame_stream(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n_c
   // pass 1 of the last part no longer outlasts the line workers of the part before).
   // (The name modes, whose line workers store the line index as they go, like it too - the pass with digests, one box, two
   // runs each: 25 % 10.10 / 10.12 ms + 0.34 behind it, 16 % 10.01 / 10.06 + 0.26.  Boxes differ by more than that.)
-  const int last_pct = std::min(std::max(env_int_early("FQGPU_STREAM_LAST_PART_PCT", 16), 1), 100);
-  auto part_begin = [&](uint32_t part) -> uint32_t {
+  uint32_t part_begin(uint32_t part) const {  // in spans
     if (part == 0 || n_parts <= 1) return part == 0 ? 0u : n_spans;
     if (part >= n_parts) return n_spans;
     const uint32_t last = std::min<uint32_t>(n_spans - (n_parts - 1), std::max<uint32_t>(1u, (uint32_t)((uint64_t)n_spans * (uint32_t)last_pct / 100u)));
     return (uint32_t)((uint64_t)(n_spans - last) * part / (n_parts - 1));
-  };
-  for (uint32_t part = 0; part < n_parts; ++part) {
-    const uint32_t span_lo = part_begin(part), span_hi = part_begin(part + 1);
-    const uint32_t chunk_lo = span_lo * kScanSpan, chunk_hi = std::min<uint32_t>(n_chunks, span_hi * kScanSpan);
-    {
-      ProfScope ps(c, want_names == 2 ? (part ? "k_stream_pass1_lines(digests)" : "k_stream_pass1(digests)")
-                      : want_names    ? (part ? "k_stream_pass1_lines(names)" : "k_stream_pass1(names)")
-                      : part          ? "k_stream_pass1_lines" : "k_stream_pass1");
-      const unsigned blocks = (chunk_hi - chunk_lo + 3) / 4;
-      const unsigned workers = (unsigned)c->cu_count * (unsigned)std::min(std::max(workers_env, 1), 4);
-#define FQG_PASS1_PART(N)                                                                                                    \
-  do {                                                                                                                       \
-    if (part == 0)                                                                                                           \
-      hipLaunchKernelGGL((k_stream_pass1<0u, N>), dim3(blocks), dim3(kBlock), 0, c->stream, d_img, nbytes, chunk_hi, so,      \
-                         c->d_cs, nc);                                                                                       \
-    else                                                                                                                     \
-      hipLaunchKernelGGL(k_stream_pass1_lines<N>, dim3(workers + blocks), dim3(kBlock), 0, c->stream, d_img, nbytes, chunk_lo, \
-                         chunk_hi, so, c->d_cs, PA, (uint8_t*)c->lines_slow.p, workers, part - 1, nc);                        \
-  } while (0)
-      if (want_names == 2) FQG_PASS1_PART(2);
-      else if (want_names) FQG_PASS1_PART(1);
-      else FQG_PASS1_PART(0);
-#undef FQG_PASS1_PART
-    }
-    {
-      ProfScope ps(c, "k_scan");
-      // (two launches: ONE, with the workgroup that finishes last doing phase B, was tried - the release fence every
-      // workgroup needs in front of its count writes the L2 back: 0.21 ms a step instead of 0.11)
-      hipLaunchKernelGGL(k_scan_a, dim3(span_hi - span_lo), dim3(kBlock), 0, c->stream, (const uint32_t*)c->tile_counts.p,
-                         n_chunks, (uint32_t*)c->tile_local.p, (unsigned long long*)c->span_sums.p, span_lo);
-      hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->span_sums.p,
-                         span_hi, d_img, nbytes, c->d_cs, span_lo, part);
-    }
   }
-  // (leaving the parted pass without its statistics: the scratch is cleared, nothing reaches the caller's accumulator)
-  auto drop_parted = [&]() {
-    if (n_parts > 1) {
-      hipLaunchKernelGGL(k_acc_merge, dim3(64), dim3(kBlock), 0, c->stream, c->pipe_acc, c->pipe_hist, (AccState*)nullptr,
-                         (unsigned long long*)nullptr, 1);
-      hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
-      c->pipe_dirty = false;
-    }
-  };
-  HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->h_cs->flags & (kFlagNul | kFlagCr | kFlagHigh | kFlagStageOverflow)) {
-    drop_parted();
-    return 1;
-  }
-  out->n_newlines = c->h_cs->n_newlines;
-  out->last_nl = c->h_cs->last_byte_is_nl != 0;
-  out->img_flags = 0;
-  const uint64_t n_lines_all = out->n_newlines + (out->last_nl ? 0 : 1);
-  const uint64_t usable = (final || out->last_nl) ? n_lines_all : out->n_newlines;
-  const uint64_t line_cap = n_lines_all + 17;
-  const uint64_t limit = 4 * (usable / 4);
-  // (the parted pass of a name mode: its line workers have stored index entries already - into room sized from the
-  // boot window.  Too small after all: a new allocation, and their stores once more, below)
-  const bool index_lost = early_line_cap && (size_t)line_cap * 8 > c->line_end.cap;
-  if ((rc = ensure(c, c->line_end, (size_t)line_cap * 8))) return rc;
-  static const bool old_pass2 = getenv("FQGPU_STREAM_PASS2_OLD") != nullptr;  // (A/B: the chunk-owned second pass)
-  if (old_pass2) {
-    ProfScope ps(c, "k_stream_pass2");
-    const unsigned per_wg = (kBlock / kWave) * kP2Batch;
-    hipLaunchKernelGGL(k_stream_pass2, dim3((n_chunks + per_wg - 1) / per_wg), dim3(kBlock), 0, c->stream, d_img, nbytes, n_chunks,
-                       (const uint32_t*)c->tile_counts.p, (const uint32_t*)c->cinfo.p, (const uint16_t*)c->stage.p,
-                       (const uint32_t*)c->tile_local.p, (const unsigned long long*)c->span_sums.p,
-                       (uint64_t*)c->line_end.p, line_cap, limit, sm, (uint32_t*)c->redo.p, c->d_cs);
-  } else {
-    ChunkRanks cr;
-    cr.counts = (const uint32_t*)c->tile_counts.p;
-    cr.local = (const uint32_t*)c->tile_local.p;
-    cr.span_excl = (const unsigned long long*)c->span_sums.p;
-    cr.n_chunks = n_chunks;
-    {
-      ProfScope ps(c, "k_stream_chunks");
-      hipLaunchKernelGGL(k_stream_chunks, dim3((n_chunks + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cr,
-                         (const uint32_t*)c->cinfo.p, limit, (uint32_t*)c->redo.p, c->d_cs);
-    }
-    LinesArgs A;
-    A.img = d_img;
+  // The arguments of the line kernels of this call.  What its variations differ in is named here or where they are
+  // made: the chunk ranks, where the statistics go (null: none), and the index mode.  n_newlines / n_lines / limit /
+  // ablate stay zero: the line workers inside the pass-1 launches take them from the call state; who launches behind
+  // the pass sets them.
+  LinesArgs lines_args(const fqg_ctx* c, const ChunkRanks& cr, AccState* acc, unsigned long long* hist, const IndexMode& ix) const {
+    LinesArgs A{};
+    A.img = img;
     A.n = nbytes;
     A.cr = cr;
     A.stage = (const uint16_t*)c->stage.p;
-    A.line_end = (uint64_t*)c->line_end.p;
-    A.line_cap = line_cap;
-    A.n_newlines = out->n_newlines;
-    A.n_lines = n_lines_all;
-    A.limit = limit;
+    A.line_end = ix.line_end;
+    A.line_cap = ix.line_cap;
     A.suspect_bits = sm.bits;
     A.suspect_cap = sm.cap;
     A.flags = sm.flags;
     A.space = rd.space;
     A.weight = rd.weight;
-    A.acc = rd.acc;
-    A.hist = rd.hist;
-    static const int lines_abl = measure_int("FQGPU_LINES_ABL");
-    A.ablate = lines_abl;
-    // the index on demand: when the caller has not said it wants it, and nothing queued by pass 1 needs it (the
-    // queue kernel finds its records through the index).  FQGPU_EAGER_INDEX=1: always in this call (A/B)
-    static const bool eager_index = getenv("FQGPU_EAGER_INDEX") != nullptr;
-    const bool lazy = !want_index && !eager_index && c->h_cs->queue_count == 0;
-    A.no_index = lazy ? 1u : 0u;
+    A.acc = acc;
+    A.hist = hist;
+    A.no_index = ix.no_index ? 1u : 0u;
     A.index_only = 0u;
-    A.keep_from = limit >= 8 ? limit - 8 : 0;
-    c->lazy.pending = false;
-    // the steps the line workers inside the pass-1 launches have done (the parted pass): the launches below begin behind
-    // them, and every line kernel of such a call adds to the context's accumulators, merged at the end
-    const uint64_t done_steps = n_parts > 1 ? c->h_cs->lines_done_steps : 0;
-    if (n_parts > 1) {
-      A.acc = c->pipe_acc;
-      A.hist = c->pipe_hist;
-    }
-    {
-      ProfScope ps(c, "k_stream_lines");
-      const uint64_t groups = (n_lines_all + 4 * kWave - 1) / (4 * kWave);
-      // a persistent grid: every workgroup must be resident from the start (one that is not would do its whole
-      // share after the others have finished)
-      if (!c->lines_per_cu) {  // (per context: a context is one device, and contexts run on threads of their own)
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k_stream_lines<false>), kBlock, 0) != hipSuccess || nb < 1)
-          nb = 4;
-        c->lines_per_cu = nb;
-      }
-      const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((groups + 3) / 4, (uint64_t)c->cu_count * c->lines_per_cu));
-      static const bool general_only = getenv("FQGPU_LINES_GENERAL") != nullptr;  // (A/B: every step through the general kernel)
-      // (more than 64 newlines in an average chunk - reads below 100 bases - or fewer than 32 - reads of kilobases: hardly a
-      // step would qualify for the kernel without a search)
-      const double nl_per_chunk = (double)out->n_newlines / (double)std::max<uint32_t>(n_chunks, 1);
-      c->lazy.grid = grid;
-      c->lazy.fast = false;
-      if (done_steps == 0 && (general_only || nl_per_chunk > 60.0 || nl_per_chunk < 32.0)) {
-        hipLaunchKernelGGL(k_stream_lines<false>, dim3(grid), dim3(kBlock), 0, c->stream, A, (const uint8_t*)nullptr);
-      } else {
-        // the steps of ordinary records in the kernel without a search, what it marks in the general one behind it
-        const uint64_t n_steps = (groups + kLinesPer - 1) / kLinesPer;
-        if (n_parts > 1 && n_steps + 4 > todo_steps_cap) return fail(c, FQG_ERR_STATE, "streaming pass: more steps than lines");
-        if (n_parts == 1) {
-          if ((rc = ensure(c, c->lines_slow, (size_t)n_steps + 4))) return rc;
-          HIP_TRY(c, hipMemsetAsync(c->lines_slow.p, 0, (size_t)n_steps, c->stream));
-        }
-        if (!c->lines_fast_per_cu) {
-          int nb = 0;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k_stream_lines_fast), kBlock, 0) != hipSuccess || nb < 1)
-            nb = 4;
-          c->lines_fast_per_cu = nb;
-        }
-        const unsigned grid_f = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_steps - std::min(done_steps, n_steps) + 3) / 4, (uint64_t)c->cu_count * c->lines_fast_per_cu));
-        if (done_steps && !lazy && (!early_line_cap || index_lost)) {
-          // the index is wanted after all (pass 1 queued byte positions), or its room was too small: the stores of the
-          // steps that are done
-          LinesArgs I = A;
-          I.index_only = 1u;
-          I.acc = nullptr;
-          I.hist = nullptr;
-          I.step_lo = 0;
-          I.step_hi = done_steps;
-          const unsigned grid_i = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((done_steps + 3) / 4, (uint64_t)c->cu_count * c->lines_fast_per_cu));
-          hipLaunchKernelGGL(k_stream_lines_fast, dim3(grid_i), dim3(kBlock), 0, c->stream, I, (uint8_t*)c->lines_slow.p);
-        }
-        LinesArgs F = A;
-        F.step_lo = done_steps;
-        F.step_hi = 0;
-        hipLaunchKernelGGL(k_stream_lines_fast, dim3(grid_f), dim3(kBlock), 0, c->stream, F, (uint8_t*)c->lines_slow.p);
-        hipLaunchKernelGGL(k_stream_lines<true>, dim3(grid), dim3(kBlock), 0, c->stream, A, (const uint8_t*)c->lines_slow.p);
-        c->lazy.grid_f = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_steps + 3) / 4, (uint64_t)c->cu_count * c->lines_fast_per_cu));
-        c->lazy.fast = true;
-      }
-    }
-    if (n_parts > 1) {
-      ProfScope ps(c, "k_acc_merge");
-      hipLaunchKernelGGL(k_acc_merge, dim3(64), dim3(kBlock), 0, c->stream, c->pipe_acc, c->pipe_hist, rd.acc, rd.hist, 0);
-      hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
-      c->pipe_dirty = false;
-      A.acc = rd.acc;
-      A.hist = rd.hist;
-    }
-    if (lazy) {
-      c->lazy.pending = true;
-      c->lazy.args = A;
-      c->lazy.args.no_index = 0u;
-      c->lazy.args.index_only = 1u;
-      c->lazy.args.acc = nullptr;
-      c->lazy.args.hist = nullptr;
-    }
-    out->records_done = true;
+    A.keep_from = ix.keep_from;
+    return A;
   }
-  if (!c->lazy.pending) {  // (on demand only when pass 1 queued nothing: see above)
+};
+
+ChunkRanks chunk_ranks(const fqg_ctx* c, uint32_t n_chunks) {
+  ChunkRanks cr;
+  cr.counts = (const uint32_t*)c->tile_counts.p;
+  cr.local = (const uint32_t*)c->tile_local.p;
+  cr.span_excl = (const unsigned long long*)c->span_sums.p;
+  cr.n_chunks = n_chunks;
+  return cr;
+}
+
+// the statistics of the parted pass: folded into `dst` (null: nowhere - the pass is left without them, nothing reaches
+// the caller's accumulator), and the scratch cleared
+void fold_parted(fqg_ctx* c, AccState* dst, unsigned long long* dst_hist) {
+  hipLaunchKernelGGL(k_acc_merge, dim3(64), dim3(kBlock), 0, c->stream, c->pipe_acc, c->pipe_hist, dst, dst_hist, dst ? 0 : 1);
+  hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
+  c->pipe_dirty = false;
+}
+
+// workgroups of `kernel` a CU holds, asked once
+// (per context: a context is one device, and contexts run on threads of their own)
+int resident_per_cu(int& asked, const void* kernel) {
+  if (!asked) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, 0) != hipSuccess || nb < 1) nb = 4;
+    asked = nb;
+  }
+  return asked;
+}
+
+// phase 1: the buffers, the call state, the quality range of the boot window
+int stream_begin(fqg_ctx* c, StreamCall& s) {
+  int rc;
+  if ((rc = ensure(c, c->tile_counts, (size_t)s.n_chunks * 4))) return rc;
+  if ((rc = ensure(c, c->tile_local, (size_t)s.n_chunks * 4))) return rc;
+  if ((rc = ensure(c, c->span_sums, (size_t)s.n_spans * 8))) return rc;
+  if ((rc = ensure(c, c->cinfo, (size_t)s.n_chunks * 4))) return rc;
+  if ((rc = ensure(c, c->redo, (size_t)s.n_chunks * 4))) return rc;
+  if ((rc = ensure(c, c->stage, (size_t)s.n_chunks * kStageCap * 2))) return rc;
+  if ((rc = ensure(c, c->queue, (size_t)kStreamQueueCap * 8))) return rc;
+  init_call_state(c);
+  HIP_TRY(c, hipMemcpyAsync(c->d_cs, c->h_cs, sizeof(CallState), hipMemcpyHostToDevice, c->stream));
+  s.so.counts = (uint32_t*)c->tile_counts.p;
+  s.so.cinfo = (uint32_t*)c->cinfo.p;
+  s.so.stage = (uint16_t*)c->stage.p;
+  s.so.queue = (unsigned long long*)c->queue.p;
+  s.so.queue_cap = kStreamQueueCap;
+  s.cr = chunk_ranks(c, s.n_chunks);
+  ProfScope ps(c, "k_stream_boot");
+  hipLaunchKernelGGL(k_stream_boot, dim3(1), dim3(kBootBlock), 0, c->stream, s.img, s.boot_span(), c->d_cs);
+  return 0;
+}
+
+// phase 2 (name modes): record slots per chunk from the mean record of the boot window: a power of two with a quarter
+// of headroom (a chunk that sees more headers is read through the line index instead)
+int stream_name_setup(fqg_ctx* c, StreamCall& s) {
+  int rc;
+  if ((rc = read_call_state(c))) return rc;
+  const double per_chunk = (double)(c->h_cs->boot_lines / 4 + 1) * (double)kChunkBytes / (double)std::max<uint32_t>(s.boot_span(), 1);
+  uint32_t shift = 3;
+  while (shift < 7 && (double)(1u << shift) < 1.25 * per_chunk + 1.0) ++shift;
+  s.nc.K = 1u << shift;
+  s.nc.fmt = s.rd.fmt;
+  s.nc.is_pe = s.rd.is_pe;
+  if ((rc = ensure(c, c->name_recs, ((size_t)s.n_chunks << shift) * (s.want_names == 2 ? kDigestWords : kNameRecWords) * 8))) return rc;
+  if ((rc = ensure(c, c->name_hcount, (size_t)s.n_chunks * 2))) return rc;
+  s.nc.recs = (unsigned long long*)c->name_recs.p;
+  s.nc.hcount = (uint16_t*)c->name_hcount.p;
+  c->names.k_shift = shift;
+  return 0;
+}
+
+// phase 3: the plan of the parts.
+// Large images that only want to be validated take the pass in PARTS: pass 1 of part p shares its launch with the line
+// workers of part p - 1 (k_stream_pass1_lines), whose statistics wait in accumulators of the context until the whole
+// image has passed without a flag that sends it to the two-pass path.  FQGPU_STREAM_PARTS=1: one launch, as before.
+// (read per call: tests and A/B runs switch them inside one process)
+int stream_plan_parts(fqg_ctx* c, StreamCall& s) {
+  int rc;
+  const int parts_env = env_int_early("FQGPU_STREAM_PARTS", 4);
+  const uint32_t parts_min_spans = (uint32_t)std::max(env_int_early("FQGPU_STREAM_PARTS_MIN_SPANS", 24), 1);  // (16 MiB each)
+  // (with the index wanted - the name modes - the line workers store it as they go, into room sized from the boot window)
+  s.n_parts = ((s.want_names || !s.want_index) && s.rd.acc && s.n_spans >= parts_min_spans)
+                  ? (uint32_t)std::min(std::max(parts_env, 1), 4) : 1u;
+  s.n_parts = std::min(s.n_parts, s.n_spans);
+  s.last_pct = std::min(std::max(env_int_early("FQGPU_STREAM_LAST_PART_PCT", 16), 1), 100);  // (see StreamCall::part_begin)
+  if (s.n_parts <= 1) return 0;
+  if (s.want_index) {
+    // lines of the image from the lines of the boot window (the name modes have waited for it above), a quarter more
+    const double per_byte = (double)(c->h_cs->boot_lines + 4) / (double)std::max<uint32_t>(s.boot_span(), 1);
+    s.early_line_cap = (uint64_t)(per_byte * 1.25 * (double)s.nbytes) + 4096;
+    if ((rc = ensure(c, c->line_end, (size_t)s.early_line_cap * 8))) return rc;
+  }
+  if (!c->pipe_hist) {
+    if (!c->pipe_acc) HIP_TRY(c, hipMalloc((void**)&c->pipe_acc, sizeof(AccState)));
+    HIP_TRY(c, hipMalloc((void**)&c->pipe_hist, sizeof(unsigned long long) * FQG_MAX_READ_LENGTH));
+    HIP_TRY(c, hipMemsetAsync(c->pipe_hist, 0, sizeof(unsigned long long) * FQG_MAX_READ_LENGTH, c->stream));
+    hipLaunchKernelGGL(k_acc_scratch_reset, dim3(1), dim3(1), 0, c->stream, c->pipe_acc);
+    c->pipe_dirty = false;
+  }
+  if (c->pipe_dirty) fold_parted(c, nullptr, nullptr);  // (a parted pass left without its merge: an error in between)
+  c->pipe_dirty = true;
+  // one mark per step for the general line kernel: every line has a byte, 512 lines a step
+  s.todo_steps_cap = s.nbytes / (uint64_t)(4 * kWave * kLinesPer) + 8;
+  if ((rc = ensure(c, c->lines_slow, (size_t)s.todo_steps_cap + 4))) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->lines_slow.p, 0, (size_t)s.todo_steps_cap, c->stream));
+  // the line workers: no chunk count (their launch has it), statistics to the scratch, the whole index or none of it
+  s.PA = s.lines_args(c, chunk_ranks(c, 0), c->pipe_acc, c->pipe_hist,
+                    s.want_index ? IndexMode{(uint64_t*)c->line_end.p, s.early_line_cap, false, ~0ull}
+                                 : IndexMode{nullptr, ~0ull, true, ~0ull});
+  return 0;
+}
+
+// phase 4: pass 1, part by part (from the second on with the line workers of the part before), and the prefix over
+// each part's newline counts
+void stream_pass1_parts(fqg_ctx* c, const StreamCall& s) {
+  const int workers_env = env_int_early("FQGPU_STREAM_LINE_WORKERS", 1);  // line-worker workgroups per CU (read per call)
+  const unsigned workers = (unsigned)c->cu_count * (unsigned)std::min(std::max(workers_env, 1), 4);
+  for (uint32_t part = 0; part < s.n_parts; ++part) {
+    const uint32_t span_lo = s.part_begin(part), span_hi = s.part_begin(part + 1);
+    const uint32_t chunk_lo = span_lo * kScanSpan, chunk_hi = std::min<uint32_t>(s.n_chunks, span_hi * kScanSpan);
+    const unsigned blocks = (chunk_hi - chunk_lo + 3) / 4;
+    {
+      ProfScope ps(c, s.want_names == 2 ? (part ? "k_stream_pass1_lines(digests)" : "k_stream_pass1(digests)")
+                      : s.want_names    ? (part ? "k_stream_pass1_lines(names)" : "k_stream_pass1(names)")
+                      : part            ? "k_stream_pass1_lines" : "k_stream_pass1");
+#define FQG_PASS1_PART(N)                                                                                                    \
+  do {                                                                                                                       \
+    if (part == 0)                                                                                                           \
+      hipLaunchKernelGGL((k_stream_pass1<0u, N>), dim3(blocks), dim3(kBlock), 0, c->stream, s.img, s.nbytes, chunk_hi, s.so,  \
+                         c->d_cs, s.nc);                                                                                     \
+    else                                                                                                                     \
+      hipLaunchKernelGGL(k_stream_pass1_lines<N>, dim3(workers + blocks), dim3(kBlock), 0, c->stream, s.img, s.nbytes,       \
+                         chunk_lo, chunk_hi, s.so, c->d_cs, s.PA, (uint8_t*)c->lines_slow.p, workers, part - 1, s.nc);       \
+  } while (0)
+      if (s.want_names == 2) FQG_PASS1_PART(2);
+      else if (s.want_names) FQG_PASS1_PART(1);
+      else FQG_PASS1_PART(0);
+#undef FQG_PASS1_PART
+    }
+    ProfScope ps(c, "k_scan");
+    // (two launches: ONE, with the workgroup that finishes last doing phase B, was tried - the release fence every
+    // workgroup needs in front of its count writes the L2 back: 0.21 ms a step instead of 0.11)
+    hipLaunchKernelGGL(k_scan_a, dim3(span_hi - span_lo), dim3(kBlock), 0, c->stream, (const uint32_t*)c->tile_counts.p,
+                       s.n_chunks, (uint32_t*)c->tile_local.p, (unsigned long long*)c->span_sums.p, span_lo);
+    hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->span_sums.p,
+                       span_hi, s.img, s.nbytes, c->d_cs, span_lo, part);
+  }
+}
+
+// phase 6: the per-chunk duties, then the line kernels behind the parts, the merge of the parted statistics and the
+// record of what an index on demand would run
+int stream_lines(fqg_ctx* c, const StreamCall& s) {
+  int rc;
+  {
+    ProfScope ps(c, "k_stream_chunks");
+    hipLaunchKernelGGL(k_stream_chunks, dim3((s.n_chunks + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, s.cr,
+                       (const uint32_t*)c->cinfo.p, s.limit, (uint32_t*)c->redo.p, c->d_cs);
+  }
+  // the index on demand: when the caller has not said it wants it, and nothing queued by pass 1 needs it (the
+  // queue kernel finds its records through the index).  FQGPU_EAGER_INDEX=1: always in this call (A/B)
+  static const bool eager_index = getenv("FQGPU_EAGER_INDEX") != nullptr;
+  const bool lazy = !s.want_index && !eager_index && c->h_cs->queue_count == 0;
+  // the steps the line workers inside the pass-1 launches have done (the parted pass): the launches below begin behind
+  // them, and every line kernel of such a call adds to the context's accumulators, merged at the end
+  const bool parted = s.n_parts > 1;
+  const uint64_t done_steps = parted ? c->h_cs->lines_done_steps : 0;
+  static const int lines_abl = measure_int("FQGPU_LINES_ABL");
+  LinesArgs A = s.lines_args(c, s.cr, parted ? c->pipe_acc : s.rd.acc, parted ? c->pipe_hist : s.rd.hist,
+                           IndexMode{(uint64_t*)c->line_end.p, s.line_cap, lazy, s.limit >= 8 ? s.limit - 8 : 0});
+  A.n_newlines = s.n_newlines;
+  A.n_lines = s.n_lines_all;
+  A.limit = s.limit;
+  A.ablate = lines_abl;
+  c->lazy.pending = false;
+  {
+    ProfScope ps(c, "k_stream_lines");
+    const uint64_t groups = (s.n_lines_all + 4 * kWave - 1) / (4 * kWave);
+    // a persistent grid: every workgroup must be resident from the start (one that is not would do its whole
+    // share after the others have finished)
+    const uint64_t per_gpu = (uint64_t)c->cu_count * resident_per_cu(c->lines_per_cu, reinterpret_cast<const void*>(k_stream_lines<false>));
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((groups + 3) / 4, per_gpu));
+    static const bool general_only = getenv("FQGPU_LINES_GENERAL") != nullptr;  // (A/B: every step through the general kernel)
+    // (more than 64 newlines in an average chunk - reads below 100 bases - or fewer than 32 - reads of kilobases: hardly a
+    // step would qualify for the kernel without a search)
+    const double nl_per_chunk = (double)s.n_newlines / (double)std::max<uint32_t>(s.n_chunks, 1);
+    c->lazy.grid = grid;
+    c->lazy.fast = false;
+    if (done_steps == 0 && (general_only || nl_per_chunk > 60.0 || nl_per_chunk < 32.0)) {
+      hipLaunchKernelGGL(k_stream_lines<false>, dim3(grid), dim3(kBlock), 0, c->stream, A, (const uint8_t*)nullptr);
+    } else {
+      // the steps of ordinary records in the kernel without a search, what it marks in the general one behind it
+      const uint64_t n_steps = (groups + kLinesPer - 1) / kLinesPer;
+      if (parted && n_steps + 4 > s.todo_steps_cap) return fail(c, FQG_ERR_STATE, "streaming pass: more steps than lines");
+      if (!parted) {
+        if ((rc = ensure(c, c->lines_slow, (size_t)n_steps + 4))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->lines_slow.p, 0, (size_t)n_steps, c->stream));
+      }
+      const uint64_t fast_per_gpu = (uint64_t)c->cu_count * resident_per_cu(c->lines_fast_per_cu, reinterpret_cast<const void*>(k_stream_lines_fast));
+      auto grid_fast = [&](uint64_t steps) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((steps + 3) / 4, fast_per_gpu)); };
+      if (done_steps && !lazy && (!s.early_line_cap || s.index_lost)) {
+        // the index is wanted after all (pass 1 queued byte positions), or its room was too small: the stores of the
+        // steps that are done
+        LinesArgs I = A;
+        I.index_only = 1u;
+        I.acc = nullptr;
+        I.hist = nullptr;
+        I.step_lo = 0;
+        I.step_hi = done_steps;
+        hipLaunchKernelGGL(k_stream_lines_fast, dim3(grid_fast(done_steps)), dim3(kBlock), 0, c->stream, I, (uint8_t*)c->lines_slow.p);
+      }
+      LinesArgs F = A;  // the steps behind the ones that are done, to the last
+      F.step_lo = done_steps;
+      F.step_hi = 0;
+      hipLaunchKernelGGL(k_stream_lines_fast, dim3(grid_fast(n_steps - std::min(done_steps, n_steps))), dim3(kBlock), 0, c->stream, F, (uint8_t*)c->lines_slow.p);
+      hipLaunchKernelGGL(k_stream_lines<true>, dim3(grid), dim3(kBlock), 0, c->stream, A, (const uint8_t*)c->lines_slow.p);
+      c->lazy.grid_f = grid_fast(n_steps);
+      c->lazy.fast = true;
+    }
+  }
+  if (parted) {
+    ProfScope ps(c, "k_acc_merge");
+    fold_parted(c, s.rd.acc, s.rd.hist);
+  }
+  if (lazy) {  // the same launches once more, stores only (index_now)
+    c->lazy.pending = true;
+    c->lazy.args = A;
+    c->lazy.args.no_index = 0u;
+    c->lazy.args.index_only = 1u;
+    c->lazy.args.acc = nullptr;
+    c->lazy.args.hist = nullptr;
+  }
+  return 0;
+}
+
+// phase 7: the suspect positions pass 1 queued, the chunks whose checks are repeated, the capture handed to the name kernels
+void stream_finish(fqg_ctx* c, const StreamCall& s) {
+  if (!c->lazy.pending) {  // (on demand only when pass 1 queued nothing: see stream_lines)
     ProfScope ps(c, "k_stream_queue");
     hipLaunchKernelGGL(k_stream_queue, dim3(64), dim3(kBlock), 0, c->stream, (const unsigned long long*)c->queue.p,
-                       (unsigned long long)kStreamQueueCap, (const uint64_t*)c->line_end.p, n_lines_all, limit / 4, sm,
+                       (unsigned long long)kStreamQueueCap, (const uint64_t*)c->line_end.p, s.n_lines_all, s.limit / 4, s.sm,
                        c->d_cs);
   }
   {
@@ -1077,29 +1085,60 @@ int frame_stream(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n_c
     ProfScope ps(c, "k_stream_redo");
     // (ordinary reads send a handful of chunks here - the ones whose speculation failed -, reads of kilobases a quarter of
     // all: a grid that fills the GPU costs 0.06 ms to start and end for the former)
-    const double nlpc = (double)out->n_newlines / (double)std::max<uint32_t>(n_chunks, 1);
-    const unsigned grid = (unsigned)std::min<uint64_t>((n_chunks + 3) / 4, (uint64_t)c->cu_count * (nlpc >= 32.0 ? 1 : 8));
-    hipLaunchKernelGGL(k_frame_fast_t<8u>, dim3(grid), dim3(kBlock), 0, c->stream, d_img, nbytes, n_chunks,
+    const double nlpc = (double)s.n_newlines / (double)std::max<uint32_t>(s.n_chunks, 1);
+    const unsigned grid = (unsigned)std::min<uint64_t>((s.n_chunks + 3) / 4, (uint64_t)c->cu_count * (nlpc >= 32.0 ? 1 : 8));
+    hipLaunchKernelGGL(k_frame_fast_t<8u>, dim3(grid), dim3(kBlock), 0, c->stream, s.img, s.nbytes, s.n_chunks,
                        (const uint32_t*)c->tile_local.p, (const unsigned long long*)c->span_sums.p,
-                       (uint64_t*)c->line_end.p, line_cap, limit, sm, c->d_cs, (const uint32_t*)c->redo.p,
+                       (uint64_t*)c->line_end.p, s.line_cap, s.limit, s.sm, c->d_cs, (const uint32_t*)c->redo.p,
                        (const uint32_t*)&c->d_cs->redo_count);
   }
-  out->checks_done = true;
-  if (want_names && !old_pass2) {
-    c->names.recs = nc.recs;
-    c->names.hcount = nc.hcount;
+  if (s.want_names) {
+    c->names.recs = s.nc.recs;
+    c->names.hcount = s.nc.hcount;
     c->names.cinfo = (const uint32_t*)c->cinfo.p;
-    c->names.cr.counts = (const uint32_t*)c->tile_counts.p;
-    c->names.cr.local = (const uint32_t*)c->tile_local.p;
-    c->names.cr.span_excl = (const unsigned long long*)c->span_sums.p;
-    c->names.cr.n_chunks = n_chunks;
-    c->names.K = nc.K;
-    c->names.digests = want_names == 2 ? 1u : 0u;
-    c->names.fmt = rd.fmt;
-    c->names.is_pe = rd.is_pe;
-    c->names_img = d_img;
-    c->names_nbytes = nbytes;
+    c->names.cr = s.cr;
+    c->names.K = s.nc.K;
+    c->names.digests = s.want_names == 2 ? 1u : 0u;
+    c->names.fmt = s.rd.fmt;
+    c->names.is_pe = s.rd.is_pe;
+    c->names_img = s.img;
+    c->names_nbytes = s.nbytes;
   }
+}
+
+// One pass over the image (see fqg_stream_kernels.hip), phase by phase in the order its launches go out.  Returns 1
+// when the image is not eligible (NUL / CR bytes, bytes >= 0x80, more newlines per chunk than the staging area
+// holds): the caller then runs frame_two_pass, which also decides about the exact path.
+int frame_stream(fqg_ctx* c, const uint8_t* d_img, uint64_t nbytes, uint32_t n_chunks, bool final, SuspectMap sm,
+                 const RecordDuties& rd, int want_names /* 0, 1 = records, 2 = digests */, bool want_index, Framed* out) {
+  int rc;
+  c->names_img = nullptr;
+  StreamCall s{d_img, nbytes, n_chunks, (n_chunks + kScanSpan - 1) / kScanSpan, final, sm, rd, want_names, want_index};
+  if ((rc = stream_begin(c, s))) return rc;
+  if (want_names && (rc = stream_name_setup(c, s))) return rc;
+  if ((rc = stream_plan_parts(c, s))) return rc;
+  stream_pass1_parts(c, s);
+  // phase 5: the flags of the whole image, its lines
+  if ((rc = read_call_state(c))) return rc;
+  if (c->h_cs->flags & (kFlagNul | kFlagCr | kFlagHigh | kFlagStageOverflow)) {
+    if (s.n_parts > 1) fold_parted(c, nullptr, nullptr);  // (not eligible: the two-pass path makes the statistics)
+    return 1;
+  }
+  out->n_newlines = s.n_newlines = c->h_cs->n_newlines;
+  out->last_nl = c->h_cs->last_byte_is_nl != 0;
+  out->img_flags = 0;
+  s.n_lines_all = s.n_newlines + (out->last_nl ? 0 : 1);
+  const uint64_t usable = (final || out->last_nl) ? s.n_lines_all : s.n_newlines;
+  s.line_cap = s.n_lines_all + 17;
+  s.limit = 4 * (usable / 4);
+  // (the parted pass of a name mode: its line workers have stored index entries already - into room sized from the
+  // boot window.  Too small after all: a new allocation, and their stores once more, in stream_lines)
+  s.index_lost = s.early_line_cap && (size_t)s.line_cap * 8 > c->line_end.cap;
+  if ((rc = ensure(c, c->line_end, (size_t)s.line_cap * 8))) return rc;
+  if ((rc = stream_lines(c, s))) return rc;
+  out->records_done = true;
+  stream_finish(c, s);
+  out->checks_done = true;
   return 0;
 }
 
@@ -1121,6 +1160,134 @@ int index_now(fqg_ctx* c) {
   return 0;
 }
 
+// What the steps of one fqg_validate call behind the framing share.
+struct ValidateCall {
+  FrameView fv;
+  const fqg_file_state* st;
+  fqg_acc* acc;  // null: no statistics
+  uint32_t weight;
+  SuspectMap sm;
+  bool frame_only;
+  uint64_t list_cap = 0;  // room of the list of records for the exact validator (the tiled paths)
+  bool tail_is_stop = false, nul_truncated = false;  // what find_stop saw
+};
+
+// what varies between the launches of k_validate_exact
+struct ExactRun {
+  unsigned grid;
+  bool listed;      // the records of the context's list (their number is read on the device), or every record
+  bool stats;       // into the caller's accumulator, or none
+  uint32_t weight;
+  uint64_t record;  // kNoRecord, or the one record whose finding's arguments are wanted
+};
+void launch_exact(fqg_ctx* c, const ValidateCall& v, const ExactRun& r, const char* scope /* null: none */) {
+  std::optional<ProfScope> ps;
+  if (scope) ps.emplace(c, scope);
+  const bool stats = r.stats && v.acc;
+  hipLaunchKernelGGL(k_validate_exact, dim3(r.grid), dim3(kBlock), 0, c->stream, v.fv, v.st->is_pe, v.st->readname_format,
+                     v.st->space, r.weight, stats ? v.acc->d_state : (AccState*)nullptr,
+                     stats ? v.acc->d_hist : (unsigned long long*)nullptr, c->d_cs, r.record,
+                     r.listed ? (const unsigned long long*)c->list.p : (const unsigned long long*)nullptr,
+                     r.listed ? (const unsigned long long*)&c->d_cs->list_count : (const unsigned long long*)nullptr);
+}
+
+// the gzgets limits, where the record-wise checks do not look: every line of an image that is only framed, and the
+// lines of an incomplete last record (the reference reads THOSE in pieces too before it finds the file truncated)
+void check_overlong(fqg_ctx* c, const FrameView& fv, uint64_t from, uint64_t upto) {
+  if (upto <= from) return;
+  ProfScope ps(c, "k_overlong");
+  FrameView lv = fv;
+  lv.n_lines = upto;
+  hipLaunchKernelGGL(k_overlong, dim3((unsigned)((upto - from + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, lv, from,
+                     c->d_cs);
+}
+
+// a record that starts with NUL ends the file silently (src/fastq.c:250): the records in front of it stand, and
+// v.fv.n_records says how many.  `tail`: lines of an incomplete last record that nothing more can follow
+int find_stop(fqg_ctx* c, ValidateCall& v, bool tail, fqg_validate_result* out) {
+  int rc;
+  uint64_t n_records = v.fv.n_records;
+  if (n_records) {
+    ProfScope ps(c, "k_find_stop");
+    hipLaunchKernelGGL(k_find_stop, dim3((unsigned)((n_records + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       c->stream, v.fv, c->d_cs, v.frame_only ? 1 : 0);
+  }
+  if (tail) {
+    // first byte of the incomplete trailing group
+    c->h_scalar[0] = ~0ull;
+    if ((rc = read_call_state(c, n_records ? v.fv.line_end + 4 * n_records - 1 : nullptr, &c->h_scalar[0]))) return rc;
+    const uint64_t at = c->h_scalar[0] + 1;
+    uint8_t b = 1;
+    HIP_TRY(c, hipMemcpy(&b, v.fv.img + at, 1, hipMemcpyDeviceToHost));
+    v.tail_is_stop = (b == 0);
+  } else if ((rc = read_call_state(c))) return rc;
+  if (c->h_cs->stop_record < n_records) {
+    n_records = c->h_cs->stop_record;
+    out->stopped = 1;
+  }
+  if (c->h_cs->trunc_record < n_records) {  // (frame-only: an earlier record with an empty line - the file is truncated THERE)
+    n_records = c->h_cs->trunc_record;
+    out->stopped = 0;
+    v.nul_truncated = true;
+  }
+  v.fv.n_records = n_records;
+  return 0;
+}
+
+// The tiled paths: the records the line kernels (or k_records_fast, behind the two-pass framing) could not vouch for
+// are listed, and the exact validator reads the list - unless the line index is still to be written: then once the
+// number of listed records is known, in fqg_validate
+int check_records(fqg_ctx* c, ValidateCall& v, bool records_done) {
+  int rc;
+  const uint64_t n_records = v.fv.n_records;
+  v.list_cap = std::max<uint64_t>(1u << 20, n_records / 16);
+  if (v.list_cap > n_records) v.list_cap = n_records;
+  if ((rc = ensure(c, c->list, (size_t)v.list_cap * 8))) return rc;
+  const unsigned grid_r =
+      (unsigned)std::min<uint64_t>((n_records + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 8);
+  if (records_done) {
+    ProfScope ps(c, "k_suspect_list");
+    hipLaunchKernelGGL(k_suspect_list, dim3((unsigned)std::min<uint64_t>((n_records / 32 + kBlock) / kBlock, 1024)), dim3(kBlock), 0,
+                       c->stream, (const uint32_t*)v.sm.bits, std::min<uint64_t>(n_records, v.sm.cap),
+                       (unsigned long long*)c->list.p, v.list_cap, &c->d_cs->list_count, v.acc ? v.acc->d_state : nullptr,
+                       (const CallState*)c->d_cs);
+  } else {
+    ProfScope ps(c, "k_records_fast");
+    hipLaunchKernelGGL(k_records_fast, dim3(grid_r), dim3(kBlock), 0, c->stream, v.fv, v.st->space, v.weight, v.sm,
+                       (unsigned long long*)c->list.p, v.list_cap, &c->d_cs->list_count,
+                       v.acc ? v.acc->d_state : nullptr, v.acc ? v.acc->d_hist : nullptr, c->d_cs);
+  }
+  if (!c->lazy.pending) launch_exact(c, v, {(unsigned)c->cu_count * 2, true, false, v.weight, kNoRecord}, "k_validate_exact");
+  return 0;
+}
+
+// The call state, read back, into the caller's result: the first finding with its arguments, or the truncated file.
+// `leftover`: lines of an incomplete last record that nothing more can follow
+int report_result(fqg_ctx* c, const ValidateCall& v, uint64_t leftover, fqg_validate_result* out) {
+  int rc;
+  const bool truncated = v.nul_truncated || (leftover && !out->stopped && !v.tail_is_stop);
+  out->tail_lines = v.nul_truncated ? 1 : truncated ? (int32_t)leftover : 0;
+  if (c->h_cs->first_key != ~0ull) {
+    out->record = c->h_cs->first_key >> 8;
+    out->code = (int32_t)(c->h_cs->first_key & 0xFF);
+    if (out->code != FQG_E_LINE_TOO_LONG) {  // (that one has no arguments, and its record may be the incomplete last one)
+      if ((rc = index_now(c))) return rc;
+      launch_exact(c, v, {1u, false, false, 1u, out->record}, nullptr);
+      if ((rc = read_call_state(c))) return rc;
+      out->aux0 = c->h_cs->aux0;
+      out->aux1 = c->h_cs->aux1;
+    }
+  } else if (truncated) {
+    // src/fastq.c:254-257: fewer than four lines left (or, in an image that is only framed, a record with a line that
+    // starts with NUL - an empty string to the reference: n_records counts the records in front of it)
+    out->code = FQG_E_TRUNCATED;
+    out->record = v.fv.n_records;
+  } else if (v.tail_is_stop && !out->stopped) {
+    out->stopped = 1;
+  }
+  return 0;
+}
+
 }  // namespace
 
 int fqg_validate(fqg_ctx* c, fqg_acc* acc, const void* image, uint64_t nbytes, int mem, int final,
@@ -1139,6 +1306,7 @@ int fqg_validate(fqg_ctx* c, fqg_acc* acc, const void* image, uint64_t nbytes, i
   if (nbytes == 0) return 0;
   if (nbytes >= (1ull << 44)) return fail(c, FQG_ERR_ARG, "image too large");
 
+  // ---- the image on the device
   int rc;
   const uint8_t* d_img;
   if (mem == FQG_MEM_HOST) {
@@ -1153,206 +1321,91 @@ int fqg_validate(fqg_ctx* c, fqg_acc* acc, const void* image, uint64_t nbytes, i
   const uint32_t n_chunks = (uint32_t)((nbytes + kChunkBytes - 1) / kChunkBytes);
   const bool frame_only = (flags & FQG_VALIDATE_FRAME_ONLY) != 0;
   if (frame_only) acc = nullptr;
+  const uint32_t name_flags = flags & (FQG_VALIDATE_NAMES | FQG_VALIDATE_NAME_DIGESTS);
+  const bool may_stream = nbytes >= c->stream_min && !(flags & FQG_VALIDATE_TWO_PASS);
   // (frame only + names: the single-pass framing runs for its capture records; what its checks find is not looked at)
-  const bool names_only = frame_only && (flags & (FQG_VALIDATE_NAMES | FQG_VALIDATE_NAME_DIGESTS)) && nbytes >= c->stream_min && !(flags & FQG_VALIDATE_TWO_PASS);
+  const bool names_only = frame_only && name_flags && may_stream;
   const bool want_checks = !(flags & FQG_VALIDATE_FORCE_EXACT) && (!frame_only || names_only);
   const uint32_t weight = (flags & FQG_VALIDATE_COUNT_TWICE) ? 2u : 1u;
 
-  // suspect bitmap, sized from the image (>= 16 bytes per record assumed; denser images overflow
+  // ---- suspect bitmap, sized from the image (>= 16 bytes per record assumed; denser images overflow
   // it, which sends every record to the exact validator)
   SuspectMap sm;
   sm.cap = std::max<uint64_t>(nbytes / 16, 1024);
   sm.flags = &c->d_cs->flags;
   sm.bits = nullptr;
+  const size_t suspect_bytes = (size_t)(sm.cap / 32 + 2) * 4;
   if (want_checks) {
-    if ((rc = ensure(c, c->suspect, (size_t)(sm.cap / 32 + 2) * 4))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->suspect.p, 0, (size_t)(sm.cap / 32 + 2) * 4, c->stream));
+    if ((rc = ensure(c, c->suspect, suspect_bytes))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->suspect.p, 0, suspect_bytes, c->stream));
     sm.bits = (uint32_t*)c->suspect.p;
   }
 
+  // ---- framing: one pass where the image allows it, else two
   Framed fr;
   bool streamed = false;
-  if (want_checks && nbytes >= c->stream_min && !(flags & FQG_VALIDATE_TWO_PASS)) {
+  if (want_checks && may_stream) {
     RecordDuties rd{st->space, weight, acc ? acc->d_state : nullptr, acc ? acc->d_hist : nullptr, st->readname_format, st->is_pe};
     // (digests need a format to canonicalise under: a file state that has none yet gets records)
-    const int names_mode = (flags & FQG_VALIDATE_NAME_DIGESTS) && st->readname_format != FQG_NAME_UNDEF ? 2
-                           : (flags & (FQG_VALIDATE_NAMES | FQG_VALIDATE_NAME_DIGESTS)) ? 1 : 0;
-    rc = frame_stream(c, d_img, nbytes, n_chunks, final != 0, sm, rd, names_mode,
-                      (flags & (FQG_VALIDATE_NAMES | FQG_VALIDATE_NAME_DIGESTS | FQG_VALIDATE_INDEX)) != 0, &fr);
+    const int names_mode = (flags & FQG_VALIDATE_NAME_DIGESTS) && st->readname_format != FQG_NAME_UNDEF ? 2 : name_flags ? 1 : 0;
+    rc = frame_stream(c, d_img, nbytes, n_chunks, final != 0, sm, rd, names_mode, name_flags || (flags & FQG_VALIDATE_INDEX), &fr);
     if (rc < 0) return rc;
     streamed = rc == 0;
-    if (!streamed) HIP_TRY(c, hipMemsetAsync(c->suspect.p, 0, (size_t)(sm.cap / 32 + 2) * 4, c->stream));
+    if (!streamed) HIP_TRY(c, hipMemsetAsync(c->suspect.p, 0, suspect_bytes, c->stream));
   }
   if (!streamed && (rc = frame_two_pass(c, d_img, nbytes, n_chunks, final != 0, want_checks && !frame_only, sm, &fr))) return rc;
-  const uint64_t n_newlines = fr.n_newlines;
-  const bool last_nl = fr.last_nl;
-  const uint32_t img_flags = fr.img_flags;
-  const uint64_t n_lines_all = n_newlines + (last_nl ? 0 : 1);
+  const uint64_t n_lines_all = fr.n_newlines + (fr.last_nl ? 0 : 1);
   // an unterminated last line is only a line when nothing more can follow
-  const uint64_t usable = (final || last_nl) ? n_lines_all : n_newlines;
-  uint64_t n_records = usable / 4;
+  const uint64_t usable = (final || fr.last_nl) ? n_lines_all : fr.n_newlines;
   const uint64_t leftover = usable % 4;
-
-  FrameView fv;
+  ValidateCall v{FrameView{}, st, acc, weight, sm, frame_only};
+  FrameView& fv = v.fv;
   fv.img = d_img;
   fv.nbytes = nbytes;
   fv.line_end = (const uint64_t*)c->line_end.p;
   fv.n_lines = n_lines_all;
-  fv.n_records = n_records;
+  fv.n_records = usable / 4;
   fv.reframed = (flags & FQG_VALIDATE_REFRAMED) ? 1u : 0u;
-  if (!fv.reframed) {
-    // the gzgets limits, where the record-wise checks do not look: every line of an image that is only framed, and the
-    // lines of an incomplete last record (the reference reads THOSE in pieces too before it finds the file truncated)
-    const uint64_t from = frame_only ? 0 : 4 * n_records;
-    const uint64_t upto = final ? n_lines_all : usable;
-    if (upto > from) {
-      ProfScope ps(c, "k_overlong");
-      FrameView lv = fv;
-      lv.n_lines = upto;
-      hipLaunchKernelGGL(k_overlong, dim3((unsigned)((upto - from + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, lv, from,
-                         c->d_cs);
-    }
-  }
+  if (!fv.reframed) check_overlong(c, fv, frame_only ? 0 : 4 * fv.n_records, final ? n_lines_all : usable);
+  if ((fr.img_flags & kFlagNul) && (rc = find_stop(c, v, leftover && final, out))) return rc;
+  const uint64_t n_records = fv.n_records;  // (in front of a record that starts with NUL)
 
-  // a record that starts with NUL ends the file silently (src/fastq.c:250)
-  bool tail_is_stop = false, nul_truncated = false;
-  if (img_flags & kFlagNul) {
-    if (n_records) {
-      ProfScope ps(c, "k_find_stop");
-      hipLaunchKernelGGL(k_find_stop, dim3((unsigned)((n_records + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                         c->stream, fv, c->d_cs, frame_only ? 1 : 0);
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-    if (leftover && final) {
-      // first byte of the incomplete trailing group
-      const uint64_t* le = (const uint64_t*)c->line_end.p;
-      if (n_records) {
-        HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[0], le + 4 * n_records - 1, 8, hipMemcpyDeviceToHost, c->stream));
-      } else c->h_scalar[0] = ~0ull;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      const uint64_t at = c->h_scalar[0] + 1;
-      uint8_t b = 1;
-      HIP_TRY(c, hipMemcpy(&b, d_img + at, 1, hipMemcpyDeviceToHost));
-      tail_is_stop = (b == 0);
-    } else {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    if (c->h_cs->stop_record < n_records) {
-      n_records = c->h_cs->stop_record;
-      out->stopped = 1;
-    }
-    if (c->h_cs->trunc_record < n_records) {  // (frame-only: an earlier record with an empty line - the file is truncated THERE)
-      n_records = c->h_cs->trunc_record;
-      out->stopped = 0;
-      nul_truncated = true;
-    }
-    fv.n_records = n_records;
-  }
-
-  // The tiled path needs an image without NUL / CR bytes (then every line is terminated by its
+  // ---- the records.  The tiled path needs an image without NUL / CR bytes (then every line is terminated by its
   // '\n' alone and the statistics follow from the line index); anything else goes through the
   // exact wave-per-record validator as a whole.
   const bool fast = fr.checks_done && !frame_only;
-  uint64_t list_cap = 0;
   if (fast) {
     out->path = streamed ? 3 : 2;
-    if (n_records) {
-      list_cap = std::max<uint64_t>(1u << 20, n_records / 16);
-      if (list_cap > n_records) list_cap = n_records;
-      if ((rc = ensure(c, c->list, (size_t)list_cap * 8))) return rc;
-      const unsigned grid_r =
-          (unsigned)std::min<uint64_t>((n_records + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 8);
-      if (fr.records_done) {
-        ProfScope ps(c, "k_suspect_list");
-        hipLaunchKernelGGL(k_suspect_list, dim3((unsigned)std::min<uint64_t>((n_records / 32 + kBlock) / kBlock, 1024)), dim3(kBlock), 0,
-                           c->stream, (const uint32_t*)sm.bits, std::min<uint64_t>(n_records, sm.cap),
-                           (unsigned long long*)c->list.p, list_cap, &c->d_cs->list_count, acc ? acc->d_state : nullptr,
-                           (const CallState*)c->d_cs);
-      } else {
-        ProfScope ps(c, "k_records_fast");
-        hipLaunchKernelGGL(k_records_fast, dim3(grid_r), dim3(kBlock), 0, c->stream, fv, st->space, weight, sm,
-                           (unsigned long long*)c->list.p, list_cap, &c->d_cs->list_count,
-                           acc ? acc->d_state : nullptr, acc ? acc->d_hist : nullptr, c->d_cs);
-      }
-      if (!c->lazy.pending) {  // (on demand: once the number of listed records is known, below)
-        ProfScope ps(c, "k_validate_exact");
-        hipLaunchKernelGGL(k_validate_exact, dim3(c->cu_count * 2), dim3(kBlock), 0, c->stream, fv, st->is_pe,
-                           st->readname_format, st->space, weight, (AccState*)nullptr,
-                           (unsigned long long*)nullptr, c->d_cs, kNoRecord,
-                           (const unsigned long long*)c->list.p, (const unsigned long long*)&c->d_cs->list_count);
-      }
-    }
+    if (n_records && (rc = check_records(c, v, fr.records_done))) return rc;
   } else if (n_records && !frame_only) {
-    ProfScope ps(c, "k_validate_exact");
-    hipLaunchKernelGGL(k_validate_exact, dim3(grid_for_waves(c, n_records)), dim3(kBlock), 0, c->stream, fv,
-                       st->is_pe, st->readname_format, st->space, weight, acc ? acc->d_state : nullptr,
-                       acc ? acc->d_hist : nullptr, c->d_cs, kNoRecord, (const unsigned long long*)nullptr,
-                       (const unsigned long long*)nullptr);
+    launch_exact(c, v, {(unsigned)grid_for_waves(c, n_records), false, true, weight, kNoRecord}, "k_validate_exact");
     out->path = 1;
   }
-  HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-  if (n_records) {
-    HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[1], (const uint64_t*)c->line_end.p + 4 * n_records - 1, 8,
-                              hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->lazy.pending && fast && n_records && c->h_cs->list_count > 0 && c->h_cs->list_count <= list_cap &&
-      !(c->h_cs->flags & (kFlagSuspectOverflow | kFlagQueueOverflow))) {
+  // ---- what was found, and where the last complete record ends
+  if ((rc = read_call_state(c, n_records ? fv.line_end + 4 * n_records - 1 : nullptr, &c->h_scalar[1]))) return rc;
+  auto overflow = [&] { return c->h_cs->list_count > v.list_cap || (c->h_cs->flags & (kFlagSuspectOverflow | kFlagQueueOverflow)); };
+  if (c->lazy.pending && fast && n_records && c->h_cs->list_count > 0 && !overflow()) {
     // records the line kernels could not vouch for: the exact validator reads them through the index
     if ((rc = index_now(c))) return rc;
-    ProfScope ps(c, "k_validate_exact");
-    hipLaunchKernelGGL(k_validate_exact, dim3(c->cu_count * 2), dim3(kBlock), 0, c->stream, fv, st->is_pe,
-                       st->readname_format, st->space, weight, (AccState*)nullptr,
-                       (unsigned long long*)nullptr, c->d_cs, kNoRecord,
-                       (const unsigned long long*)c->list.p, (const unsigned long long*)&c->d_cs->list_count);
-    HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_exact(c, v, {(unsigned)c->cu_count * 2, true, false, weight, kNoRecord}, "k_validate_exact");
+    if ((rc = read_call_state(c))) return rc;
   }
   out->n_records = n_records;
   out->n_lines = n_lines_all;
-  out->tail_lines = nul_truncated ? 1 : (final && leftover && !out->stopped && !tail_is_stop) ? (int32_t)leftover : 0;
   out->consumed = n_records ? c->h_scalar[1] + 1 : 0;
   if (out->consumed > nbytes) out->consumed = nbytes;  // unterminated last line
-
-  if (fast && n_records &&
-      (c->h_cs->list_count > list_cap || (c->h_cs->flags & (kFlagSuspectOverflow | kFlagQueueOverflow)))) {
+  if (fast && n_records && overflow()) {
     // more suspects than the queue / bitmap holds (e.g. every record carries its name on line 3):
     // let the exact validator look at every record; the statistics of the tiled pass stand
     if ((rc = index_now(c))) return rc;
-    ProfScope ps(c, "k_validate_exact");
-    hipLaunchKernelGGL(k_validate_exact, dim3(grid_for_waves(c, n_records)), dim3(kBlock), 0, c->stream, fv,
-                       st->is_pe, st->readname_format, st->space, weight, (AccState*)nullptr,
-                       (unsigned long long*)nullptr, c->d_cs, kNoRecord, (const unsigned long long*)nullptr,
-                       (const unsigned long long*)nullptr);
-    HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_exact(c, v, {(unsigned)grid_for_waves(c, n_records), false, false, weight, kNoRecord}, "k_validate_exact");
+    if ((rc = read_call_state(c))) return rc;
   }
-  if (c->h_cs->first_key != ~0ull) {
-    out->record = c->h_cs->first_key >> 8;
-    out->code = (int32_t)(c->h_cs->first_key & 0xFF);
-    if (out->code != FQG_E_LINE_TOO_LONG) {  // (that one has no arguments, and its record may be the incomplete last one)
-      if ((rc = index_now(c))) return rc;
-      hipLaunchKernelGGL(k_validate_exact, dim3(1), dim3(kBlock), 0, c->stream, fv, st->is_pe,
-                         st->readname_format, st->space, 1u, (AccState*)nullptr, (unsigned long long*)nullptr,
-                         c->d_cs, out->record, (const unsigned long long*)nullptr,
-                         (const unsigned long long*)nullptr);
-      HIP_TRY(c, hipMemcpyAsync(c->h_cs, c->d_cs, sizeof(CallState), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      out->aux0 = c->h_cs->aux0;
-      out->aux1 = c->h_cs->aux1;
-    }
-  } else if (nul_truncated || (final && leftover && !out->stopped && !tail_is_stop)) {
-    // src/fastq.c:254-257: fewer than four lines left (or, in an image that is only framed, a record with a line that
-    // starts with NUL - an empty string to the reference: n_records counts the records in front of it)
-    out->code = FQG_E_TRUNCATED;
-    out->record = n_records;
-  } else if (tail_is_stop && !out->stopped) {
-    out->stopped = 1;
-  }
+  if ((rc = report_result(c, v, final ? leftover : 0, out))) return rc;
   c->frame = fv;
   c->frame_valid = true;
   c->frame_img_owned = (mem == FQG_MEM_HOST);
-  c->frame_flags = img_flags;
+  c->frame_flags = fr.img_flags;
   HIP_TRY(c, hipGetLastError());
   return 0;
 }

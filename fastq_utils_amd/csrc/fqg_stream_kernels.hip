@@ -17,10 +17,12 @@
 //                       after it, "the byte after that is '\n'") through a per-wave LDS table, so
 //                       that the global stores are contiguous
 //   k_scan_a/b      prefix over the per-chunk newline counts (fqg_kernels.hip)
-//   k_stream_pass2  one wavefront per chunk, now with the true rank: staged entries -> line_end[],
-//                   header-start checks ('@', not empty; "+\n") by line type, verification of the
-//                   speculation (a wrong or missing one sends the chunk to the redo list, where
-//                   k_frame_fast_t repeats the checks with the true type), quality range merge
+//   k_stream_chunks one lane per chunk, now with the true rank: verification of the speculation (a
+//                   wrong or missing one sends the chunk to the redo list, where k_frame_fast_t
+//                   repeats the checks with the true type), quality range merge
+//   k_stream_lines  one lane per record: staged entries -> line_end[], header-start checks ('@', not
+//                   empty; "+\n") by line type, lengths, statistics (k_stream_lines_fast: the
+//                   steps of ordinary records, without a search)
 //   k_stream_queue  queued suspect positions -> record bits (binary search in line_end[])
 //
 // Nothing here decides an error code: as in the two-pass path, records the checks cannot vouch for
@@ -680,96 +682,10 @@ __global__ __launch_bounds__(kBlock) void k_stream_pass1(const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------
-// pass 2: staged entries -> line index, header-start checks, verification of the speculation
-// ------------------------------------------------------------------------------------------
-constexpr int kP2Batch = 8;  // chunks per wavefront (their loads are issued together)
-
-__global__ __launch_bounds__(kBlock) void k_stream_pass2(const uint8_t* __restrict__ img, uint64_t n,
-                                                         uint32_t n_chunks, const uint32_t* __restrict__ counts,
-                                                         const uint32_t* __restrict__ cinfo,
-                                                         const uint16_t* __restrict__ stage,
-                                                         const uint32_t* __restrict__ chunk_local,
-                                                         const unsigned long long* __restrict__ span_excl,
-                                                         uint64_t* __restrict__ line_end, uint64_t line_cap,
-                                                         uint64_t limit, SuspectMap suspect,
-                                                         uint32_t* __restrict__ redo, CallState* __restrict__ cs) {
-  const int lane = lane_id();
-  const uint32_t c0 = (blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)) * kP2Batch;
-  if (c0 >= n_chunks) return;
-  // lane b < kP2Batch holds the scalars of chunk c0 + b
-  uint32_t cnt = 0, info = 0;
-  uint64_t rank0 = 0;
-  const uint32_t mine = c0 + (uint32_t)lane;
-  if (lane < kP2Batch && mine < n_chunks) {
-    cnt = counts[mine];
-    info = cinfo[mine];
-    rank0 = span_excl[mine / kScanSpan] + chunk_local[mine];
-  }
-  uint32_t e[kP2Batch], tot[kP2Batch];
-  uint64_t r0[kP2Batch];
-#pragma unroll
-  for (int b = 0; b < kP2Batch; ++b) {
-    const uint32_t cb_cnt = (uint32_t)__builtin_amdgcn_readlane(cnt, b);
-    tot[b] = cb_cnt < (uint32_t)kStageCap ? cb_cnt : (uint32_t)kStageCap;
-    r0[b] = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)rank0, b) |
-            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(rank0 >> 32), b) << 32);
-    e[b] = (uint32_t)lane < tot[b] ? stage[(uint64_t)(c0 + b) * kStageCap + lane] : 0u;
-  }
-  auto entry = [&](uint32_t chunk, uint64_t rank, uint32_t i, uint32_t ent) {
-    const uint64_t L = rank + i;
-    if (L < line_cap) line_end[L] = (uint64_t)chunk * kChunkBytes + (ent & 0xFFFu);
-    const uint64_t nx = L + 1;  // the line that starts after this '\n'
-    if (nx < limit) {
-      const uint32_t cls = (ent >> 12) & 3u, nl2 = (ent >> 14) & 1u;
-      const uint32_t t = (uint32_t)nx & 3u;
-      const bool bad = t == 0 ? !(cls == kClsAt && !nl2) : (t == 2 ? !(cls == kClsPlus && nl2) : false);
-      if (bad) mark_suspect(suspect, nx >> 2);
-    }
-  };
-#pragma unroll
-  for (int b = 0; b < kP2Batch; ++b) {
-    if ((uint32_t)lane < tot[b]) entry(c0 + b, r0[b], (uint32_t)lane, e[b]);
-    for (uint32_t i = kWave + lane; i < tot[b]; i += kWave)  // more than 64 newlines in 4 KiB: rare
-      entry(c0 + b, r0[b], i, stage[(uint64_t)(c0 + b) * kStageCap + i]);
-  }
-  const bool own = lane < kP2Batch && mine < n_chunks;
-  bool again = false;
-  if (own) {
-    if (mine == 0 && limit > 0 && (img[0] != '@' || (n > 1 && img[1] == '\n'))) mark_suspect(suspect, 0);
-    // only chunks that hold bytes of complete records need their byte checks to stand
-    if (rank0 < limit) {
-      // (a chunk that reaches beyond the last complete record is repeated too: its quality range may
-      // include bytes of an incomplete record)
-      if (chunk_info_redo(info, (uint32_t)rank0) || rank0 + cnt >= limit) again = true;
-      else if (chunk_info_range(info, (uint32_t)rank0)) {
-        // (look first: the hull settles after a few chunks, and every later one would still be an atomic on one address)
-        const uint32_t qlo = (info >> 8) & 0xFFu, qhi = (info >> 16) & 0xFFu;
-        if (qlo < __atomic_load_n(&cs->qmin_byte, __ATOMIC_RELAXED)) atomicMin(&cs->qmin_byte, qlo);
-        if (qhi > __atomic_load_n(&cs->qmax_byte, __ATOMIC_RELAXED)) atomicMax(&cs->qmax_byte, qhi);
-      }
-    }
-    if (mine == n_chunks - 1 && n > 0 && !cs->last_byte_is_nl && cs->n_newlines < line_cap)
-      line_end[cs->n_newlines] = n;
-  }
-  // the redo list: one reservation per wavefront (long reads send EVERY chunk here - no "+" line in 4 KiB to
-  // speculate from - and two million single adds to one address took longer than the rest of the kernel)
-  const unsigned long long am = __ballot(again);
-  if (am) {
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&cs->redo_count, (uint32_t)__builtin_popcountll(am));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    if (again) {
-      const uint32_t at = base + (uint32_t)__builtin_popcountll(am & ((1ull << lane) - 1ull));
-      if (at < n_chunks) redo[at] = mine;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// pass 2, second form: the per-chunk duties (k_stream_chunks) and the per-line / per-record duties
-// (k_stream_lines) separately.  k_stream_pass2 above walks the image chunk by chunk, so a wavefront's
-// line_end[] stores start wherever its first chunk's rank happens to fall, and the per-record statistics
-// needed a further pass over the 32 B / record it had just written (k_records_fast).  Here a LANE OWNS A
+// pass 2: the per-chunk duties (k_stream_chunks) and the per-line / per-record duties (k_stream_lines)
+// separately.  Its first form (k_stream_pass2, one wavefront per chunk; since removed) walked the image chunk
+// by chunk, so a wavefront's line_end[] stores started wherever its first chunk's rank happened to fall, and the
+// per-record statistics needed a further pass over the 32 B / record it had just written (k_records_fast).  Here a LANE OWNS A
 // RECORD: it fetches the five staged entries that bound its four lines (2-byte loads, neighbouring lanes
 // neighbouring addresses), writes the record's four line ends as one aligned 32-byte piece (a wavefront writes
 // 2 KiB, aligned), checks the header starts, and derives the lengths, the statistics and the suspect bit from

@@ -89,7 +89,6 @@ int main(int argc, char** argv) {
     P1(0u, "k_stream_pass1");
     hipLaunchKernelGGL(k_scan_a, dim3(n_spans), dim3(kBlock), 0, 0, counts, n_tiles, local, spans);
     hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, 0, spans, n_spans, img, n, cs);
-    report("k_stream_pass2", time_ms(reps, [&] { hipLaunchKernelGGL(k_stream_pass2, dim3((n_tiles + 31) / 32), dim3(kBlock), 0, 0, img, n, n_tiles, counts, cinfo, stage, local, spans, line_end, 4 * reads + 32, 4 * reads, sm, redo, cs); }));
     {
       // Does the second framing pass overlap with pass 1 when the two run on streams of their own?  (pass 1 is bound by
       // vector-ALU cycles, k_stream_lines_fast by memory latency - but pass 1 fills every wave slot and most of the LDS.)
