@@ -1,23 +1,16 @@
 // fq_input.h - host side of the drop-in programs: reading (optionally gzipped) FASTQ files into
 // pinned staging buffers, piece by piece, with the incomplete tail of one piece carried into the
-// next.  Decompression stays on the host (zlib), as in the reference (src/fastq.c:631-661).
+// next.  Decompression stays on the host (zlib), as in the reference (src/fastq.c:631-661); how an input is opened
+// and read is fq_source.h.
 //
 // Reading runs AHEAD of the GPU: a producer thread fills a ring of pinned slots while the caller has
 // the previous piece copied to the device and validated (what the reference does serially with four
-// gzgets per record, src/fastq.c:245-261).  A plain (not gzipped) regular file is read with pread() by
-// several threads at once - 50 Mreads/s of 150 bp reads are 17.5 GB/s, more than one core copies.  A gzip
-// file is inflated on every core the process may use: a bgzip'd one block by block (read_bgzf), any other one by
-// chunks whose first blocks are searched for (fq_pgzip.h); stdin and small files by one zlib thread - all ahead of the GPU.
+// gzgets per record, src/fastq.c:245-261).
 //
 // Layout of a slot: [ headroom | raw bytes ].  The producer writes raw file bytes behind the headroom
 // without knowing where the previous piece's last complete record ended; the consumer learns that from
 // the validation of the previous piece and copies the few carried bytes in FRONT of the raw bytes.
 #pragma once
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -26,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -35,21 +29,10 @@
 #include <vector>
 
 #include "../../include/fqg.h"
-#include "fq_parallel.h"
-#include "fq_pgzip.h"
 #include "fq_reframe.h"
-#include "fq_respawn.h"
+#include "fq_source.h"
 
 namespace fqhost {
-
-// src/fastq.h:68-80
-#define FQ_PRINT_ERROR(...)       \
-  do {                            \
-    fprintf(stderr, "\nERROR: "); \
-    fprintf(stderr, __VA_ARGS__); \
-    fprintf(stderr, "\n");        \
-  } while (0)
-constexpr int kExitParams = 1, kExitSys = 2, kExitFormat = 3;
 
 // The programs run one job and exit: un-pinning hundreds of megabytes of staging slots first (0.1 - 0.2 s) buys nothing -
 // the operating system takes the memory back.  Set once by a program's main(); library-style users leave it alone.
@@ -135,55 +118,6 @@ inline size_t piece_for_file(size_t piece, uint64_t file_bytes, bool compressed)
 inline char* slot_alloc(fqg_ctx* ctx, size_t bytes) { return SlotPool::get().take(ctx, bytes); }
 inline void slot_release(fqg_ctx* ctx, char* p) { SlotPool::get().give(ctx, p); }
 
-// How the programs leave: with everything they said flushed, and WITHOUT exit()'s hooks.  The HIP runtime tears itself
-// down in one of them, and it must not meet a thread of ours that is still inside a HIP call (a reader pinning its next
-// slot while the main thread has found the file's first error): that is a crash after the error message, i.e. a wrong
-// exit status.  Nothing is lost: outputs are closed by those who write them before they leave.
-[[noreturn]] inline void leave(int code) {
-  fflush(stdout);
-  fflush(stderr);
-  if (getenv("FQGPU_PLAIN_EXIT")) exit(code);  // (tools/exit_stress.py: does the process survive exit()'s hooks?)
-  _exit(code);
-}
-
-inline unsigned host_read_threads() {
-  if (const char* e = getenv("FQGPU_HOST_THREADS")) return (unsigned)std::max(1L, strtol(e, nullptr, 10));
-  const unsigned hw = std::thread::hardware_concurrency();
-  // (a dozen copy a tmpfs file faster than PCIe takes it; more of them only compete with the DMA for host memory:
-  // 8 / 16 / 32 / 64 threads -> 1.06 / 1.16 / 1.24 / 1.46 s for the 100 M-read file of the bench)
-  return std::max(1u, std::min(12u, hw ? hw : 1u));
-}
-
-// (ReaderPool - a few threads that stay around - lives in fq_parallel.h)
-
-// gzip files below this size stay with one zlib thread (FQGPU_PGZIP_MIN: tests send tiny files through the chunked reader)
-inline uint64_t pgzip_min_bytes() {
-  if (const char* e = getenv("FQGPU_PGZIP_MIN")) return (uint64_t)std::max(0L, atol(e));
-  return 1u << 20;
-}
-
-// The many-core reader for the gzip file open on fd (fq_pgzip.h), or nothing when one zlib thread is to read it: small
-// files, a single usable core, FQGPU_NO_PARALLEL_INFLATE.  (What that reader does not want to decide it leaves to one
-// zlib stream of its own, so every file gzopen reads is read.)
-inline std::unique_ptr<ParallelGunzip> open_pgzip(int fd, uint64_t size, const char* path) {
-  if (size < pgzip_min_bytes() || host_threads() <= 1 || getenv("FQGPU_NO_PARALLEL_INFLATE")) return nullptr;
-  const unsigned T = std::min(host_threads(), 64u);
-  // (tools/pgzip_scan.sh on the 16-core share of an EPYC 9575F: 2.6 / 3.0 / 3.5 GB/s inflated with chunks of 1 / 2 / 4 MiB)
-  size_t chunk = std::max<size_t>(512u << 10, std::min<size_t>(4u << 20, (128u << 20) / T));
-  chunk = std::min<size_t>(chunk, std::max<size_t>((size_t)size / T, 128u << 10));
-  if (const char* e = getenv("FQGPU_PGZIP_CHUNK")) chunk = (size_t)std::max(4096L, atol(e));
-  return std::unique_ptr<ParallelGunzip>(new ParallelGunzip(fd, size, path, T, chunk));
-}
-inline void pgzip_report(const ParallelGunzip* pg, const std::string& path) {
-  if (!pg || !(getenv("FQGPU_PGZIP_DEBUG") || getenv("FQGPU_TIMING"))) return;
-  const ParallelGunzip::Stats& st = pg->stats();
-  fprintf(fqhost::diag(), "fqgpu timing: %s inflated by chunks: %llu rounds, %llu chunks joined, %llu without a block start, %llu wrong guesses, "
-          "%llu members%s%s; reading %.3f s, finding + inflating %.3f s, joining %.3f s, markers -> bytes + CRC-32 %.3f s\n",
-          path.c_str(), (unsigned long long)st.batches, (unsigned long long)st.chunks_joined, (unsigned long long)st.chunks_not_found,
-          (unsigned long long)st.chunks_discarded, (unsigned long long)st.members, st.fell_back ? "; one zlib stream from: " : "",
-          st.fell_back ? st.why.c_str() : "", st.s_load, st.s_decode, st.s_join + st.s_windows, st.s_narrow);
-}
-
 // Readers that run ahead of the GPU, and exit().  A program that links the per-record library (libfastq_gpu.so under the
 // reference's own main()) leaves through exit() whenever it likes - on its first finding, say, while a producer thread is
 // pinning or filling the next slot, i.e. is INSIDE a HIP call.  exit() runs the HIP runtime's own teardown from one of
@@ -191,7 +125,7 @@ inline void pgzip_report(const ParallelGunzip* pg, const std::string& path) {
 // status).  So the hooks stop the readers first: every Input with a live producer is registered here, and the handler
 // - registered with atexit() when the first of them starts, i.e. AFTER the runtime was initialised by fqg_open, and
 // therefore run BEFORE the runtime's handlers (exit() runs them last-registered first) - tells them to stop and joins
-// them.  The drop-in programs themselves leave through _exit() (leave(), above) and never get here.
+// them.  The drop-in programs themselves leave through _exit() (leave(), fq_source.h) and never get here.
 class ExitQuiesce {
  public:
   typedef void (*StopFn)(void*);
@@ -259,49 +193,180 @@ class ExitQuiesce {
   bool hooked_ = false;
 };
 
+// Pinned slots handed from ONE producer to any number of consumers, for the readers whose items have no order among
+// them (fq_multi.h, fq_blocks.h).  The producer takes a free slot (acquire), fills it and publishes an Item that says
+// where in the slot it lies (Item::slot, Item::size); a consumer takes the next item (next) and gives its slot back
+// (release).
+//
+// Pinning a slot takes six times as long as filling it (128 MiB: 23 ms against 3.6 ms from tmpfs): the slots are pinned
+// by a thread of their own, one after the other, while the producer fills - and fills again - the ones it has.  (The
+// producer pinned them itself, on its way: 0.18 s of a 0.5 s job in front of every byte read after them.)  All the
+// slots the owner asked for are pinned while the producer still runs - consumers may each hold one while another
+// waits for the next item with a lock of the caller's held - and a slot that cannot be pinned is the queue's failure:
+// nobody is left waiting for a slot that will not come.
+template <class Item>
+class PinnedQueue {
+ public:
+  PinnedQueue(fqg_ctx* ctx, int n_slots) : ctx_(ctx), slots_((size_t)n_slots) {}
+  ~PinnedQueue() {
+    stop();
+    for (auto& s : slots_) slot_release(ctx_, s.buf);
+  }
+  PinnedQueue(const PinnedQueue&) = delete;
+  PinnedQueue& operator=(const PinnedQueue&) = delete;
+
+  // the producer thread runs `produce`, the pinner gives every slot `slot_bytes`
+  void start(size_t slot_bytes, std::function<void()> produce) {
+    producer_ = std::thread(std::move(produce));
+    pinner_ = std::thread([this, slot_bytes] { pin(slot_bytes); });
+  }
+  // both threads told to stop and joined (the owner's destructor, before it lets go of what the producer reads)
+  void stop() {
+    abort();
+    if (producer_.joinable()) producer_.join();
+    if (pinner_.joinable()) pinner_.join();
+  }
+  double pin_seconds() const { return t_pin_; }  // (FQGPU_TIMING; after stop())
+
+  // ---- the producer's side ----
+  // a free slot, now the producer's; -1 when the queue has stopped or failed
+  int acquire() {
+    std::unique_lock<std::mutex> lk(mu_);
+    int s = -1;
+    cv_.wait(lk, [&] {
+      if (quit_ || failed_) return true;
+      for (size_t i = 0; i < slots_.size(); ++i)
+        if (slots_[i].buf && !slots_[i].busy) {
+          s = (int)i;
+          return true;
+        }
+      return false;
+    });
+    if (s >= 0) slots_[(size_t)s].busy = true;
+    return s;
+  }
+  char* data(int slot) const { return slots_[(size_t)slot].buf; }
+  // room for `want` bytes in a slot the producer holds, the first `keep` of them kept; false: the queue has failed
+  bool grow(int slot, size_t keep, size_t want) {
+    Slot& s = slots_[(size_t)slot];
+    if (want <= s.cap) return true;
+    const size_t cap = std::max(want, s.cap + s.cap / 2);
+    char* nb = slot_alloc(ctx_, cap + 1);
+    if (!nb) {
+      fail("unable to allocate pinned memory");
+      return false;
+    }
+    if (keep) memcpy(nb, s.buf, keep);
+    slot_release(ctx_, s.buf);
+    s.buf = nb;
+    s.cap = cap;
+    return true;
+  }
+  void give_back(int slot) {
+    std::lock_guard<std::mutex> lk(mu_);
+    slots_[(size_t)slot].busy = false;
+    cv_.notify_all();
+  }
+  void publish(const Item& it) {
+    std::lock_guard<std::mutex> lk(mu_);
+    ready_.push_back(it);
+    cv_.notify_all();
+  }
+  void finish() {  // the last item has been published
+    std::lock_guard<std::mutex> lk(mu_);
+    done_ = true;
+    cv_.notify_all();
+  }
+  void fail(const std::string& msg) {
+    std::lock_guard<std::mutex> lk(mu_);
+    fail_locked(msg);
+  }
+  bool stopped() {
+    std::lock_guard<std::mutex> lk(mu_);
+    return quit_;
+  }
+
+  // ---- the consumers' side (thread-safe) ----
+  // next item in the producer's order; false when there are no more
+  bool next(Item* out) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !ready_.empty() || done_ || failed_ || quit_; });
+    if (quit_) return false;
+    if (failed_) {
+      FQ_PRINT_ERROR("%s.\n", fail_msg_.c_str());
+      leave(kExitSys);
+    }
+    if (ready_.empty()) return false;
+    *out = ready_.front();
+    ready_.pop_front();
+    bytes_handed_out() += out->size;
+    return true;
+  }
+  void release(const Item& it) { give_back(it.slot); }
+  // Stop handing out items: wakes the producer (which may be waiting for a free slot that nobody will release any
+  // more) and every consumer waiting in next(), which then returns false.  For the error paths of the consumers: they
+  // stop with items still held, and joining them without this would wait forever.
+  void abort() {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      quit_ = true;
+    }
+    cv_.notify_all();
+  }
+
+ private:
+  struct Slot {
+    char* buf = nullptr;
+    size_t cap = 0;
+    bool busy = false;
+  };
+  void fail_locked(const std::string& msg) {
+    if (!failed_) fail_msg_ = msg;
+    failed_ = true;
+    cv_.notify_all();
+  }
+  void pin(size_t bytes) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < slots_.size(); ++i) {
+      {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (quit_ || failed_ || done_) break;
+      }
+      char* buf = slot_alloc(ctx_, bytes + 1);
+      std::lock_guard<std::mutex> lk(mu_);
+      if (!buf) {
+        if (!quit_ && !done_) fail_locked("unable to allocate pinned memory");  // (nobody needs the slot any more otherwise)
+        break;
+      }
+      slots_[i].buf = buf;
+      slots_[i].cap = bytes;
+      cv_.notify_all();
+    }
+    t_pin_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+
+  fqg_ctx* ctx_;
+  std::vector<Slot> slots_;
+  std::deque<Item> ready_;
+  std::thread producer_, pinner_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  bool quit_ = false, failed_ = false, done_ = false;
+  std::string fail_msg_;
+  double t_pin_ = 0;
+};
+
 class Input {
  public:
-  Input(fqg_ctx* ctx, const char* path, size_t piece_bytes) : ctx_(ctx), path_(path), cap_(piece_bytes) {
-    // fastq_open, src/fastq.c:631-661
-    if (path_ == "-") gz_ = gzdopen(fileno(stdin), "rb");
-    else {
-      // a regular file that does not start with the gzip magic is what zlib would pass through unchanged
-      const int fd = open(path, O_RDONLY);
-      struct stat sb;
-      if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
-        unsigned char magic[18];
-        memset(magic, 0, sizeof(magic));
-        const ssize_t got = pread(fd, magic, sizeof(magic), 0);
-        if (!(got >= 2 && magic[0] == 0x1f && magic[1] == 0x8b)) {
-          plain_fd_ = fd;
-          plain_size_ = (uint64_t)sb.st_size;
-        } else if (cap_ = piece_for_file(cap_, (uint64_t)sb.st_size, true);
-                   got == 18 && bgzf_block_size(magic, 18) > 0 && !getenv("FQGPU_NO_PARALLEL_INFLATE")) {
-          // bgzip'd FASTQ: a sequence of small gzip members that say how long they are (SAM/BAM specification 4.1) -
-          // inflated on all cores (read_bgzf below) instead of by one zlib thread
-          bgzf_fd_ = fd;
-          bgzf_size_ = (uint64_t)sb.st_size;
-        } else if ((pgz_ = open_pgzip(fd, (uint64_t)sb.st_size, path))) {
-          pgz_fd_ = fd;  // any other gzip file of some size: chunks of it are inflated side by side
-        }
-      }
-      if (plain_fd_ < 0 && bgzf_fd_ < 0 && pgz_fd_ < 0) {
-        if (fd >= 0) close(fd);
-        gz_ = gzopen(path, "r");
-      }
-    }
-    if (!gz_ && plain_fd_ < 0 && bgzf_fd_ < 0 && pgz_fd_ < 0) {
-      FQ_PRINT_ERROR("Unable to open %s", path);
-      leave(kExitParams);
-    }
-    if (gz_) gzbuffer(gz_, 1 << 20);
-    if (plain_fd_ >= 0 && plain_size_ < cap_) cap_ = std::max<size_t>(plain_size_, 1);  // small file: one small slot
-    if (bgzf_fd_ >= 0) cap_ = std::max<size_t>(cap_, 1u << 17);  // (whole blocks of up to 64 KiB are inflated into a slot)
+  Input(fqg_ctx* ctx, const char* path, size_t piece_bytes) : ctx_(ctx), src_(path, bgzf_blocks()), cap_(piece_bytes) {
+    if (src_.inflated() && src_.file_bytes()) cap_ = piece_for_file(cap_, src_.file_bytes(), true);
+    if (src_.kind() == FastqSource::kPlain && src_.plain_bytes() < cap_) cap_ = std::max<size_t>(src_.plain_bytes(), 1);  // small file: one small slot
+    if (src_.kind() == FastqSource::kBgzf) cap_ = std::max<size_t>(cap_, 1u << 17);  // (whole blocks of up to 64 KiB are inflated into a slot)
     // The reference's gzgets limits (fq_reframe.h).  Inflated input and stdin pass through one thread anyway: it cuts
     // as it goes (a memchr per line beside the inflate).  A plain file is read by many threads and handed over as it
     // is; the GPU reports a line beyond the limits (FQG_E_LINE_TOO_LONG) and the program starts over with
     // FQGPU_REFRAME set (fq_respawn.h), which brings it here.
-    reframe_ = ((gz_ != nullptr || bgzf_fd_ >= 0 || pgz_fd_ >= 0) && reframe_supported()) || reframing();
+    reframe_ = (src_.inflated() && reframe_supported()) || reframing();
   }
   // the producer is told to stop and joined (the destructor; exit(): ExitQuiesce)
   void stop_reading() {
@@ -315,13 +380,6 @@ class Input {
   ~Input() {
     ExitQuiesce::get().remove(this);
     stop_reading();
-    if (gz_) gzclose(gz_);
-    if (plain_fd_ >= 0) close(plain_fd_);
-    if (bgzf_fd_ >= 0) close(bgzf_fd_);
-    pgzip_report(pgz_.get(), path_);
-    pgz_.reset();
-    if (pgz_fd_ >= 0) close(pgz_fd_);
-    free(bz_raw_);
     for (Slot& s : slots_) slot_release(ctx_, s.buf);
     slot_release(ctx_, whole_);
     slot_release(ctx_, big_);
@@ -394,8 +452,8 @@ class Input {
   // what fqg_validate must be told about this input's pieces
   uint32_t vflags() const { return reframe_ ? FQG_VALIDATE_REFRAMED : 0u; }
   // bytes of a plain (uncompressed, seekable) input, 0 when unknown: a size hint for whoever sizes tables from it
-  uint64_t plain_bytes() const { return plain_fd_ >= 0 ? plain_size_ : 0; }
-  const std::string& path() const { return path_; }
+  uint64_t plain_bytes() const { return src_.plain_bytes(); }
+  const std::string& path() const { return src_.path(); }
 
  private:
   static constexpr int kSlots = 3;
@@ -423,60 +481,16 @@ class Input {
     return p;
   }
 
-  // one read of up to `want` bytes behind what the slot holds; false at end of input
-  size_t read_gz(char* dst, size_t want, bool* at_end) {
-    size_t len = 0;
-    while (len < want) {
-      const size_t ask = std::min<size_t>(want - len, 1u << 30);
-      const int got = gzread(gz_, dst + len, (unsigned)ask);
-      if (got < 0) {
-        int en = 0;
-        std::lock_guard<std::mutex> lk(mu_);
-        fail_msg_ = gzerror(gz_, &en);
-        failed_ = true;
-        cv_.notify_all();
-        return len;
-      }
-      if (got == 0) {
-        *at_end = true;
-        return len;
-      }
-      len += (size_t)got;
-    }
-    const int c = gzgetc(gz_);  // a file that ends exactly where the buffer does
-    if (c < 0) *at_end = true;
-    else gzungetc(c, gz_);
-    return len;
+  static FastqSource::Options bgzf_blocks() {
+    FastqSource::Options o;
+    o.bgzf = true;
+    return o;
   }
-  size_t read_plain(char* dst, size_t want, bool* at_end) {
-    const uint64_t left = plain_size_ - plain_off_;
-    const size_t len = (size_t)std::min<uint64_t>(want, left);
-    const unsigned T = (unsigned)std::min<uint64_t>(host_read_threads(), std::max<uint64_t>(1, len >> 22));
-    if (T > 1 && !pool_) pool_.reset(new ReaderPool(host_read_threads()));
-    std::atomic<bool> bad{false};
-    auto part = [&](unsigned t) {
-      const size_t a = (len * t / T) & ~(size_t)4095, b = t + 1 == T ? len : (len * (t + 1) / T) & ~(size_t)4095;
-      size_t done = a;
-      while (done < b) {
-        const ssize_t got = pread(plain_fd_, dst + done, b - done, (off_t)(plain_off_ + done));
-        if (got <= 0) {
-          bad = true;
-          return;
-        }
-        done += (size_t)got;
-      }
-    };
-    if (T <= 1) part(0);
-    else pool_->run(T, part);
-    if (bad) {
-      std::lock_guard<std::mutex> lk(mu_);
-      fail_msg_ = "read error";
-      failed_ = true;
-      cv_.notify_all();
-    }
-    plain_off_ += len;
-    if (plain_off_ >= plain_size_) *at_end = true;
-    return len;
+  void fail(const std::string& msg) {
+    std::lock_guard<std::mutex> lk(mu_);
+    fail_msg_ = msg;
+    failed_ = true;
+    cv_.notify_all();
   }
 
   // The reference's reads return whole lines as long as no line reaches the smallest of its buffers: then there is nothing
@@ -523,187 +537,12 @@ class Input {
     return true;
   }
 
-  size_t read_some(char* dst, size_t want, bool* at_end) {
-    if (plain_fd_ >= 0) return read_plain(dst, want, at_end);
-    if (bgzf_fd_ >= 0) return read_bgzf(dst, want, at_end);
-    if (pgz_) return read_pgz(dst, want, at_end);
-    return read_gz(dst, want, at_end);
-  }
-  size_t read_pgz(char* dst, size_t want, bool* at_end) {
-    const size_t len = pgz_->read(dst, want, at_end);
-    if (pgz_->failed()) {  // (zlib's text, as gzerror gives it)
-      std::lock_guard<std::mutex> lk(mu_);
-      fail_msg_ = pgz_->error();
-      failed_ = true;
-      cv_.notify_all();
-    }
-    return len;
-  }
-
-  // ---- BGZF input (bgzip'd FASTQ; SAM/BAM specification 4.1) ------------------------------------------------------
-  // total size of the block that starts at p when p is a BGZF block header (gzip member, FEXTRA with the 'B' 'C'
-  // subfield), 0 otherwise
-  static size_t bgzf_block_size(const unsigned char* p, size_t avail) {
-    if (avail < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-    const size_t xlen = p[10] | ((size_t)p[11] << 8);
-    size_t q = 12;
-    while (q + 4 <= 12 + xlen && q + 4 <= avail) {
-      const size_t slen = p[q + 2] | ((size_t)p[q + 3] << 8);
-      if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2 && q + 6 <= avail) {
-        const size_t bsize = (p[q + 4] | ((size_t)p[q + 5] << 8)) + 1;
-        return bsize >= 12 + xlen + 8 ? bsize : 0;
-      }
-      q += 4 + slen;
-    }
-    return 0;
-  }
-  // up to `want` inflated bytes: compressed bytes are read in pieces of 32 MiB, the blocks in them are listed
-  // (their sizes are in their headers and trailers) and every block is inflated to its own place, many at a time.
-  // Whole blocks only: fewer than 64 KiB short of `want` is "full".
-  size_t read_bgzf(char* dst, size_t want, bool* at_end) {
-    struct Block {
-      size_t at, size, xlen, out_at, isize;
-    };
-    size_t len = 0;
-    auto fail = [&](const char* what) {
-      std::lock_guard<std::mutex> lk(mu_);
-      fail_msg_ = what;
-      failed_ = true;
-      cv_.notify_all();
-    };
-    for (;;) {
-      // refill the compressed window [bz_at_, bz_buf_.size()): what is left of it to the front, then up to 128 MiB of
-      // the file behind it, read by the pool (one thread reads a tmpfs file at a few GB/s - less than the pool inflates)
-      if (bz_buf_.size() - bz_at_ < (1u << 17) && bgzf_off_ < bgzf_size_) {
-        if (!inflate_pool_) {
-          inflate_pool_.reset(new ReaderPool(host_threads()));  // (fq_parallel.h: the cores this process may use)
-        }
-        const size_t old = bz_buf_.size() - bz_at_, add = (size_t)std::min<uint64_t>(128u << 20, bgzf_size_ - bgzf_off_);
-        if (bz_raw_cap_ < old + add) {  // (plain memory, never zero-filled: a vector's resize would write it first)
-          unsigned char* nb = static_cast<unsigned char*>(malloc(old + (128u << 20)));
-          if (!nb) {
-            fail("out of memory");
-            return len;
-          }
-          if (old) memcpy(nb, bz_buf_.data() + bz_at_, old);
-          free(bz_raw_);
-          bz_raw_ = nb;
-          bz_raw_cap_ = old + (128u << 20);
-        } else if (old) memmove(bz_raw_, bz_buf_.data() + bz_at_, old);
-        const unsigned T = (unsigned)std::min<size_t>(inflate_pool_->size(), std::max<size_t>(1, add >> 22));
-        std::atomic<bool> bad_read{false};
-        inflate_pool_->run(T, [&](unsigned t) {
-          const size_t a = (add * t / T) & ~(size_t)4095, b = t + 1 == T ? add : (add * (t + 1) / T) & ~(size_t)4095;
-          size_t done = a;
-          while (done < b) {
-            const ssize_t got = pread(bgzf_fd_, bz_raw_ + old + done, b - done, (off_t)(bgzf_off_ + done));
-            if (got <= 0) {
-              bad_read = true;
-              return;
-            }
-            done += (size_t)got;
-          }
-        });
-        if (bad_read) {
-          fail("read error");
-          return len;
-        }
-        bz_buf_ = Span{bz_raw_, old + add};
-        bz_at_ = 0;
-        bgzf_off_ += add;
-      }
-      if (bz_at_ == bz_buf_.size()) {
-        *at_end = true;
-        return len;
-      }
-      std::vector<Block> blocks;
-      size_t p = bz_at_, total = 0;
-      while (p < bz_buf_.size()) {
-        const size_t bsize = bgzf_block_size(bz_buf_.data() + p, bz_buf_.size() - p);
-        if (!bsize) {
-          if (bz_buf_.size() - p < 18 && bgzf_off_ < bgzf_size_) break;  // a header cut by the window: next round
-          fail("not a BGZF block where one was expected (a bgzip'd file followed by other data?)");
-          return len;
-        }
-        if (p + bsize > bz_buf_.size()) {
-          if (bgzf_off_ < bgzf_size_) break;
-          fail("truncated BGZF block");
-          return len;
-        }
-        const unsigned char* t = bz_buf_.data() + p + bsize - 4;
-        const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
-        if (isize > 65536) {
-          fail("BGZF block larger than 64 KiB");
-          return len;
-        }
-        if (len + total + isize > want) break;
-        const size_t xlen = bz_buf_[p + 10] | ((size_t)bz_buf_[p + 11] << 8);
-        blocks.push_back({p, bsize, xlen, len + total, isize});
-        total += isize;
-        p += bsize;
-      }
-      if (blocks.empty()) {
-        if (p < bz_buf_.size() && bgzf_off_ >= bgzf_size_ && len + 65536 > want) return len;  // no room for the next block
-        if (p < bz_buf_.size() && len + 65536 > want) return len;
-        if (p >= bz_buf_.size() && bgzf_off_ >= bgzf_size_) {
-          *at_end = true;
-          return len;
-        }
-        if (bz_buf_.size() - bz_at_ >= (1u << 17)) return len;  // (cannot be: a window of 128 KiB holds a block)
-        continue;
-      }
-      // (inflating is all this input costs - zlib gives a few hundred MB/s per core, the GPU takes tens of GB/s: every
-      // core the host has, FQGPU_HOST_THREADS caps it)
-      const unsigned T = (unsigned)std::min<size_t>(inflate_pool_->size(), std::max<size_t>(1, blocks.size() / 4));
-      std::atomic<bool> bad{false};
-      const unsigned char* src = bz_buf_.data();
-      inflate_pool_->run(T, [&](unsigned t) {
-        z_stream zs;  // one inflate state per thread and batch, reset per block (setting one up allocates its window)
-        memset(&zs, 0, sizeof(zs));
-        if (inflateInit2(&zs, -15) != Z_OK) {
-          bad = true;
-          return;
-        }
-        for (size_t i = blocks.size() * t / T; i < blocks.size() * (t + 1) / T && !bad; ++i) {
-          const Block& b = blocks[i];
-          if (b.isize == 0) continue;  // (the end-of-file marker, or an empty block)
-          if (inflateReset(&zs) != Z_OK) {
-            bad = true;
-            break;
-          }
-          zs.next_in = const_cast<Bytef*>(src + b.at + 12 + b.xlen);
-          zs.avail_in = (uInt)(b.size - 12 - b.xlen - 8);
-          zs.next_out = reinterpret_cast<Bytef*>(dst + b.out_at);
-          zs.avail_out = (uInt)b.isize;
-          const int rc = inflate(&zs, Z_FINISH);
-          const bool good = rc == Z_STREAM_END && zs.total_out == b.isize;
-          const unsigned char* c = src + b.at + b.size - 8;
-          const uint32_t want_crc = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
-          if (!good || (uint32_t)crc32(crc32(0L, Z_NULL, 0), reinterpret_cast<const Bytef*>(dst + b.out_at), (uInt)b.isize) != want_crc)
-            bad = true;
-        }
-        inflateEnd(&zs);
-      });
-      if (bad) {
-        fail("corrupt BGZF block (inflate or CRC-32 failed)");
-        return len;
-      }
-      len += total;
-      bz_at_ = p;
-      if (bz_at_ == bz_buf_.size() && bgzf_off_ >= bgzf_size_) {
-        *at_end = true;
-        return len;
-      }
-      if (len + 65536 > want) return len;
-    }
-  }
-
   void produce() {
     // pinning a slot takes as long as filling it: the slots behind the first are allocated by a helper while the first
     // is being read (the file may well end inside the first)
     const size_t head = std::min(kHead, std::max<size_t>(cap_, 4096));  // (tiny files: tiny slots)
     std::thread helper;
-    const bool more = plain_fd_ >= 0 && plain_size_ > cap_;  // (gz input, stdin: unknown - the slots are pinned as they are needed)
+    const bool more = src_.plain_bytes() > cap_;  // (gz input, stdin: unknown - the slots are pinned as they are needed)
     if (more)
       helper = std::thread([this, head] {
         for (int i = 1; i < kSlots; ++i) {
@@ -729,49 +568,39 @@ class Input {
         if (quit_) return;
       }
       if (!s.buf) {
-        if (i > 0 && more) {
-          std::lock_guard<std::mutex> lk(mu_);
-          fail_msg_ = "unable to allocate pinned memory";
-          failed_ = true;
-          cv_.notify_all();
-          return;
-        }
+        if (i > 0 && more) return fail("unable to allocate pinned memory");
         s.buf = alloc(head + slot_room() + 1);
       }
       s.head = head;
       bool at_end = false;
       size_t len;
-      if (!reframe_) len = read_some(s.buf + s.head, cap_, &at_end);
+      if (!reframe_) len = src_.read(s.buf + s.head, cap_, &at_end);
       else {
         // raw bytes = what the last round held back + a fresh read; the cut form of what can be judged goes out
         char* raw = s.buf + s.head;
         const size_t held = rf_tail_.size(), want = std::max(cap_, kReframeMin) - held;
         if (held) memcpy(raw, rf_tail_.data(), held);
-        const size_t n = held + read_some(raw + held, want, &at_end);
+        const size_t n = held + src_.read(raw + held, want, &at_end);
         bool clean = true;
         size_t taken;
         if (!short_lines_only(raw, n, at_end, &taken)) taken = rf_.run(raw, n, at_end, rf_out_, &clean);
         rf_tail_.assign(raw + taken, n - taken);
         len = taken;
         if (!clean) {
-          if (rf_out_.size() > slot_room()) {  // (cannot be: two bytes per limit - 1 >= 999 bytes were allowed for)
-            std::lock_guard<std::mutex> lk(mu_);
-            fail_msg_ = "internal: a re-framed piece outgrew its slot";
-            failed_ = true;
-            cv_.notify_all();
-            return;
-          }
+          // (cannot be: two bytes per limit - 1 >= 999 bytes were allowed for)
+          if (rf_out_.size() > slot_room()) return fail("internal: a re-framed piece outgrew its slot");
           memcpy(raw, rf_out_.data(), rf_out_.size());
           len = rf_out_.size();
         }
       }
+      if (src_.failed()) return fail(src_.error());
       {
         std::lock_guard<std::mutex> lk(mu_);
         s.len = len;
         s.last = at_end;
         s.ready = true;
         cv_.notify_all();
-        if (at_end || failed_) return;
+        if (at_end) return;
       }
     }
   }
@@ -782,34 +611,22 @@ class Input {
     size_t cap = std::max<size_t>(cap_, 4096), len = whole_carry_;
     // a plain file's size is known: one allocation of exactly what is left (growing by doubling would hold the old and
     // the new pinned buffer at once and copy a 32 GB file seven times); gz input and stdin grow as they go
-    if (plain_fd_ >= 0 && plain_size_ >= plain_off_) cap = std::max<size_t>((size_t)(plain_size_ - plain_off_) + len + 1, 4096);
+    if (src_.kind() == FastqSource::kPlain) cap = std::max<size_t>((size_t)src_.plain_left() + len + 1, 4096);
     char* buf = alloc(cap + 1);
     if (len) memcpy(buf, data_ + carry_at_, len);
     whole_carry_ = 0;
     bool at_end = false;
     while (!at_end) {
-      if (len == cap || (bgzf_fd_ >= 0 && cap - len < 65536)) {  // (read_bgzf fills whole blocks only)
+      if (len == cap || (src_.kind() == FastqSource::kBgzf && cap - len < 65536)) {  // (whole blocks only)
         char* nb = alloc(cap * 2 + 1);
         memcpy(nb, buf, len);
         slot_release(ctx_, buf);
         buf = nb;
         cap *= 2;
       }
-      if (plain_fd_ >= 0) len += read_plain(buf + len, cap - len, &at_end);
-      else if (bgzf_fd_ >= 0) len += read_bgzf(buf + len, cap - len, &at_end);
-      else if (pgz_) len += read_pgz(buf + len, cap - len, &at_end);
-      else {
-        const int got = gzread(gz_, buf + len, (unsigned)std::min<size_t>(cap - len, 1u << 30));
-        if (got < 0) {
-          int en = 0;
-          FQ_PRINT_ERROR("%s.\n", gzerror(gz_, &en));
-          leave(kExitSys);
-        }
-        if (got == 0) at_end = true;
-        len += (size_t)got;
-      }
-      if (failed_) {
-        FQ_PRINT_ERROR("%s.\n", fail_msg_.c_str());
+      len += src_.read(buf + len, cap - len, &at_end);
+      if (src_.failed()) {
+        FQ_PRINT_ERROR("%s.\n", src_.error().c_str());
         leave(kExitSys);
       }
     }
@@ -835,27 +652,10 @@ class Input {
   }
 
   fqg_ctx* ctx_;
-  std::string path_;
-  gzFile gz_ = nullptr;
-  int plain_fd_ = -1;
-  uint64_t plain_size_ = 0, plain_off_ = 0;
-  int bgzf_fd_ = -1;  // bgzip'd input: blocks inflated on many threads (read_bgzf)
-  uint64_t bgzf_size_ = 0, bgzf_off_ = 0;
-  int pgz_fd_ = -1;  // any other gzip file: chunks inflated on many threads (fq_pgzip.h)
-  std::unique_ptr<ParallelGunzip> pgz_;
-  struct Span {  // the compressed window (bytes of bz_raw_)
-    const unsigned char* p = nullptr;
-    size_t n = 0;
-    const unsigned char* data() const { return p; }
-    size_t size() const { return n; }
-    unsigned char operator[](size_t i) const { return p[i]; }
-  } bz_buf_;
-  unsigned char* bz_raw_ = nullptr;
-  size_t bz_raw_cap_ = 0, bz_at_ = 0;
-  std::unique_ptr<ReaderPool> inflate_pool_;
+  FastqSource src_;
   size_t cap_;
   Slot slots_[kSlots];
-  std::unique_ptr<ReaderPool> pool_, scan_pool_;
+  std::unique_ptr<ReaderPool> scan_pool_;
   std::thread producer_;
   std::mutex mu_;
   std::condition_variable cv_;

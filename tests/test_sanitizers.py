@@ -1,7 +1,7 @@
 """ASan / UBSan (and TSan for the reader thread) builds of the CPU-side C / C++ of this repository (SURVEY section 5,
 sanitizer row): the oracle restatements (oracle/fq_oracle.c, rl_oracle.c), the container code of libfastq_gpu.so that
 needs no GPU (compat/range_list_compat.cpp), the host-side (de)compression (host/fq_parallel.h) and the host stager
-(host/fq_input.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
+(host/fq_source.h, fq_input.h, fq_multi.h, fq_blocks.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
 import gzip
 import os
 import subprocess
@@ -108,7 +108,7 @@ def test_host_input_stager_runs_clean(tmpdir, san):
             h = ((h ^ c) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
         return h
     want = ("%d %d" % (len(data), fnv(data))).encode()
-    # bgzip'd input (BGZF: small gzip members that carry their size) is inflated on many threads (fq_input.h, read_bgzf);
+    # bgzip'd input (BGZF: small gzip members that carry their size) is inflated on many threads (fq_source.h, read_bgzf);
     # FQGPU_NO_PARALLEL_INFLATE sends the same file through zlib's gzread instead - the same bytes either way
     from tests import bamgen
     bgz = tmpdir / "x.txt.bgz.gz"
@@ -229,3 +229,91 @@ def test_record_block_cutter_runs_clean(tmpdir, san):
                     out = p.stdout.decode().split()
                     assert p.returncode == 0 and out[-1] == "ok" and int(out[1]) == size, (name, per_block, consumers, p.stdout, p.stderr.decode()[-1500:])
                     assert (b"inflated by chunks" in p.stderr) == bool(extra), p.stderr.decode()[-500:]
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_fastq_source_runs_clean(tmpdir, san):
+    """fq_source.h: every kind of input read through FastqSource::read in calls of 4096 / 100000 / 50000000 bytes, with and
+    without line counting, must give the bytes zlib's gzread gives, raise at_end with the call that delivers the last
+    byte (files of a multiple of `want` bytes included) and report line runs that tile each call's bytes."""
+    flags = ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g", "-O1"]
+    exe = str(tmpdir / ("source_" + san.split(",")[0]))
+    subprocess.run(["g++", "-std=c++17", "-pthread"] + flags + ["-o", exe, os.path.join(CXX, "source_check.cpp"), "-lz"], check=True)
+    from tests import bamgen
+    rng = np.random.default_rng(12)
+    lines = [bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), int(rng.integers(1, 400))).astype(np.uint8)) for _ in range(6000)]
+    data = (b"\n".join(lines) + b"\n")[:12 * 100000]  # (a multiple of two of the three sizes asked for)
+    assert len(data) == 1200000 and len(data) % 4096 != 0
+    big = data * 8 + data[:777]  # (beyond 4 MiB a plain file is read by several threads)
+    files = {"x.txt": data, "big.txt": big, "x.txt.gz": gzip.compress(data, 1), "empty.txt": b"",
+             "x.bgz.gz": bamgen.bgzf(data[:1 << 20], block=0x4000, level=1)[:-28] + bamgen.bgzf(data[1 << 20:], level=1)}
+    inflated = {"x.txt": data, "big.txt": big, "x.txt.gz": data, "empty.txt": b"", "x.bgz.gz": data}
+    for name, content in files.items():
+        (tmpdir / name).write_bytes(content)
+    env = dict(ENV, FQGPU_HOST_THREADS="3", TSAN_OPTIONS="halt_on_error=1")
+    chunked = {"FQGPU_PGZIP_MIN": "0", "FQGPU_PGZIP_CHUNK": "20000", "FQGPU_PGZIP_DEBUG": "1"}
+
+    def run(name, want, count, bgzf="0", limit="-", extra={}, stdin=False):
+        path = str(tmpdir / name)
+        with open(path, "rb") as f:
+            p = subprocess.run([exe, "-" if stdin else path, path, want, count, bgzf, limit], env=dict(env, **extra),
+                               stdin=f if stdin else subprocess.DEVNULL, capture_output=True, timeout=300)
+        size = len(inflated[name]) if limit == "-" else min(len(inflated[name]), int(limit))
+        out = p.stdout.decode().split()
+        assert p.returncode == 0 and out[-1] == "ok" and int(out[1]) == size, (name, want, count, bgzf, limit, extra, stdin, p.stdout, p.stderr.decode()[-1500:])
+        return p
+
+    for want in ("4096", "100000", "50000000"):
+        for count in ("0", "1"):
+            for name in ("x.txt", "big.txt", "empty.txt"):
+                run(name, want, count)
+            run("x.txt.gz", want, count)                                      # one zlib thread
+            p = run("x.txt.gz", want, count, extra=chunked)                   # inflated by chunks (fq_pgzip.h)
+            assert b"inflated by chunks" in p.stderr, p.stderr.decode()[-500:]
+            run("x.bgz.gz", want, count, bgzf="1")                            # block by block
+            run("x.bgz.gz", want, count, bgzf="0")                            # a gzip file like any other: zlib ...
+            p = run("x.bgz.gz", want, count, bgzf="0", extra=chunked)         # ... or chunks
+            assert b"inflated by chunks" in p.stderr, p.stderr.decode()[-500:]
+            run("x.txt", want, count, stdin=True)
+            run("x.txt.gz", want, count, stdin=True)
+            for limit in ("500001", "400000"):                                # mid-file; the second a multiple of 100000
+                run("x.txt", want, count, limit=limit)
+                run("big.txt", want, count, limit="5000001")
+                run("x.txt.gz", want, count, limit=limit)
+                run("x.txt.gz", want, count, limit=limit, extra=chunked)
+                run("x.bgz.gz", want, count, bgzf="1", limit=limit)       # (a limit: bytes, not whole blocks - zlib reads it)
+    broken = bytearray(files["x.bgz.gz"])
+    broken[len(broken) // 2] ^= 0x55  # a flipped byte in the middle of some block: inflate or CRC-32 must notice
+    (tmpdir / "broken.bgz.gz").write_bytes(bytes(broken))
+    bad = str(tmpdir / "broken.bgz.gz")
+    p = subprocess.run([exe, bad, str(tmpdir / "x.txt"), "100000", "1", "1", "-"], env=env, capture_output=True, timeout=300)
+    assert p.returncode == 2 and b"BGZF" in p.stderr, (p.returncode, p.stdout, p.stderr.decode()[-800:])
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_cutters_fail_when_pinned_memory_runs_out(tmpdir, san):
+    """PinnedQueue (fq_input.h) under fq_multi.h and fq_blocks.h: when a slot cannot be pinned - the first, or one
+    behind it - the run ends by itself with "unable to allocate pinned memory" and status 2; nobody is left waiting for
+    a slot that will not come (three consumers, each holding an item while it asks for the next, eight slots)."""
+    flags = ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g", "-O1"]
+    exe = str(tmpdir / ("pinfail_" + san.split(",")[0]))
+    subprocess.run(["g++", "-std=c++17", "-pthread"] + flags + ["-o", exe, os.path.join(CXX, "pin_fail_check.cpp"), "-lz"], check=True)
+    rng = np.random.default_rng(13)
+    recs = []
+    for i in range(6000):
+        n = int(rng.integers(1, 300))
+        seq = bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n).astype(np.uint8))
+        recs.append(b"@r%d\n" % i + seq + b"\n+\n" + b"I" * n + b"\n")
+    data = b"".join(recs)
+    (tmpdir / "many.fq").write_bytes(data)
+    (tmpdir / "many.fq.gz").write_bytes(gzip.compress(data, 1))
+    # (the programs leave through _exit from the thread that learns of the failure, the others still running: threads
+    # that were never joined are no finding here, races are)
+    env = dict(ENV, FQGPU_HOST_THREADS="3", TSAN_OPTIONS="halt_on_error=1:report_thread_leaks=0")
+    for name in ("many.fq", "many.fq.gz"):
+        for which, size in (("pieces", "4096"), ("blocks", "7")):  # (hundreds of pieces, hundreds of blocks)
+            for k in ("1", "3"):
+                p = subprocess.run([exe, str(tmpdir / name), which, size, k], env=env, capture_output=True, timeout=300)
+                assert p.returncode == 2 and b"unable to allocate pinned memory" in p.stderr, (name, which, k, p.returncode, p.stdout, p.stderr.decode()[-1500:])
+            p = subprocess.run([exe, str(tmpdir / name), which, size, "1000000"], env=env, capture_output=True, timeout=300)
+            assert p.returncode == 0 and p.stdout.startswith(b"no failure (%d lines)" % data.count(b"\n")), (name, which, p.stdout, p.stderr.decode()[-1500:])
