@@ -15,11 +15,11 @@
 #include <vector>
 
 #include <chrono>
-#include <map>
 
 #include "fq_common.h"
 #include "fq_multi.h"
 #include "fq_names_multi.h"
+#include "fq_ordered.h"
 
 namespace {
 
@@ -56,7 +56,7 @@ void run_single_noindex(const char* path, Stats& S) {
     const uint64_t& b;
     ~Report() {
       if (on) fprintf(fqhost::diag(), "\nfqgpu timing: %llu pieces, %.3f GB; waiting for the reader %.3f s, copy + validate %.3f s; %.3f s since the program started\n",
-                      (unsigned long long)p, b / 1e9, w, g, (double)clock() / CLOCKS_PER_SEC >= 0 ? since_start() : 0.0);
+                      (unsigned long long)p, b / 1e9, w, g, since_start());
     }
   } report{timing, t_wait, t_gpu, n_pieces, n_bytes};
   for (;;) {
@@ -104,177 +104,167 @@ void run_single_noindex(const char* path, Stats& S) {
 size_t multi_piece_bytes() { return getenv("FQGPU_CHUNK_MB") ? piece_bytes() : (size_t)64 << 20; }
 int multi_slots(size_t n_contexts) { return (int)n_contexts + 3; }
 
-// ---- -r, one file, several GPUs (FQGPU_DEVICES=0,1,..): the same loop over record-aligned pieces that have no
-// order among them (fq_multi.h).  One thread + context + accumulator per device; this thread takes the results in
-// file order, so the ticker, the first finding and its text are the serial loop's; the statistics of a clean file
-// are the element-wise merge of the devices' accumulators (fqg_acc_export / fqg_acc_merge).
-void run_single_noindex_multi(const char* path, Stats& S, const std::vector<int>& devs) {
-  struct Dev {
-    fqg_ctx* ctx = nullptr;
-    fqg_acc* acc = nullptr;
-  };
-  std::vector<Dev> D(devs.size());
-  D[0].ctx = g_ctx;  // (opened on devs[0])
-  D[0].acc = S.acc1;
-  // (before the piece cutter starts to pin its slots: an allocation of the runtime waits for the one in front of it, and
-  // the seven small ones of a context behind slots of tens of MiB took 0.19 s)
-  if (getenv("FQGPU_TIMING")) fprintf(fqhost::diag(), "fqgpu timing: opening %zu more contexts %.3f s after the program started\n", devs.size() - 1, since_start());
-  for (size_t i = 1; i < devs.size(); ++i) {
-    const int rc = fqg_open(devs[i], &D[i].ctx);
-    if (rc != 0) {
-      FQ_PRINT_ERROR("FQGPU_DEVICES: device %d is not a usable MI355X GPU (fqg_open: %d)", devs[i], rc);
-      fqhost::leave(kExitSys);
-    }
-    if (fqg_acc_create(D[i].ctx, &D[i].acc) != 0) die_lib("fqg_acc_create", -1);
-  }
-  if (getenv("FQGPU_TIMING")) fprintf(fqhost::diag(), "fqgpu timing: ... opened %.3f s after the program started\n", since_start());
-  const size_t piece = multi_piece_bytes();
-  struct Done {
-    Piece p;
-    fqg_validate_result r{};
-    int rc = 0;
-    std::string err;
-  };
-  std::map<uint64_t, Done> done;
-  std::mutex mu, fetch_mu;
-  std::condition_variable cv;
-  std::atomic<bool> stop{false};
-  bool exhausted = false;  // (under fetch_mu)
-  uint64_t n_pieces = ~0ull;  // known once the final piece was handed out (under mu)
-  Probe pr;
-  bool rerun_serial = false, probe_printed = false;
-  {
-    AlignedPieces src(g_ctx, path, piece, multi_slots(devs.size()));
-    const bool timing = getenv("FQGPU_TIMING") != nullptr;
+// ---- one file over several GPUs (FQGPU_DEVICES=0,1,..): record-aligned pieces that have no order among them
+// (fq_multi.h) go to whichever context is free - one thread + context + accumulator per device -, and this thread takes
+// the results in file order (fq_ordered.h), so the ticker, the first finding and its text are the serial loop's; the
+// statistics of a clean file are the element-wise merge of the devices' accumulators (fqg_acc_export / fqg_acc_merge).
+struct MultiDev {
+  fqg_ctx* ctx = nullptr;
+  fqg_acc* acc = nullptr;
+};
 
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    auto work = [&](size_t di) {
-      double t_wait = 0, t_gpu = 0;
-      uint64_t n = 0;
-      struct Report {
-        bool on;
-        size_t di;
-        const double &w, &g;
-        const uint64_t& n;
-        ~Report() {
-          if (on) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu pieces; waiting for a piece %.3f s, copy + validate %.3f s; %.3f s since the program started\n",
-                          di, (unsigned long long)n, w, g, since_start());
-        }
-      } report{timing, di, t_wait, t_gpu, n};
-      for (;;) {
-        Done d;
-        fqg_file_state st;
-        const double t0 = timing ? now() : 0;
-        {
-          std::lock_guard<std::mutex> lk(fetch_mu);
-          if (exhausted || stop || !src.next(&d.p)) {
-            exhausted = true;
-            return;
-          }
-          if (d.p.final) exhausted = true;
-          probe_piece(pr, d.p.data, d.p.size, 1);  // piece 0 is handed out first: the state is the first record's
-          st = pr.st;
-        }
-        const double t1 = timing ? now() : 0;
-        d.rc = fqg_validate(D[di].ctx, D[di].acc, d.p.data, d.p.size, FQG_MEM_HOST, d.p.final ? 1 : 0, &st, 0, &d.r);
-        if (timing) t_wait += t1 - t0, t_gpu += now() - t1, ++n;
+// g_ctx (opened on devs[0]) with the accumulator device 0 adds to, and a context + accumulator for every further device
+std::vector<MultiDev> open_devices(const std::vector<int>& devs, fqg_acc* acc_of_first) {
+  const std::vector<fqg_ctx*> ctx = fqhost::open_more_contexts(g_ctx, devs);
+  std::vector<MultiDev> D(devs.size());
+  D[0].acc = acc_of_first;
+  for (size_t i = 0; i < D.size(); ++i) {
+    D[i].ctx = ctx[i];
+    if (i && fqg_acc_create(D[i].ctx, &D[i].acc) != 0) die_lib("fqg_acc_create", -1);
+  }
+  return D;
+}
+
+std::vector<char> export_acc(fqg_acc* acc) {
+  size_t used = 0;
+  if (fqg_acc_export(acc, nullptr, 0, &used) != 0) die_lib("fqg_acc_export", -1);
+  std::vector<char> buf(used);
+  if (fqg_acc_export(acc, buf.data(), buf.size(), &used) != 0) die_lib("fqg_acc_export", -1);
+  buf.resize(used);
+  return buf;
+}
+
+struct PieceDone {  // what comes back from a context
+  Piece p;
+  fqg_file_state st{};  // the state it was validated under
+  fqg_validate_result r{};
+  int rc = 0;
+  std::string err;
+};
+struct PieceTimes {  // FQGPU_TIMING: one context's seconds
+  double gpu = 0, keep = 0;
+};
+using PieceRun = fqhost::OrderedRun<PieceDone>;
+
+// One pass of all devices over a file.  validate_as: the state the records are validated under (null: the file's own,
+// decided from its first record).
+//   keep(di, d)           in context di's thread, behind a validation that went well (may set d.rc / d.err)
+//   report(di, waits, t)  FQGPU_TIMING: context di's line, printed as its thread ends
+//   body(d, stop)         in this thread, piece after piece in file order; false ends the pass.  stop() joins the contexts'
+//                         threads: it comes before anything is printed about a piece that ends the run.
+template <class Keep, class Report, class Body>
+void pieces_over_contexts(const char* path, const std::vector<MultiDev>& D, int is_pe, uint32_t flags, const fqg_file_state* validate_as,
+                          uint64_t limit, Probe& pr, Keep keep, Report report, Body body) {
+  AlignedPieces src(g_ctx, path, multi_piece_bytes(), multi_slots(D.size()), limit);
+  const bool timing = getenv("FQGPU_TIMING") != nullptr;
+  std::vector<PieceTimes> T(D.size());
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  PieceRun run(
+      D.size(), 0,
+      [&](uint64_t, PieceDone& d, bool& last) {
+        if (!src.next(&d.p)) return false;
+        last = d.p.final;
+        probe_piece(pr, d.p.data, d.p.size, is_pe);  // piece 0 is handed out first: the state is the first record's
+        d.st = validate_as ? *validate_as : pr.st;
+        return true;
+      },
+      [&](size_t di, PieceDone& d) {
+        const double t1 = now();
+        d.rc = fqg_validate(D[di].ctx, D[di].acc, d.p.data, d.p.size, FQG_MEM_HOST, d.p.final ? 1 : 0, &d.st, flags, &d.r);
+        const double t2 = now();
         if (d.rc) d.err = fqg_last_error(D[di].ctx);
         else if (!d.p.final && d.r.code == FQG_OK && !d.r.stopped && d.r.consumed != d.p.size) {
           d.rc = FQG_ERR_ARG;
           d.err = "a piece cut at a record boundary was not consumed whole";
-        }
-        std::lock_guard<std::mutex> lk(mu);
-        if (d.p.final) n_pieces = d.p.seq + 1;
-        done.emplace(d.p.seq, std::move(d));
-        cv.notify_all();
-      }
-    };
-    std::vector<std::thread> th;
-    for (size_t i = 0; i < devs.size(); ++i) th.emplace_back(work, i);
-    auto join_all = [&] {
-      stop = true;
-      src.abort();  // (a worker may be waiting for a piece, the producer for a slot that stays held after a finding)
-      for (auto& t : th)
-        if (t.joinable()) t.join();
-    };
-    bool info_pending = true;
-    for (uint64_t k = 0;; ++k) {
-      Done d;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return done.count(k) || k >= n_pieces; });
-        if (!done.count(k)) break;
-        d = std::move(done[k]);
-        done.erase(k);
-      }
-      const uint64_t base = d.p.first_record;
-      const fqg_validate_result& r = d.r;
-      if (d.rc) {
-        join_all();
-        FQ_PRINT_ERROR("GPU library failure in fqg_validate (%d): %s", d.rc, d.err.c_str());
-        fqhost::leave(kExitSys);
-      }
-      if (info_pending && base == 0 && r.n_records > 0) {
-        if (!(r.code && r.record == 0 && is_early_code(r.code))) {
-          print_probe(pr);
-          probe_printed = true;
-        }
-        info_pending = false;
-      }
-      if (r.code) {
-        join_all();
-        const uint64_t R = base + r.record;
-        ticker(base + 1, R, 100000);
-        if (r.code == FQG_E_TRUNCATED) fail_truncated(path, 4 * R);
-        if (r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path, R);
-        print_validation_error(path, 4 * (R + 1), r, locate_record(d.p.data, d.p.size, r.record));
-        fqhost::leave(kExitFormat);
-      }
-      if (r.stopped) {
-        // a NUL at a record start ends the file here (src/fastq.c:250): what later pieces added to the accumulators
-        // does not belong to it.  Rare enough to simply run the serial loop again on one device.
-        join_all();
-        rerun_serial = true;
-        break;
-      }
-      ticker(base + 1, base + r.n_records, 100000);
-      src.release(d.p);
-      if (d.p.final) break;
-    }
-    join_all();
-  }
-  if (rerun_serial) {
-    for (size_t i = 1; i < D.size(); ++i) {
-      fqg_acc_destroy(D[i].acc);
-      fqg_close(D[i].ctx);
-    }
-    if (strcmp(path, "-") == 0) {
-      FQ_PRINT_ERROR("Error in file %s: a NUL byte at a record start with FQGPU_DEVICES on a stream: use one device",
-                     path);
+        } else keep(di, d);
+        T[di].gpu += t2 - t1, T[di].keep += now() - t2;
+      },
+      [&] { src.abort(); },  // (a worker may be waiting for a piece, the producer for a slot that stays held after a finding)
+      [&](size_t di, const PieceRun::Waits& w) {
+        if (timing) report(di, w, T[di]);
+      });
+  const std::function<void()> stop = [&] { run.stop(); };
+  PieceDone d;
+  while (run.next(d)) {
+    if (d.rc) {
+      run.stop();
+      FQ_PRINT_ERROR("GPU library failure in fqg_validate (%d): %s", d.rc, d.err.c_str());
       fqhost::leave(kExitSys);
     }
+    if (!body(d, stop)) break;
+    src.release(d.p);
+    if (d.p.final) break;
+  }
+}  // (`run` goes first: the threads are joined before the cutter is taken down)
+
+[[noreturn]] void refuse_nul_on_stream(const char* path) {
+  FQ_PRINT_ERROR("Error in file %s: a NUL byte at a record start with FQGPU_DEVICES on a stream: use one device", path);
+  fqhost::leave(kExitSys);
+}
+
+// ---- -r, one file, several GPUs: validate_single_fastq_file (src/fastq_info.c:155-176) over the pieces
+void run_single_noindex_multi(const char* path, Stats& S, const std::vector<int>& devs) {
+  // (before the piece cutter starts to pin its slots: an allocation of the runtime waits for the one in front of it, and
+  // the seven small ones of a context behind slots of tens of MiB took 0.19 s)
+  if (getenv("FQGPU_TIMING")) fprintf(fqhost::diag(), "fqgpu timing: opening %zu more contexts %.3f s after the program started\n", devs.size() - 1, since_start());
+  const std::vector<MultiDev> D = open_devices(devs, S.acc1);
+  if (getenv("FQGPU_TIMING")) fprintf(fqhost::diag(), "fqgpu timing: ... opened %.3f s after the program started\n", since_start());
+  Probe pr;
+  bool rerun_serial = false, probe_printed = false, info_pending = true;
+  pieces_over_contexts(
+      path, D, 1, 0, nullptr, ~0ull, pr, [](size_t, PieceDone&) {},
+      [](size_t di, const PieceRun::Waits& w, const PieceTimes& t) {
+        fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu pieces; waiting for a piece %.3f s, copy + validate %.3f s; %.3f s since the program started\n",
+                di, (unsigned long long)w.items, w.fetch, t.gpu, since_start());
+      },
+      [&](const PieceDone& d, const std::function<void()>& stop) {
+        const uint64_t base = d.p.first_record;
+        const fqg_validate_result& r = d.r;
+        if (info_pending && base == 0 && r.n_records > 0) {
+          if (!(r.code && r.record == 0 && is_early_code(r.code))) {
+            print_probe(pr);
+            probe_printed = true;
+          }
+          info_pending = false;
+        }
+        if (r.code) {
+          stop();
+          const uint64_t R = base + r.record;
+          ticker(base + 1, R, 100000);
+          if (r.code == FQG_E_TRUNCATED) fail_truncated(path, 4 * R);
+          if (r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path, R);
+          print_validation_error(path, 4 * (R + 1), r, locate_record(d.p.data, d.p.size, r.record));
+          fqhost::leave(kExitFormat);
+        }
+        // a NUL at a record start ends the file here (src/fastq.c:250): what later pieces added to the accumulators
+        // does not belong to it.  Rare enough to simply run the serial loop again on one device.
+        if (r.stopped) {
+          rerun_serial = true;
+          return false;
+        }
+        ticker(base + 1, base + r.n_records, 100000);
+        return true;
+      });
+  for (size_t i = 1; i < D.size(); ++i) {
+    if (!rerun_serial) {
+      const std::vector<char> buf = export_acc(D[i].acc);
+      LIB(fqg_acc_merge(S.acc1, buf.data(), buf.size()));
+    }
+    fqg_acc_destroy(D[i].acc);
+    fqg_close(D[i].ctx);
+  }
+  if (rerun_serial) {
+    if (strcmp(path, "-") == 0) refuse_nul_on_stream(path);
     LIB(fqg_acc_reset(S.acc1));
     probe_line_is_out() = probe_printed;
     run_single_noindex(path, S);
     probe_line_is_out() = false;
     return;
   }
-  {
-    std::vector<char> buf;
-    for (size_t i = 1; i < D.size(); ++i) {
-      size_t used = 0;
-      if (fqg_acc_export(D[i].acc, nullptr, 0, &used) != 0) die_lib("fqg_acc_export", -1);
-      buf.resize(used);
-      if (fqg_acc_export(D[i].acc, buf.data(), buf.size(), &used) != 0) die_lib("fqg_acc_export", -1);
-      LIB(fqg_acc_merge(S.acc1, buf.data(), used));
-      fqg_acc_destroy(D[i].acc);
-      fqg_close(D[i].ctx);
-    }
-    printf("\n");
-    fqg_file_stats fs;
-    LIB(fqg_acc_read(S.acc1, &fs));
-    S.num_reads1 = fs.num_rds;
-  }
+  printf("\n");
+  fqg_file_stats fs;
+  LIB(fqg_acc_read(S.acc1, &fs));
+  S.num_reads1 = fs.num_rds;
 }
 
 // ---- default and paired modes over several GPUs (FQGPU_DEVICES=0,1,..) --------------------------------------------
@@ -282,10 +272,6 @@ void run_single_noindex_multi(const char* path, Stats& S, const std::vector<int>
 // kept) by whichever context is free, and the names are tested ACROSS the contexts by the fingerprint exchange of
 // fq_names_multi.h instead of one device's index.  Findings are ordered as the serial loops order them: per record
 // read (truncation), name (wrong header), duplicate / unpaired, validation.
-struct MultiDev {
-  fqg_ctx* ctx = nullptr;
-  fqg_acc* acc = nullptr;
-};
 struct MultiPass {
   bool stopped = false;       // a NUL at a record start ends the file there: the caller passes again with that limit
   uint64_t stop_offset = 0;   // ... bytes of the (inflated) file in front of that record
@@ -300,149 +286,55 @@ struct MultiPass {
   std::vector<fqhost::NameShard> shards;  // per device: the frames it kept
 };
 
-// one pass of all devices over a file.  validate_as: the state the records are validated under (null: the file's
-// own, decided from its first record); acc_of_first: the accumulator device 0 adds to
-MultiPass multi_pass(const char* path, std::vector<MultiDev>& D, int is_pe, uint32_t flags, const fqg_file_state* validate_as,
+MultiPass multi_pass(const char* path, const std::vector<MultiDev>& D, int is_pe, uint32_t flags, const fqg_file_state* validate_as,
                      uint64_t limit = ~0ull, bool print_info = true) {
   MultiPass out;
   out.shards.resize(D.size());
   for (size_t i = 0; i < D.size(); ++i) out.shards[i].ctx = D[i].ctx;
-  const size_t piece = multi_piece_bytes();
-  struct Done {
-    Piece p;
-    fqg_validate_result r{};
-    int rc = 0;
-    std::string err;
-  };
-  std::map<uint64_t, Done> done;
-  std::mutex mu, fetch_mu, shard_mu;
-  std::condition_variable cv;
-  std::atomic<bool> stop{false};
-  bool exhausted = false;        // (under fetch_mu)
-  uint64_t n_pieces = ~0ull;     // known once the final piece was handed out (under mu)
-  AlignedPieces src(g_ctx, path, piece, multi_slots(D.size()), limit);
-  const bool timing = getenv("FQGPU_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  auto work = [&](size_t di) {
-    double t_wait = 0, t_gpu = 0, t_keep = 0;
-    uint64_t n = 0;
-    struct Report {
-      bool on;
-      size_t di;
-      const double &w, &g, &k;
-      const uint64_t& n;
-      ~Report() {
-        if (on) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu pieces; waiting for a piece %.3f s, copy + validate %.3f s, keeping the frame %.3f s\n",
-                        di, (unsigned long long)n, w, g, k);
-      }
-    } report{timing, di, t_wait, t_gpu, t_keep, n};
-    for (;;) {
-      Done d;
-      fqg_file_state st;
-      const double t0 = timing ? now() : 0;
-      {
-        std::lock_guard<std::mutex> lk(fetch_mu);
-        if (exhausted || stop || !src.next(&d.p)) {
-          exhausted = true;
-          return;
-        }
-        if (d.p.final) exhausted = true;
-        probe_piece(out.pr, d.p.data, d.p.size, is_pe);  // piece 0 is handed out first: the state is the first record's
-        st = validate_as ? *validate_as : out.pr.st;
-      }
-      const double t1 = timing ? now() : 0;
-      d.rc = fqg_validate(D[di].ctx, D[di].acc, d.p.data, d.p.size, FQG_MEM_HOST, d.p.final ? 1 : 0, &st, flags, &d.r);
-      const double t2 = timing ? now() : 0;
-      if (d.rc) d.err = fqg_last_error(D[di].ctx);
-      else if (!d.p.final && d.r.code == FQG_OK && !d.r.stopped && d.r.consumed != d.p.size) {
-        d.rc = FQG_ERR_ARG;
-        d.err = "a piece cut at a record boundary was not consumed whole";
-      } else if (d.r.n_records) {
+  bool info_pending = true;
+  pieces_over_contexts(
+      path, D, is_pe, flags, validate_as, limit, out.pr,
+      [&](size_t di, PieceDone& d) {
+        if (!d.r.n_records) return;
         fqg_frame* fr = nullptr;
         d.rc = fqg_frame_retain(D[di].ctx, &fr);
         if (d.rc) d.err = fqg_last_error(D[di].ctx);
-        else {
-          std::lock_guard<std::mutex> lk(shard_mu);
-          out.shards[di].pieces.push_back(fqhost::NameShard::Piece{fr, d.p.first_record, d.r.n_records});
+        // (shards[di] is this thread's alone until the threads are joined)
+        else out.shards[di].pieces.push_back(fqhost::NameShard::Piece{fr, d.p.first_record, d.r.n_records});
+      },
+      [](size_t di, const PieceRun::Waits& w, const PieceTimes& t) {
+        fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu pieces; waiting for a piece %.3f s, copy + validate %.3f s, keeping the frame %.3f s\n",
+                di, (unsigned long long)w.items, w.fetch, t.gpu, t.keep);
+      },
+      [&](const PieceDone& d, const std::function<void()>&) {  // (nothing is printed here about a piece that ends the pass)
+        const uint64_t base = d.p.first_record;
+        const fqg_validate_result& r = d.r;
+        int stage = -1;
+        if (r.code == FQG_E_TRUNCATED || r.code == FQG_E_LINE_TOO_LONG) stage = 0;
+        else if (r.code == FQG_E_HDR1_AT) stage = 1;
+        else if (r.code) stage = 3;
+        if (info_pending && base == 0 && r.n_records > 0) {
+          if (!(stage >= 0 && stage <= 1 && r.record == 0)) {
+            if (print_info) print_probe(out.pr);
+            out.probe_printed = true;
+          }
+          info_pending = false;
         }
-      }
-      if (timing) t_wait += t1 - t0, t_gpu += t2 - t1, t_keep += now() - t2, ++n;
-      std::lock_guard<std::mutex> lk(mu);
-      if (d.p.final) n_pieces = d.p.seq + 1;
-      done.emplace(d.p.seq, std::move(d));
-      cv.notify_all();
-    }
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 0; i < D.size(); ++i) th.emplace_back(work, i);
-  auto join_all = [&] {
-    stop = true;
-    src.abort();
-    for (auto& t : th)
-      if (t.joinable()) t.join();
-  };
-  bool info_pending = true;
-  for (uint64_t k = 0;; ++k) {
-    Done d;
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return done.count(k) || k >= n_pieces; });
-      if (!done.count(k)) break;
-      d = std::move(done[k]);
-      done.erase(k);
-    }
-    const uint64_t base = d.p.first_record;
-    const fqg_validate_result& r = d.r;
-    if (d.rc) {
-      join_all();
-      FQ_PRINT_ERROR("GPU library failure in fqg_validate (%d): %s", d.rc, d.err.c_str());
-      fqhost::leave(kExitSys);
-    }
-    int stage = -1;
-    if (r.code == FQG_E_TRUNCATED || r.code == FQG_E_LINE_TOO_LONG) stage = 0;
-    else if (r.code == FQG_E_HDR1_AT) stage = 1;
-    else if (r.code) stage = 3;
-    if (info_pending && base == 0 && r.n_records > 0) {
-      if (!(stage >= 0 && stage <= 1 && r.record == 0)) {
-        if (print_info) print_probe(out.pr);
-        out.probe_printed = true;
-      }
-      info_pending = false;
-    }
-    if (r.stopped && stage < 0) {
-      join_all();
-      out.stopped = true;
-      out.stop_offset = d.p.stream_offset + r.consumed;
-      return out;
-    }
-    if (stage >= 0) {
-      join_all();
-      out.have = true;
-      out.rec = base + r.record;
-      out.stage = stage;
-      out.r = r;
-      out.text = locate_record(d.p.data, d.p.size, r.record);
-      out.n_records = base + r.n_records;
-      return out;
-    }
-    out.n_records = base + r.n_records;
-    src.release(d.p);
-    if (d.p.final) break;
-  }
-  join_all();
+        if (r.stopped && stage < 0) {
+          out.stopped = true;
+          out.stop_offset = d.p.stream_offset + r.consumed;
+          return false;
+        }
+        out.n_records = base + r.n_records;
+        if (stage < 0) return true;
+        out.have = true;
+        out.rec = base + r.record;
+        out.stage = stage;
+        out.r = r;
+        out.text = locate_record(d.p.data, d.p.size, r.record);
+        return false;
+      });
   return out;
-}
-
-void merge_device_stats(std::vector<MultiDev>& D, Stats& S) {
-  std::vector<char> buf;
-  for (size_t i = 1; i < D.size(); ++i) {
-    size_t used = 0;
-    if (fqg_acc_export(D[i].acc, nullptr, 0, &used) != 0) die_lib("fqg_acc_export", -1);
-    buf.resize(used);
-    if (fqg_acc_export(D[i].acc, buf.data(), buf.size(), &used) != 0) die_lib("fqg_acc_export", -1);
-    LIB(fqg_acc_merge(S.acc1, buf.data(), used));
-    if (fqg_acc_reset(D[i].acc) != 0) die_lib("fqg_acc_reset", -1);
-  }
 }
 
 void release_shards(std::vector<fqhost::NameShard>& sh) {
@@ -451,42 +343,75 @@ void release_shards(std::vector<fqhost::NameShard>& sh) {
   sh.clear();
 }
 
+// A pass, and where a NUL byte at a record start ends the file (src/fastq.c:250) one more: what later pieces added to the
+// accumulators and to the shards does not belong to it, so restore() puts the accumulators back where they were and the
+// file is passed once more, ending where the reference stops reading
+template <class Restore>
+MultiPass pass_up_to_nul(const char* path, const std::vector<MultiDev>& D, int is_pe, uint32_t flags, const fqg_file_state* validate_as, Restore restore) {
+  MultiPass pass = multi_pass(path, D, is_pe, flags, validate_as);
+  if (!pass.stopped) return pass;
+  release_shards(pass.shards);
+  if (strcmp(path, "-") == 0) refuse_nul_on_stream(path);
+  restore();
+  pass = multi_pass(path, D, is_pe, flags, validate_as, pass.stop_offset, !pass.probe_printed);
+  if (pass.stopped) {
+    FQ_PRINT_ERROR("Error in file %s: the file changed while it was read", path);
+    fqhost::leave(kExitSys);
+  }
+  return pass;
+}
+
+// Which finding does the serial loop hit first?  Per record: read (0), name (1), duplicate / unpaired (2: `name_found` at
+// record `name_rec`, said as `name_what` + `name`), validation (3: said of verr_path at *verr_line; null: the record's own
+// line).  Leaves with it; returns when there is none.
+void leave_on_first_finding(const char* path, const MultiPass& pass, bool name_found, uint64_t name_rec, const char* name_what,
+                            const std::string& name, const char* verr_path, const unsigned long* verr_line) {
+  uint64_t best = ~0ull;
+  int stage = 9;
+  if (pass.have) {
+    best = pass.rec;
+    stage = pass.stage;
+  }
+  if (name_found && (name_rec < best || (name_rec == best && 2 < stage))) {
+    best = name_rec;
+    stage = 2;
+  }
+  if (best == ~0ull) return;
+  ticker(1, best, 100000);
+  if (stage == 0) {
+    if (pass.r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path, best);
+    fail_truncated(path, 4 * best);
+  }
+  if (stage == 1) fail_wrong_header(path, 4 * (best + 1), pass.text.l[0]);
+  if (stage == 2) {
+    FQ_PRINT_ERROR("Error in file %s: line %lu: %s %s", path, (unsigned long)(4 * (best + 1)), name_what, name.c_str());
+    fqhost::leave(kExitFormat);
+  }
+  print_validation_error(verr_path, verr_line ? *verr_line : (unsigned long)(4 * (best + 1)), pass.r, pass.text);
+  fqhost::leave(kExitFormat);
+}
+
+void merge_device_stats(const std::vector<MultiDev>& D, Stats& S) {
+  for (size_t i = 1; i < D.size(); ++i) {
+    const std::vector<char> buf = export_acc(D[i].acc);
+    LIB(fqg_acc_merge(S.acc1, buf.data(), buf.size()));
+    if (fqg_acc_reset(D[i].acc) != 0) die_lib("fqg_acc_reset", -1);
+  }
+}
+
 struct MultiIndexed {
   std::vector<MultiDev> D;
   fqhost::NamesOfFile f1;
 };
 
-// file 1 of the default / paired mode.  Always returns true (a file that holds a NUL at a record start is passed over
-// once more with the limit the first pass found, below; nothing falls back to the one-device loop any more).
-bool run_index_multi(const char* path, int is_pe, Stats& S, IndexedFile& F, MultiIndexed& M, const std::vector<int>& devs) {
-  M.D.resize(devs.size());
-  M.D[0].ctx = g_ctx;
-  M.D[0].acc = S.acc1;
-  for (size_t i = 1; i < devs.size(); ++i) {
-    const int rc = fqg_open(devs[i], &M.D[i].ctx);
-    if (rc != 0) {
-      FQ_PRINT_ERROR("FQGPU_DEVICES: device %d is not a usable MI355X GPU (fqg_open: %d)", devs[i], rc);
-      fqhost::leave(kExitSys);
-    }
-    if (fqg_acc_create(M.D[i].ctx, &M.D[i].acc) != 0) die_lib("fqg_acc_create", -1);
-  }
-  MultiPass pass = multi_pass(path, M.D, is_pe, FQG_VALIDATE_COUNT_TWICE | FQG_VALIDATE_INDEX, nullptr);
-  if (pass.stopped) {
-    // a NUL byte at a record start ends the file there (src/fastq.c:250): what later pieces added to the accumulators
-    // and to the shards does not belong to it - once more, with the file ending where the reference stops reading
-    release_shards(pass.shards);
-    if (strcmp(path, "-") == 0) {
-      FQ_PRINT_ERROR("Error in file %s: a NUL byte at a record start with FQGPU_DEVICES on a stream: use one device", path);
-      fqhost::leave(kExitSys);
-    }
+// file 1 of the default / paired mode (a file that holds a NUL at a record start is passed over once more with the limit
+// the first pass found; nothing falls back to the one-device loop)
+void run_index_multi(const char* path, int is_pe, Stats& S, IndexedFile& F, MultiIndexed& M, const std::vector<int>& devs) {
+  M.D = open_devices(devs, S.acc1);
+  MultiPass pass = pass_up_to_nul(path, M.D, is_pe, FQG_VALIDATE_COUNT_TWICE | FQG_VALIDATE_INDEX, nullptr, [&] {
     for (auto& d : M.D)
       if (fqg_acc_reset(d.acc) != 0) die_lib("fqg_acc_reset", -1);
-    pass = multi_pass(path, M.D, is_pe, FQG_VALIDATE_COUNT_TWICE | FQG_VALIDATE_INDEX, nullptr, pass.stop_offset, !pass.probe_printed);
-    if (pass.stopped) {
-      FQ_PRINT_ERROR("Error in file %s: the file changed while it was read", path);
-      fqhost::leave(kExitSys);
-    }
-  }
+  });
   M.f1.shards = std::move(pass.shards);
   M.f1.st = pass.pr.st;
   M.f1.flag = 0;
@@ -501,38 +426,13 @@ bool run_index_multi(const char* path, int is_pe, Stats& S, IndexedFile& F, Mult
     FQ_PRINT_ERROR("GPU library failure in the read-name exchange: %s", ex.error.c_str());
     fqhost::leave(kExitSys);
   }
-  // which finding does the serial loop hit first?  per record: read (0), name (1), duplicate (2), validation (3)
-  uint64_t best = ~0ull;
-  int stage = 9;
-  if (pass.have) {
-    best = pass.rec;
-    stage = pass.stage;
-  }
-  if (dup && (dup_rec < best || (dup_rec == best && 2 < stage))) {
-    best = dup_rec;
-    stage = 2;
-  }
-  if (best != ~0ull) {
-    ticker(1, best, 100000);
-    if (stage == 0) {
-      if (pass.r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path, best);
-      fail_truncated(path, 4 * best);
-    }
-    if (stage == 1) fail_wrong_header(path, 4 * (best + 1), pass.text.l[0]);
-    if (stage == 2) {
-      FQ_PRINT_ERROR("Error in file %s: line %lu: duplicated sequence %s", path, (unsigned long)(4 * (best + 1)), dup_name.c_str());
-      fqhost::leave(kExitFormat);
-    }
-    print_validation_error(path, 4 * (best + 1), pass.r, pass.text);
-    fqhost::leave(kExitFormat);
-  }
+  leave_on_first_finding(path, pass, dup, dup_rec, "duplicated sequence", dup_name, path, nullptr);
   ticker(1, pass.n_records, 100000);
   merge_device_stats(M.D, S);
   F.st = pass.pr.st;
   F.n_records = pass.n_records;
   F.entries = pass.n_records;
   F.index_mem = 8 + pass.n_records * (16 + 1 + 24) + name_bytes;  // what the reference adds up (src/fastq.c:609, src/fastq_info.c:293)
-  return true;
 }
 
 // the second file of a pair over the same devices (src/fastq_info.c:322-362)
@@ -540,30 +440,14 @@ void run_pair_second_file_multi(const char* path1, const char* path2, Stats& S, 
   const unsigned long cline1 = 4 * F.n_records;  // fd1->cline stays where indexing left it
   // file-2 records are validated against file 1's state and counters (src/fastq_info.c:345); names under file 2's own
   // (the accumulators as file 1 left them: a second file that ends at a NUL byte is passed over twice)
-  std::vector<std::vector<char>> before(M.D.size());
-  for (size_t i = 0; i < M.D.size(); ++i) {
-    size_t used = 0;
-    if (fqg_acc_export(M.D[i].acc, nullptr, 0, &used) != 0) die_lib("fqg_acc_export", -1);
-    before[i].resize(used);
-    if (fqg_acc_export(M.D[i].acc, before[i].data(), before[i].size(), &used) != 0) die_lib("fqg_acc_export", -1);
-  }
-  MultiPass pass = multi_pass(path2, M.D, 1, FQG_VALIDATE_INDEX, &F.st);
-  if (pass.stopped) {
-    release_shards(pass.shards);
-    if (strcmp(path2, "-") == 0) {
-      FQ_PRINT_ERROR("Error in file %s: a NUL byte at a record start with FQGPU_DEVICES on a stream: use one device", path2);
-      fqhost::leave(kExitSys);
-    }
+  std::vector<std::vector<char>> before;
+  for (const MultiDev& d : M.D) before.push_back(export_acc(d.acc));
+  MultiPass pass = pass_up_to_nul(path2, M.D, 1, FQG_VALIDATE_INDEX, &F.st, [&] {
     for (size_t i = 0; i < M.D.size(); ++i) {
       if (fqg_acc_reset(M.D[i].acc) != 0) die_lib("fqg_acc_reset", -1);
       if (fqg_acc_merge(M.D[i].acc, before[i].data(), before[i].size()) != 0) die_lib("fqg_acc_merge", -1);
     }
-    pass = multi_pass(path2, M.D, 1, FQG_VALIDATE_INDEX, &F.st, pass.stop_offset, !pass.probe_printed);
-    if (pass.stopped) {
-      FQ_PRINT_ERROR("Error in file %s: the file changed while it was read", path2);
-      fqhost::leave(kExitSys);
-    }
-  }
+  });
   fqhost::NamesOfFile f2;
   f2.shards = std::move(pass.shards);
   f2.st = pass.pr.st;
@@ -582,30 +466,8 @@ void run_pair_second_file_multi(const char* path1, const char* path2, Stats& S, 
     FQ_PRINT_ERROR("GPU library failure in the read-name exchange: %s", ex.error.c_str());
     fqhost::leave(kExitSys);
   }
-  uint64_t best = ~0ull;
-  int stage = 9;
-  if (pass.have) {
-    best = pass.rec;
-    stage = pass.stage;
-  }
-  if (po.has_first && (po.first_unpaired < best || (po.first_unpaired == best && 2 < stage))) {
-    best = po.first_unpaired;
-    stage = 2;
-  }
-  if (best != ~0ull) {
-    ticker(1, best, 100000);
-    if (stage == 0) {
-      if (pass.r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path2, best);
-      fail_truncated(path2, 4 * best);
-    }
-    if (stage == 1) fail_wrong_header(path2, 4 * (best + 1), pass.text.l[0]);
-    if (stage == 2) {
-      FQ_PRINT_ERROR("Error in file %s: line %lu: unpaired read - %s", path2, (unsigned long)(4 * (best + 1)), po.first_name.c_str());
-      fqhost::leave(kExitFormat);
-    }
-    print_validation_error(path1, cline1, pass.r, pass.text);  // named after file 1, like the reference
-    fqhost::leave(kExitFormat);
-  }
+  // (a validation finding is named after file 1, like the reference)
+  leave_on_first_finding(path2, pass, po.has_first, po.first_unpaired, "unpaired read -", po.first_name, path1, &cline1);
   ticker(1, pass.n_records, 100000);
   merge_device_stats(M.D, S);
   printf("\n");
@@ -788,7 +650,7 @@ void run_paired_sorted(const char* p1, const char* p2, Stats& S) {
   if (r2.n_records) LIB(fqg_frame_retain(g_ctx, &f2));
   fqg_index_result cr{};
   if (f1 && f2) LIB(fqg_names_compare(g_ctx, f1, &pr1.st, f2, &pr2.st, &cr));
-  const uint64_t n1 = r1.stopped ? r1.n_records : r1.n_records, n2 = r2.n_records;
+  const uint64_t n1 = r1.n_records, n2 = r2.n_records;
   // read failures: a NUL-started line inside the file (reported as the first finding), or an
   // incomplete last record (always known through tail_lines)
   const bool t1 = r1.code == FQG_E_TRUNCATED || r1.code == FQG_E_LINE_TOO_LONG;
@@ -981,10 +843,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "DEFAULT_HASHSIZE=%lu\n", 39000001ul);
     fprintf(stderr, "Scanning and indexing all reads from %s\n", file1);
     F.lookups = is_paired_data && file2 != nullptr;  // (one file, or "pe": the index is only the uniqueness test)
-    if (!(devices.size() > 1 && run_index_multi(file1, is_paired_data, S, F, multi, devices))) {
-      multi.D.clear();
-      run_index_file(file1, is_paired_data, S, F);
-    }
+    if (devices.size() > 1) run_index_multi(file1, is_paired_data, S, F, multi, devices);
+    else run_index_file(file1, is_paired_data, S, F);
     fprintf(stderr, "Scanning complete.\n");
     S.num_reads1 = F.entries;
     fprintf(stderr, "\n");

@@ -12,7 +12,6 @@
 #include <algorithm>
 #include <chrono>
 #include <deque>
-#include <map>
 #include <set>
 #include <functional>
 #include <string>
@@ -21,6 +20,7 @@
 #include "fq_blocks.h"
 #include "fq_input.h"
 #include "fq_multi.h"
+#include "fq_ordered.h"
 #include "fq_parallel.h"
 
 // SURVEY 5 "metrics", as bin/fastq_info has it: FQGPU_JSON_METRICS=<file> writes the machine-readable twin of the
@@ -230,15 +230,7 @@ struct BlockRun {
 
 [[noreturn]] void run_blocks(const BlockRun& A, const std::vector<int>& devs) {
   const size_t nd = devs.size();
-  std::vector<fqg_ctx*> ctx(nd, nullptr);
-  ctx[0] = g_ctx;  // (opened on devs[0])
-  for (size_t i = 1; i < nd; ++i) {
-    const int rc = fqg_open(devs[i], &ctx[i]);
-    if (rc != 0) {
-      FQ_PRINT_ERROR("FQGPU_DEVICES: device %d is not a usable MI355X GPU (fqg_open: %d)", devs[i], rc);
-      fqhost::leave(kExitSys);
-    }
-  }
+  const std::vector<fqg_ctx*> ctx = fqhost::open_more_contexts(g_ctx, devs);  // (ctx[0]: g_ctx, opened on devs[0])
   RecordBlocks* cut[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   fqg_file_state st0[6];
   memset(st0, 0, sizeof(st0));
@@ -275,6 +267,7 @@ struct BlockRun {
     char* out[3] = {nullptr, nullptr, nullptr};   // the text of every output: pinned buffers that go round (OutPool)
     size_t out_cap[3] = {0, 0, 0};
     std::string wrong_header;                     // the text of the header line of a FQG_E_WRONG_HEADER finding
+    Block b[6];                                   // the context's thread's: given back before the unit is handed over
   };
   // The text a unit brings back from the GPU: pinned buffers that go round between the contexts' threads and the thread
   // that writes.  Into fresh pageable memory the copy ran at 7.5 GB/s per context (page faults, a bounce buffer) and the
@@ -351,180 +344,136 @@ struct BlockRun {
   const uint64_t window = nd + 1;
   const size_t outs_per_unit = A.out_sam ? 1 : (size_t)((A.P->emit[1] ? 1 : 0) + (A.P->emit[2] ? 1 : 0));
   OutPool out_pool{g_ctx, (size_t)window * std::max<size_t>(outs_per_unit, 1)};
-  uint64_t n_written = 0;  // units the writer is done with (under mu)
-  std::map<uint64_t, Unit> done;
-  std::mutex mu, fetch_mu;
-  std::condition_variable cv;
-  std::atomic<bool> stop{false};
-  bool exhausted = false;     // (under fetch_mu)
-  uint64_t next_seq = 0;      // (under fetch_mu)
-  uint64_t n_units = ~0ull;   // known once a unit with the end of an input was handed out (under mu)
-
   const bool timing = getenv("FQGPU_TIMING") != nullptr;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  auto work = [&](size_t di) {
-    fqg_ctx* c = ctx[di];
-    double t_wait = 0, t_frame = 0, t_transform = 0, t_out = 0, t_hand = 0;
-    uint64_t n_units_done = 0;
-    struct Report {
-      bool on;
-      size_t di;
-      const double &w, &f, &t, &o, &h;
-      const uint64_t& n;
-      ~Report() {
-        if (on) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu units; waiting for blocks %.3f s, copy + framing %.3f s, transform %.3f s, output D2H %.3f s, handing over %.3f s\n",
-                        di, (unsigned long long)n, w, f, t, o, h);
-      }
-    } report{timing, di, t_wait, t_frame, t_transform, t_out, t_hand, n_units_done};
-    for (;;) {
-      Unit u;
-      Block b[6];
-      const double t0 = timing ? now() : 0;
-      {
-        std::lock_guard<std::mutex> lk(fetch_mu);
-        {
-          std::unique_lock<std::mutex> lk2(mu);
-          cv.wait(lk2, [&] { return stop.load() || next_seq < n_written + window; });
-        }
-        if (exhausted || stop) return;
-        bool all = true;
-        for (int x = READ1; x <= INDEX3 && all; ++x)
-          if (cut[x] && !cut[x]->next(&b[x])) all = false;
-        if (!all) {  // (only after an abort: a unit that holds the end of an input is the last one handed out)
-          exhausted = true;
-          return;
-        }
-        u.seq = next_seq++;
+  struct UnitTimes {  // FQGPU_TIMING: one context's seconds
+    double frame = 0, transform = 0, out = 0;
+  };
+  std::vector<UnitTimes> T(nd);
+  using UnitRun = OrderedRun<Unit>;
+  // (fq_ordered.h: the units to whichever context is free, the results to this thread in unit order)
+  UnitRun run(
+      nd, window,
+      [&](uint64_t seq, Unit& u, bool& last) {
+        for (int x = READ1; x <= INDEX3; ++x)  // (false only after an abort: a unit that holds the end of an input is the last one handed out)
+          if (cut[x] && !cut[x]->next(&u.b[x])) return false;
+        u.seq = seq;
         for (int x = READ1; x <= INDEX3; ++x)
-          if (cut[x] && b[x].final) exhausted = true;
-        if (exhausted) {
-          std::lock_guard<std::mutex> lk2(mu);
-          n_units = u.seq + 1;
-        }
-      }
-      const double t1 = timing ? now() : 0;
-      t_wait += t1 - t0;
-      const fqg_frame* frames[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      fqg_frame* held[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      fqg_file_state states[6];
-      memcpy(states, st0, sizeof(states));
-      uint64_t first[6] = {0, 0, 0, 0, 0, 0};
-      auto lib_fail = [&](const char* what, int rc) {
-        u.rc = rc;
-        u.err = std::string(what) + ": " + fqg_last_error(c);
-      };
-      u.n = ~0ull;
-      for (int x = READ1; x <= INDEX3 && !u.rc; ++x)
-        if (cut[x]) {
-          fqg_validate_result r;
-          const int rc = fqg_validate(c, nullptr, b[x].data, b[x].size, FQG_MEM_HOST, b[x].final ? 1 : 0, &states[x],
-                                      FQG_VALIDATE_FRAME_ONLY, &r);
-          if (rc) {
-            lib_fail("fqg_validate", rc);
-            break;
-          }
-          if (r.code == FQG_E_LINE_TOO_LONG) {  // (the thread that takes the results starts the program over: refuse_long_line)
-            u.long_line_file = x;
-            u.long_line_record = u.seq * B + r.record;
-            u.rc = FQG_ERR_ARG;
-            break;
-          }
-          // a header line that starts with a NUL byte is "no entry" for the reference (src/fastq.c:250): this input ends
-          // HERE, cleanly, whatever follows - the unit is the last one the consumer looks at
-          const bool ends_here = r.stopped != 0;
-          // ... and another line of a record that starts with NUL is an empty string: the file is truncated there
-          // (src/fastq.c:254; tail_lines > 0) - the last unit as well
-          const bool cut_short = !ends_here && r.code == FQG_E_TRUNCATED && !b[x].final;
-          if (cut_short) u.ends = true;
-          if (ends_here) {
-            // frame the records in front of it once more, alone: what follows the NUL is not this file's any more
-            u.ends = true;
-            const int rc2 = fqg_validate(c, nullptr, b[x].data, r.consumed, FQG_MEM_HOST, 1, &states[x], FQG_VALIDATE_FRAME_ONLY, &r);
-            if (rc2) {
-              lib_fail("fqg_validate", rc2);
+          if (cut[x] && u.b[x].final) last = true;
+        return true;
+      },
+      [&](size_t di, Unit& u) {
+        fqg_ctx* c = ctx[di];
+        Block* const b = u.b;
+        const double t1 = timing ? now() : 0;
+        const fqg_frame* frames[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        fqg_frame* held[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        fqg_file_state states[6];
+        memcpy(states, st0, sizeof(states));
+        uint64_t first[6] = {0, 0, 0, 0, 0, 0};
+        auto lib_fail = [&](const char* what, int rc) {
+          u.rc = rc;
+          u.err = std::string(what) + ": " + fqg_last_error(c);
+        };
+        u.n = ~0ull;
+        for (int x = READ1; x <= INDEX3 && !u.rc; ++x)
+          if (cut[x]) {
+            fqg_validate_result r;
+            const int rc = fqg_validate(c, nullptr, b[x].data, b[x].size, FQG_MEM_HOST, b[x].final ? 1 : 0, &states[x],
+                                        FQG_VALIDATE_FRAME_ONLY, &r);
+            if (rc) {
+              lib_fail("fqg_validate", rc);
               break;
             }
-          }
-          if (!b[x].final && !ends_here && !cut_short && (r.n_records != B || r.consumed != b[x].size)) {
-            u.rc = FQG_ERR_STATE;
-            u.err = std::string("a block of ") + A.file[x] + " cut at a record boundary was not consumed whole";
-            break;
-          }
-          u.records[x] = r.n_records;
-          u.tail_lines[x] = ends_here ? 0 : r.tail_lines;
-          u.final[x] = b[x].final || ends_here || cut_short;
-          u.open_end[x] = b[x].final && !ends_here && r.tail_lines == 0 && r.n_records > 0 && b[x].size > 0 && b[x].data[b[x].size - 1] != '\n';
-          u.n = std::min<uint64_t>(u.n, r.n_records);
-          if (r.n_records) {
-            const int rc2 = fqg_frame_retain(c, &held[x]);
-            if (rc2) {
-              lib_fail("fqg_frame_retain", rc2);
+            if (r.code == FQG_E_LINE_TOO_LONG) {  // (the thread that takes the results starts the program over: refuse_long_line)
+              u.long_line_file = x;
+              u.long_line_record = u.seq * B + r.record;
+              u.rc = FQG_ERR_ARG;
               break;
             }
-            frames[x] = held[x];
-          }
-        }
-      const double t2 = timing ? now() : 0;
-      t_frame += t2 - t1;
-      double t3 = t2;
-      if (!u.rc && u.n > 0) {
-        fqg_barcode_params Pb = *A.P;
-        const int rc = fqg_barcodes_transform(c, frames, states, first, &Pb, u.n, u.seq * B, &u.r);
-        if (rc) lib_fail("fqg_barcodes_transform", rc);
-        t3 = timing ? now() : 0;
-        t_transform += t3 - t2;
-        for (int which = 0; which < 3 && !u.rc; ++which)
-          if (u.r.out_bytes[which]) {
-            u.out[which] = out_pool.take(u.r.out_bytes[which], &u.out_cap[which]);
-            if (!u.out[which]) {
-              u.rc = FQG_ERR_NOMEM;
-              u.err = "no pinned memory for the output text";
+            // a header line that starts with a NUL byte is "no entry" for the reference (src/fastq.c:250): this input ends
+            // HERE, cleanly, whatever follows - the unit is the last one the consumer looks at
+            const bool ends_here = r.stopped != 0;
+            // ... and another line of a record that starts with NUL is an empty string: the file is truncated there
+            // (src/fastq.c:254; tail_lines > 0) - the last unit as well
+            const bool cut_short = !ends_here && r.code == FQG_E_TRUNCATED && !b[x].final;
+            if (cut_short) u.ends = true;
+            if (ends_here) {
+              // frame the records in front of it once more, alone: what follows the NUL is not this file's any more
+              u.ends = true;
+              const int rc2 = fqg_validate(c, nullptr, b[x].data, r.consumed, FQG_MEM_HOST, 1, &states[x], FQG_VALIDATE_FRAME_ONLY, &r);
+              if (rc2) {
+                lib_fail("fqg_validate", rc2);
+                break;
+              }
+            }
+            if (!b[x].final && !ends_here && !cut_short && (r.n_records != B || r.consumed != b[x].size)) {
+              u.rc = FQG_ERR_STATE;
+              u.err = std::string("a block of ") + A.file[x] + " cut at a record boundary was not consumed whole";
               break;
             }
-            const int rc2 = fqg_barcodes_output(c, which, u.out[which], u.r.out_bytes[which]);
-            if (rc2) lib_fail("fqg_barcodes_output", rc2);
+            u.records[x] = r.n_records;
+            u.tail_lines[x] = ends_here ? 0 : r.tail_lines;
+            u.final[x] = b[x].final || ends_here || cut_short;
+            u.open_end[x] = b[x].final && !ends_here && r.tail_lines == 0 && r.n_records > 0 && b[x].size > 0 && b[x].data[b[x].size - 1] != '\n';
+            u.n = std::min<uint64_t>(u.n, r.n_records);
+            if (r.n_records) {
+              const int rc2 = fqg_frame_retain(c, &held[x]);
+              if (rc2) {
+                lib_fail("fqg_frame_retain", rc2);
+                break;
+              }
+              frames[x] = held[x];
+            }
           }
-        if (!u.rc && u.r.code == FQG_E_WRONG_HEADER) {
-          const Block& bb = b[u.r.file];
-          const char *p = bb.data, *end = bb.data + bb.size;
-          for (uint64_t line = 0; p < end && line < 4 * u.r.n_done; ++line) {
-            const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
-            p = nl ? nl + 1 : end;
+        const double t2 = timing ? now() : 0;
+        T[di].frame += t2 - t1;
+        double t3 = t2;
+        if (!u.rc && u.n > 0) {
+          fqg_barcode_params Pb = *A.P;
+          const int rc = fqg_barcodes_transform(c, frames, states, first, &Pb, u.n, u.seq * B, &u.r);
+          if (rc) lib_fail("fqg_barcodes_transform", rc);
+          t3 = timing ? now() : 0;
+          T[di].transform += t3 - t2;
+          for (int which = 0; which < 3 && !u.rc; ++which)
+            if (u.r.out_bytes[which]) {
+              u.out[which] = out_pool.take(u.r.out_bytes[which], &u.out_cap[which]);
+              if (!u.out[which]) {
+                u.rc = FQG_ERR_NOMEM;
+                u.err = "no pinned memory for the output text";
+                break;
+              }
+              const int rc2 = fqg_barcodes_output(c, which, u.out[which], u.r.out_bytes[which]);
+              if (rc2) lib_fail("fqg_barcodes_output", rc2);
+            }
+          if (!u.rc && u.r.code == FQG_E_WRONG_HEADER) {
+            const Block& bb = b[u.r.file];
+            const char *p = bb.data, *end = bb.data + bb.size;
+            for (uint64_t line = 0; p < end && line < 4 * u.r.n_done; ++line) {
+              const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+              p = nl ? nl + 1 : end;
+            }
+            const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
+            u.wrong_header.assign(p, nl ? nl + 1 : end);
           }
-          const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-          u.wrong_header.assign(p, nl ? nl + 1 : end);
-        }
-      } else if (!u.rc) u.n = 0;
-      const double t4 = timing ? now() : 0;
-      t_out += t4 - t3;
-      for (int x = READ1; x <= INDEX3; ++x)
-        if (cut[x]) {
-          if (held[x]) fqg_frame_release(held[x]);
-          cut[x]->release(b[x]);
-        }
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        const uint64_t seq = u.seq;
-        done.emplace(seq, std::move(u));
-        cv.notify_all();
-      }
-      if (timing) t_hand += now() - t4, ++n_units_done;
-    }
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 0; i < nd; ++i) th.emplace_back(work, i);
-  auto join_all = [&] {
-    stop = true;
-    out_pool.stop();
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      cv.notify_all();
-    }
-    for (int x = READ1; x <= INDEX3; ++x)
-      if (cut[x]) cut[x]->abort();
-    for (auto& t : th)
-      if (t.joinable()) t.join();
-  };
+        } else if (!u.rc) u.n = 0;
+        const double t4 = timing ? now() : 0;
+        T[di].out += t4 - t3;
+        for (int x = READ1; x <= INDEX3; ++x)
+          if (cut[x]) {
+            if (held[x]) fqg_frame_release(held[x]);
+            cut[x]->release(b[x]);
+          }
+      },
+      [&] {  // (a context may be waiting for an output buffer or for blocks, a cutter for a slot that stays held)
+        out_pool.stop();
+        for (int x = READ1; x <= INDEX3; ++x)
+          if (cut[x]) cut[x]->abort();
+      },
+      [&](size_t di, const UnitRun::Waits& w) {
+        if (timing) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu units; waiting for blocks %.3f s, copy + framing %.3f s, transform %.3f s, output D2H %.3f s, handing over %.3f s\n",
+                            di, (unsigned long long)w.items, w.fetch, T[di].frame, T[di].transform, T[di].out, w.hand_over);
+      });
 
   unsigned long processed = 0, discarded = 0;
   bool first_batch = true;
@@ -532,19 +481,14 @@ struct BlockRun {
   bool have_last = false;
   double t_main_wait = 0;
   const double t_loop = now();
-  for (uint64_t k = 0;; ++k) {
+  for (;;) {
     Unit u;
-    {
-      const double tw = timing ? now() : 0;
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return done.count(k) || k >= n_units; });
-      if (timing) t_main_wait += now() - tw;
-      if (!done.count(k)) break;
-      u = std::move(done[k]);
-      done.erase(k);
-    }
+    const double tw = timing ? now() : 0;
+    const bool more = run.next(u);
+    if (timing) t_main_wait += now() - tw;
+    if (!more) break;
     if (u.rc) {
-      join_all();
+      run.stop();
       if (u.long_line_file) refuse_long_line(A.file[u.long_line_file], u.long_line_record);
       FQ_PRINT_ERROR("GPU library failure in %s (%d)", u.err.c_str(), u.rc);
       fqhost::leave(kExitSys);
@@ -565,7 +509,7 @@ struct BlockRun {
       if (r.out_bytes[0]) fwrite(u.out[0], 1, r.out_bytes[0], stdout);
       for (int which = 1; which < 3; ++which)
         if (r.out_bytes[which] && !A.outgz[which].write(u.out[which], r.out_bytes[which])) {
-          join_all();
+          run.stop();
           FQ_PRINT_ERROR("%s.\n", A.outgz[which].error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
           fqhost::leave(kExitSys);
         }
@@ -577,7 +521,7 @@ struct BlockRun {
         fflush(stderr);
       }
       if (r.code != FQG_OK) {
-        join_all();
+        run.stop();
         if (r.code == FQG_E_WRONG_HEADER) {  // src/fastq.c:448-451, with the file's own line counter
           const uint64_t reads_of_file = u.seq * B + r.n_done + 1;
           FQ_PRINT_ERROR("Error in file %s: line %lu: wrong header %s", A.file[r.file], (unsigned long)(4 * reads_of_file),
@@ -592,17 +536,13 @@ struct BlockRun {
       out_pool.give(u.out[which], u.out_cap[which]);
       u.out[which] = nullptr;
     }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      ++n_written;
-      cv.notify_all();
-    }
+    run.done();
     const bool ends = u.ends;
     last = std::move(u);
     have_last = true;
     if (ends) break;  // (later units, if any were handed out, are dropped)
   }
-  join_all();
+  run.stop();
   if (timing) fprintf(fqhost::diag(), "fqgpu timing: the thread that writes: %.3f s in the loop, %.3f s of them waiting for the next unit\n", now() - t_loop, t_main_wait);
   // an incomplete record where the next read would have happened is a truncated file (src/fastq.c:254-257); a clean
   // end of any input just ends the loop.  The first input, in file order, that has nothing left decides - unless the

@@ -3,6 +3,7 @@
 // src/fastq_pre_barcodes.c:594-727: iteration k uses record k of every input): when every input is cut at the same
 // record numbers, block j of all inputs is a unit of work with no order among the units, and whichever device is free
 // takes the next one ("shards naturally" by record block).
+// (How the units go to the devices' threads and their results come back in unit order: fq_ordered.h.)
 //
 // A record is four lines, so the cut behind record R is the byte behind the 4R-th newline.  The reader threads count
 // the newlines of what they read while the bytes are in their cache (as host/fq_multi.h does); the cut is then

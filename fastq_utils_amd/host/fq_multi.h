@@ -8,6 +8,7 @@
 // among them: whichever device is free takes the next one.  What the serial loop would report - the first finding
 // in file order, the progress ticker, the statistics of a clean file - is put together on the host: findings by
 // piece order, statistics by fqg_acc_export / fqg_acc_merge.  No collective is needed on this path.
+// (How the pieces go to the devices' threads and their results come back in piece order: fq_ordered.h.)
 #pragma once
 #include <functional>
 
@@ -160,6 +161,19 @@ inline std::vector<int> devices_from_env() {
     p = *end == ',' ? end + 1 : end;
   }
   return d;
+}
+
+// the contexts of a run over `devs`: `first` (open already, on devs[0]) and one more for every further entry
+inline std::vector<fqg_ctx*> open_more_contexts(fqg_ctx* first, const std::vector<int>& devs) {
+  std::vector<fqg_ctx*> ctx(devs.size(), first);
+  for (size_t i = 1; i < devs.size(); ++i) {
+    const int rc = fqg_open(devs[i], &ctx[i]);
+    if (rc != 0) {
+      FQ_PRINT_ERROR("FQGPU_DEVICES: device %d is not a usable MI355X GPU (fqg_open: %d)", devs[i], rc);
+      leave(kExitSys);
+    }
+  }
+  return ctx;
 }
 
 }  // namespace fqhost

@@ -1,7 +1,7 @@
 """ASan / UBSan (and TSan for the reader thread) builds of the CPU-side C / C++ of this repository (SURVEY section 5,
 sanitizer row): the oracle restatements (oracle/fq_oracle.c, rl_oracle.c), the container code of libfastq_gpu.so that
 needs no GPU (compat/range_list_compat.cpp), the host-side (de)compression (host/fq_parallel.h) and the host stager
-(host/fq_source.h, fq_input.h, fq_multi.h, fq_blocks.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
+(host/fq_source.h, fq_input.h, fq_multi.h, fq_blocks.h, fq_ordered.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
 import gzip
 import os
 import subprocess
@@ -317,3 +317,15 @@ def test_cutters_fail_when_pinned_memory_runs_out(tmpdir, san):
                 assert p.returncode == 2 and b"unable to allocate pinned memory" in p.stderr, (name, which, k, p.returncode, p.stdout, p.stderr.decode()[-1500:])
             p = subprocess.run([exe, str(tmpdir / name), which, size, "1000000"], env=env, capture_output=True, timeout=300)
             assert p.returncode == 0 and p.stdout.startswith(b"no failure (%d lines)" % data.count(b"\n")), (name, which, p.stdout, p.stderr.decode()[-1500:])
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_ordered_worker_pool_runs_clean(tmpdir, san):
+    """fq_ordered.h (the hand-over under the loops over several contexts): results come back in fetch order, each once,
+    with and without a window; a consumer that stops early - workers waiting inside fetch or for the window - gets
+    stop() back with every thread joined; a source that brings nothing ends the consumer.  Every case ends by itself."""
+    flags = ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g", "-O1"]
+    exe = str(tmpdir / ("ordered_" + san.split(",")[0]))
+    subprocess.run(["g++", "-std=c++17", "-pthread", "-Wall", "-Wextra"] + flags + ["-o", exe, os.path.join(CXX, "ordered_run_check.cpp")], check=True)
+    p = subprocess.run([exe], env=dict(ENV, TSAN_OPTIONS="halt_on_error=1"), capture_output=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.startswith(b"ok 48"), (p.stdout, p.stderr.decode()[-1500:])
