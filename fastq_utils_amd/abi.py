@@ -41,6 +41,7 @@ EXPORTS = [
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
+    "fqg_bam2fastq", "fqg_bam2fastq_output",
     "fqg_umi_count", "fqg_umi_features", "fqg_umi_record_features", "fqg_umi_replayed_features", "fqg_umi_umis",
     "fqg_umi_cells", "fqg_umi_entries", "fqg_umi_emit",
     "fqg_fp_owner", "fqg_names_fingerprints", "fqg_names_fingerprints_acct", "fqg_names_fingerprints_named", "fqg_frame_name_records", "fqg_frame_names_equal", "fqg_device_alloc", "fqg_device_free",
@@ -114,6 +115,19 @@ class BamTagsParams(C.Structure):
 class BamTagsResult(C.Structure):
     _fields_ = [("n_alignments", C.c_uint64), ("n_tagged", C.c_uint64), ("out_bytes", C.c_uint64), ("record", C.c_uint64),
                 ("code", C.c_int32), ("reserved", C.c_int32)]
+
+
+class B2fParams(C.Structure):
+    _fields_ = [("tenx", C.c_int32), ("reserved", C.c_int32), ("first_alignment", C.c_uint64)]
+
+
+class B2fResult(C.Structure):
+    _fields_ = [("n_alignments", C.c_uint64), ("out_bytes", C.c_uint64 * 6), ("first_record", C.c_uint64 * 6),
+                ("warn_record", C.c_uint64), ("record", C.c_uint64), ("entry", C.c_uint64), ("aux", C.c_uint64),
+                ("code", C.c_int32), ("reserved", C.c_int32)]
+
+
+B2F_UNUSED = 0xFFFFFFFFFFFFFFFF
 
 
 class UmiResult(C.Structure):
@@ -290,6 +304,8 @@ def load():
     L.fqg_umi_count.argtypes = [vp, vp, u64, C.c_int, C.POINTER(u64), u64, C.POINTER(UmiParams), C.POINTER(UmiResult)]
     L.fqg_bam_add_tags.argtypes = [vp, vp, u64, C.c_int, C.POINTER(u64), u64, C.POINTER(BamTagsParams), C.POINTER(BamTagsResult)]
     L.fqg_bam_add_tags_output.argtypes = [vp, vp, u64]
+    L.fqg_bam2fastq.argtypes = [vp, vp, u64, C.c_int, C.POINTER(u64), u64, C.POINTER(B2fParams), C.POINTER(B2fResult)]
+    L.fqg_bam2fastq_output.argtypes = [vp, C.c_int, vp, u64]
     L.fqg_umi_emit.argtypes = [vp, C.POINTER(C.c_uint32), u64, C.c_uint32, C.POINTER(UmiResult)]
     L.fqg_umi_features.argtypes = [vp, vp, u64]
     L.fqg_umi_cells.argtypes = [vp, C.POINTER(u64), u64]
@@ -927,6 +943,40 @@ class Context:
             dst = C.create_string_buffer(max(1, r.out_bytes))
             self._check(L.fqg_bam_add_tags_output(self.h, dst, r.out_bytes))
             out["records"] = dst.raw[:r.out_bytes]
+        return out
+
+    def bam2fastq(self, stream, tenx=False, offsets=None, nbytes=None, first_alignment=0):
+        """bam2fastq's alignment loop (src/bam2fastq.c:249-355) on an inflated BAM stream: bytes (host) or an int device
+        pointer (then `nbytes` and `offsets` are required).  Returns the result fields (out_bytes and first_record as
+        lists of six) and `streams`: the six output byte strings (FILE_LOC order; three used with tenx).  With a
+        finding (code != 0) all of it describes the alignments in front of `record`."""
+        L = load()
+        host = isinstance(stream, (bytes, bytearray))
+        if host:
+            buf = (C.c_char * max(1, len(stream))).from_buffer_copy(stream)
+            nbytes = len(stream)
+        if offsets is None:
+            n, used = C.c_uint64(), C.c_uint64()
+            self._check(L.fqg_bam_index_records(buf, nbytes, None, 0, C.byref(n), C.byref(used)))
+            offs = (C.c_uint64 * max(1, n.value))()
+            self._check(L.fqg_bam_index_records(buf, nbytes, offs, n.value, C.byref(n), C.byref(used)))
+            n_rec = n.value
+        else:
+            n_rec = len(offsets)
+            offs = offsets if isinstance(offsets, C.Array) else (C.c_uint64 * max(1, n_rec))(*offsets)
+        p = B2fParams()
+        p.tenx, p.first_alignment = int(tenx), first_alignment
+        r = B2fResult()
+        self._check(L.fqg_bam2fastq(self.h, buf if host else C.c_void_p(int(stream)), nbytes, MEM_HOST if host else MEM_DEVICE,
+                                    offs, n_rec, C.byref(p), C.byref(r)))
+        out = {k: getattr(r, k) for k in ("n_alignments", "warn_record", "record", "entry", "aux", "code")}
+        out["out_bytes"], out["first_record"] = list(r.out_bytes), list(r.first_record)
+        out["streams"] = []
+        for s in range(6):
+            dst = C.create_string_buffer(max(1, r.out_bytes[s]))
+            if r.out_bytes[s]:
+                self._check(L.fqg_bam2fastq_output(self.h, s, dst, r.out_bytes[s]))
+            out["streams"].append(dst.raw[:r.out_bytes[s]])
         return out
 
     @staticmethod

@@ -28,6 +28,7 @@
 #include "fqg_umi_rl_kernels.hip"
 #include "fqg_umi_cell_kernels.hip"
 #include "fqg_bamtags_kernels.hip"
+#include "fqg_bam2fastq_kernels.hip"
 
 using namespace fqg;
 
@@ -152,6 +153,8 @@ struct fqg_ctx {
   uint64_t bc_out_bytes[3] = {0, 0, 0};
   DevBuf bt_in, bt_off, bt_tables, bt_rec, bt_size, bt_local, bt_sums, bt_call, bt_out;  // fqg_bam_add_tags
   uint64_t bt_out_bytes = 0;
+  DevBuf b2f_in, b2f_off, b2f_size, b2f_local, b2f_sums, b2f_call, b2f_out;  // fqg_bam2fastq
+  uint64_t b2f_out_at[6] = {0, 0, 0, 0, 0, 0}, b2f_out_bytes[6] = {0, 0, 0, 0, 0, 0};
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
 
@@ -408,7 +411,7 @@ void fqg_close(fqg_ctx* c) {
   release(c->bc_status);
   release(c->bc_tile_big);
   for (DevBuf* b : {&c->bt_in, &c->bt_off, &c->bt_tables, &c->bt_rec, &c->bt_size, &c->bt_local, &c->bt_sums, &c->bt_call,
-                    &c->bt_out})
+                    &c->bt_out, &c->b2f_in, &c->b2f_off, &c->b2f_size, &c->b2f_local, &c->b2f_sums, &c->b2f_call, &c->b2f_out})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
@@ -2787,5 +2790,6 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 #include "fqg_umi_abi.inc"
 #include "fqg_fp_abi.inc"
 #include "fqg_bamtags_abi.inc"
+#include "fqg_bam2fastq_abi.inc"
 
 }  // extern "C"

@@ -602,6 +602,37 @@ int fqg_bam_add_tags(fqg_ctx *ctx, const void *stream, uint64_t nbytes, int mem,
                      uint64_t n_records, const fqg_bam_tags_params *params, fqg_bam_tags_result *out);
 int fqg_bam_add_tags_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
 
+/* ---- bam2fastq --------------------------------------------------------------------------------------
+ * Replaces the alignment loop of bam2fastq (src/bam2fastq.c:249-355): every alignment becomes FASTQ records in up to
+ * six output streams, numbered as the reference's FILE_LOC (:41): 0 _1, 1 _2, 2 _cell, 3 _sample, 4 _umi, 5 the
+ * single-end file; with tenx (-X / --10xV2 / --10xV3) 0 _R1, 1 _R2, 2 _I1.  Input as for fqg_bam_add_tags: the
+ * inflated BAM stream and the offset of every alignment (fqg_bam_index_records).  The streams stay on the device until
+ * fqg_bam2fastq_output copies them.
+ * A finding (code != 0) ends the conversion at alignment `record`, as the reference's exit does: every other field of
+ * the result, and the streams, then describe the alignments BEFORE it.  Within one alignment the reference writes in
+ * the order 0|1|5, 2, 4, 3 (tenx: 0, 2, 1); FQG_E_B2F_SAMPLE_QUAL is found after stream 0 was written (opened). */
+#define FQG_B2F_STREAMS 6
+#define FQG_B2F_UNUSED 0xFFFFFFFFFFFFFFFFull
+typedef struct {
+  int32_t tenx;
+  int32_t reserved;
+  uint64_t first_alignment; /* alignments in front of this piece (messages count from 1 over the whole file) */
+} fqg_b2f_params;
+typedef struct {
+  uint64_t n_alignments;                  /* counted (secondary ones too); with a finding: the ones before it */
+  uint64_t out_bytes[FQG_B2F_STREAMS];
+  uint64_t first_record[FQG_B2F_STREAMS]; /* first alignment (index in this call) that wrote to the stream, or FQG_B2F_UNUSED */
+  uint64_t warn_record;                   /* first alignment without `on`: "Warning: bam file was not generated with fastq2bam." */
+  uint64_t record;                        /* the alignment with the finding (index in this call) */
+  uint64_t entry;                         /* first_alignment + record + 1: the number the messages print */
+  uint64_t aux;                           /* FQG_E_B2F_SAMPLE_QUAL: offset of the sample barcode (a C string) in the stream */
+  int32_t code;                           /* FQG_OK or one of FQG_E_B2F_* */
+  int32_t reserved;
+} fqg_b2f_result;
+int fqg_bam2fastq(fqg_ctx *ctx, const void *stream, uint64_t nbytes, int mem, const uint64_t *offsets,
+                  uint64_t n_records, const fqg_b2f_params *params, fqg_b2f_result *out);
+int fqg_bam2fastq_output(fqg_ctx *ctx, int stream_id, void *host_dst, uint64_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif

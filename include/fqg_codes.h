@@ -65,7 +65,23 @@ enum fqg_code {
    * characters or longer, makes the reference read / write memory it does not own.  Refused. */
   FQG_E_TAGS_NAME = 22,
   /* :275-277  header->target_name[tid] with tid beyond the header's references (--tx).  Refused. */
-  FQG_E_TAGS_TID = 23
+  FQG_E_TAGS_TID = 23,
+  /* bam2fastq with -X / --10xV2 / --10xV3, src/bam2fastq.c:303-306, :316-317  "missing cell tag / cell quality tag /
+   * umi tag / umi quality tag in entry N", "missing sample quality tag in entry N for sample S": exit 3 */
+  FQG_E_B2F_CELL = 24,
+  FQG_E_B2F_CELL_QUAL = 25,
+  FQG_E_B2F_UMI = 26,
+  FQG_E_B2F_UMI_QUAL = 27,
+  FQG_E_B2F_SAMPLE_QUAL = 28,
+  /* :269-271  an alignment without the `on` tag under a 10x option: "Unable to continue - bam file was not generated
+   * by fastq2bam", exit 1 */
+  FQG_E_B2F_NOT_FASTQ2BAM = 29,
+  /* Not reference outcomes.  :242-243, :145-162  a read of 10 000 bases or more overruns the reference's stack
+   * buffers.  Refused. */
+  FQG_E_B2F_TOO_LONG = 30,
+  /* bam_aux_get / bam_aux2Z / bam1_qname read on behind the record when a field, a Z value without NUL or the read
+   * name does not end inside it.  Refused. */
+  FQG_E_B2F_AUX = 31
 };
 
 /* read-name formats, src/fastq.h:25-28 (INTEGERNAME and NOP share the value 2) */

@@ -686,6 +686,96 @@ def gen_bam_tags():
     print("bam_add_tags invocations:", len(out), "by exit status:", by)
 
 
+# ---- bam2fastq (run_tests.sh:43-92) --------------------------------------------------------------------------------
+B2F_DATA = os.path.join(GOLD, "data_b2f")
+B2F_REF_FIXTURES = ("se", "pe", "test", "test10", "test10e1", "test10e3", "test10e4", "test10e5", "test10e6", "no_qual")
+LIBBAM_SRC = ("bgzf.c kstring.c bam_aux.c bam.c bam_import.c sam.c bam_index.c bam_pileup.c bam_lpileup.c bam_md.c razf.c "
+              "faidx.c bedidx.c knetfile.c bam_sort.c sam_header.c bam_reheader.c kprobaln.c bam_cat.c").split()
+
+
+def build_ref_bam2fastq(tmp):
+    """the reference's bam2fastq, compiled as oracle/Makefile compiles bam_add_tags, into `tmp` (outside the repository)"""
+    subprocess.run(["tar", "-xjf", os.path.join(REF, "deps", "samtools-0.1.19.tar.bz2"), "-C", tmp], check=True)
+    sam = os.path.join(tmp, "samtools-0.1.19")
+    subprocess.run(["gcc", "-O2", "-w", "-c", "-D_FILE_OFFSET_BITS=64", "-D_LARGEFILE64_SOURCE", "-D_USE_KNETFILE", "-I."] + LIBBAM_SRC,
+                   cwd=sam, check=True)
+    exe = os.path.join(tmp, "bam2fastq")
+    src = os.path.join(REF, "src")
+    subprocess.run(["gcc", "-O3", "-w", "-I" + src, "-I" + sam, "-o", exe, os.path.join(src, "bam2fastq.c"), os.path.join(src, "fastq.c"),
+                    os.path.join(src, "hash.c")] + glob.glob(os.path.join(sam, "*.o")) + ["-lz", "-lm", "-lpthread"], check=True)
+    return exe
+
+
+def bam2fastq_jobs():
+    """(args, stdin file or None); OUT stands for the output prefix"""
+    b = lambda n: "data_b2f/" + n + ".bam"
+    jobs = [([], None), (["-i"], None), (["-o"], None), (["--10x"], None), (["--bam", b("no_qual")], None)]   # run_tests.sh:45-49
+    jobs += [(["--bam", b("test10e%d" % k), "--10xV2"], None) for k in (1, 3, 4, 5, 6)]                     # :50-54
+    jobs += [(["--bam", b("missing_no_qual"), "--out", "OUT"], None), (["-h"], None)]                       # :55, :59
+    jobs += [(["--bam", b("test"), "--out", "OUT", "-X"], None)]                                             # :66
+    # :56-84 otherwise run a fixture with no option, -X, --10xV2 or --10xV3: all of them, on every fixture
+    fixtures = [b(n) for n in B2F_REF_FIXTURES] + ["data_b2f/" + n for n in sorted(b2f_synthetic())]
+    fixtures += ["data_umi/test_annot.bam", "data_umi/test_one_cell.bam", "data_tags/trans_small.bam", "data_tags/syn_tags.bam"]
+    fixtures += ["data_umi/" + n for n in sorted(os.listdir(os.path.join(GOLD, "data_umi"))) if n.startswith("syn_") and n.endswith(".bam")]
+    for f in fixtures:
+        for mode in ([], ["-X"], ["--10xV2"], ["--10xV3"]):
+            jobs.append((["--bam", f, "--out", "OUT"] + mode, None))
+    # the option table: abbreviations, = forms, options behind the operands, unknown options (ignored), --help, stdin
+    jobs += [(["--ba", b("se"), "--ou=OUT"], None), (["-b" + b("pe"), "-oOUT", "--verbose"], None),
+             (["stray", "--out", "OUT", "--bam", b("test10"), "--10xV"], None), (["--bam", b("se"), "--out", "OUT", "--nonsense", "-q"], None),
+             (["--help", "--bam", b("se"), "--out", "OUT"], None), (["--bam"], None), (["--bam", b("se"), "--out"], None),
+             (["--bam", b("se")], None), (["--out", "OUT"], None), (["--bam", "-", "--out", "OUT"], b("pe")),
+             (["--bam", "-", "--out", "OUT", "--10xV3"], b("test10")), (["--bam", b("se"), "--out", "no/such/folder/x"], None)]
+    return jobs
+
+
+def b2f_synthetic():
+    sys.path.insert(0, REPO)
+    from tests import b2f_gen
+    return b2f_gen.golden_bams()
+
+
+def gen_bam2fastq():
+    import hashlib
+    import tempfile
+
+    sys.path.insert(0, REPO)
+    from tests import bamgen
+    os.makedirs(B2F_DATA, exist_ok=True)
+    for n in B2F_REF_FIXTURES:   # the reference's own small fixtures for this program
+        shutil.copyfile(os.path.join(REF, "tests", n + ".bam"), os.path.join(B2F_DATA, n + ".bam"))
+        os.chmod(os.path.join(B2F_DATA, n + ".bam"), 0o644)
+    for n, raw in b2f_synthetic().items():
+        with open(os.path.join(B2F_DATA, n), "wb") as f:
+            f.write(bamgen.bgzf(raw, level=9))
+    out = []
+    with tempfile.TemporaryDirectory() as build:
+        exe = build_ref_bam2fastq(build)
+        for args, stdin in bam2fastq_jobs():
+            with tempfile.TemporaryDirectory(dir=GOLD) as tmp:
+                rel = os.path.relpath(tmp, GOLD)
+                real = [a.replace("OUT", rel + "/o") if a.endswith("OUT") else a for a in args]
+                p = subprocess.run(["bam2fastq"] + real, executable=exe, cwd=GOLD, capture_output=True, timeout=600,
+                                   stdin=open(os.path.join(GOLD, stdin), "rb") if stdin else subprocess.DEVNULL)
+                entry = {"args": args, "stdin": stdin, "exit": p.returncode, "stdout": p.stdout.decode("latin-1"),
+                         "stderr": p.stderr.decode("latin-1").replace(rel + "/", "SCRATCH/"), "files": {}}
+                for n in sorted(os.listdir(tmp)):
+                    if p.returncode != 0:   # (never closed: what they hold is not defined)
+                        entry["files"][n] = None
+                        continue
+                    data = gzip.decompress(open(os.path.join(tmp, n), "rb").read())
+                    entry["files"][n] = {"bytes": len(data), "sha256": hashlib.sha256(data).hexdigest()}
+                    if len(data) < 4096:
+                        entry["files"][n]["content"] = data.decode("latin-1")
+                out.append(entry)
+    with open(os.path.join(GOLD, "bam2fastq.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    by = {}
+    for o in out:
+        by[o["exit"]] = by.get(o["exit"], 0) + 1
+    print("bam2fastq invocations:", len(out), "by exit status:", by)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("all", "fastq_info"):
@@ -700,3 +790,5 @@ if __name__ == "__main__":
         gen_filters()
     if which in ("all", "bam_tags"):
         gen_bam_tags()
+    if which in ("all", "bam2fastq"):
+        gen_bam2fastq()
