@@ -820,18 +820,8 @@ class Context:
         if offsets_device is not None:  # (device pointer, number of records): the index lies in HBM beside the records
             assert not host
             offs, n_rec = C.cast(C.c_void_p(int(offsets_device[0])), C.POINTER(C.c_uint64)), int(offsets_device[1])
-        elif offsets is None:
-            n, used = C.c_uint64(), C.c_uint64()
-            self._check(L.fqg_bam_index_records(buf, nbytes, None, 0, C.byref(n), C.byref(used)))
-            offs = (C.c_uint64 * max(1, n.value))()
-            self._check(L.fqg_bam_index_records(buf, nbytes, offs, n.value, C.byref(n), C.byref(used)))
-            n_rec = n.value
         else:
-            n_rec = len(offsets)
-            if hasattr(offsets, "c"):       # a wrapper that already holds a ctypes array (bench.py)
-                offs = offsets.c
-            else:
-                offs = offsets if isinstance(offsets, C.Array) else (C.c_uint64 * max(1, n_rec))(*offsets)
+            offs, n_rec, _ = _bam_offsets(buf if host else None, nbytes, offsets)
         p = UmiParams()
         p.feat_tag, p.cell_tag, p.umi_tag = feat_tag[:2], cell_tag[:2], umi_tag[:2]
         p.sorted_by_cell, p.uniq_mapped_only = int(sorted_by_cell), int(uniq_mapped_only)
@@ -910,15 +900,7 @@ class Context:
         if host:
             buf = (C.c_char * max(1, len(stream))).from_buffer_copy(stream)
             nbytes = len(stream)
-        if offsets is None:
-            n, used = C.c_uint64(), C.c_uint64()
-            self._check(L.fqg_bam_index_records(buf, nbytes, None, 0, C.byref(n), C.byref(used)))
-            offs = (C.c_uint64 * max(1, n.value))()
-            self._check(L.fqg_bam_index_records(buf, nbytes, offs, n.value, C.byref(n), C.byref(used)))
-            n_rec = n.value
-        else:
-            n_rec = len(offsets)
-            offs = offsets.c if hasattr(offsets, "c") else (offsets if isinstance(offsets, C.Array) else (C.c_uint64 * max(1, n_rec))(*offsets))
+        offs, n_rec, _ = _bam_offsets(buf if host else None, nbytes, offsets)
         nt = len(targets)
         blob, tx_off, tx_len, gx_off, gx_len = bytearray(), [], [], [], []
         for t in targets:
@@ -955,15 +937,7 @@ class Context:
         if host:
             buf = (C.c_char * max(1, len(stream))).from_buffer_copy(stream)
             nbytes = len(stream)
-        if offsets is None:
-            n, used = C.c_uint64(), C.c_uint64()
-            self._check(L.fqg_bam_index_records(buf, nbytes, None, 0, C.byref(n), C.byref(used)))
-            offs = (C.c_uint64 * max(1, n.value))()
-            self._check(L.fqg_bam_index_records(buf, nbytes, offs, n.value, C.byref(n), C.byref(used)))
-            n_rec = n.value
-        else:
-            n_rec = len(offsets)
-            offs = offsets if isinstance(offsets, C.Array) else (C.c_uint64 * max(1, n_rec))(*offsets)
+        offs, n_rec, _ = _bam_offsets(buf if host else None, nbytes, offsets)
         p = B2fParams()
         p.tenx, p.first_alignment = int(tenx), first_alignment
         r = B2fResult()
@@ -1009,6 +983,25 @@ class Context:
     def synth_fastq(self, device_ptr, n_records, read_len=150, first_index=0, seed=12345, mate=1):
         self._check(load().fqg_synth_fastq(self.h, C.c_void_p(int(device_ptr)), n_records, read_len,
                                            first_index, seed, mate))
+
+
+def _bam_offsets(buf, nbytes, offsets=None):
+    """(ctypes array of the alignments' offsets - one entry at least -, how many, the end of the last complete record):
+    the caller's `offsets` - a sequence, a ctypes array or a wrapper that already holds one as `.c` (bench.py); the end
+    is None then - or, without them, those of the inflated BAM stream in the host buffer `buf`"""
+    if offsets is not None:
+        n_rec = len(offsets)
+        if hasattr(offsets, "c"):
+            return offsets.c, n_rec, None
+        return (offsets if isinstance(offsets, C.Array) else (C.c_uint64 * max(1, n_rec))(*offsets)), n_rec, None
+    L = load()
+    n, used = C.c_uint64(), C.c_uint64()
+    rc = L.fqg_bam_index_records(buf, nbytes, None, 0, C.byref(n), C.byref(used))
+    if rc != 0:
+        raise FqgError(f"libfqgpu error {rc}: fqg_bam_index_records: not a BAM stream")
+    offs = (C.c_uint64 * max(1, n.value))()
+    L.fqg_bam_index_records(buf, nbytes, offs, n.value, C.byref(n), C.byref(used))
+    return offs, n.value, used.value
 
 
 def synth_record_bytes(read_len=150):

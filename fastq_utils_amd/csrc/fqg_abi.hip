@@ -151,9 +151,10 @@ struct fqg_ctx {
   BcCall* d_bcall = nullptr;
   BcCall* h_bcall = nullptr;  // pinned
   uint64_t bc_out_bytes[3] = {0, 0, 0};
-  DevBuf bt_in, bt_off, bt_tables, bt_rec, bt_size, bt_local, bt_sums, bt_call, bt_out;  // fqg_bam_add_tags
+  DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
+  DevBuf bt_tables, bt_call, bt_out;  // fqg_bam_add_tags
   uint64_t bt_out_bytes = 0;
-  DevBuf b2f_in, b2f_off, b2f_size, b2f_local, b2f_sums, b2f_call, b2f_out;  // fqg_bam2fastq
+  DevBuf b2f_call, b2f_out;  // fqg_bam2fastq
   uint64_t b2f_out_at[6] = {0, 0, 0, 0, 0, 0}, b2f_out_bytes[6] = {0, 0, 0, 0, 0, 0};
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
@@ -188,6 +189,12 @@ int fail(fqg_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
   do {                                                                \
     hipError_t e__ = (call);                                          \
     if (e__ != hipSuccess) return fail((c), FQG_ERR_HIP, #call, e__); \
+  } while (0)
+
+#define NEED(rc_)        \
+  do {                   \
+    int r__ = (rc_);     \
+    if (r__) return r__; \
   } while (0)
 
 int ensure(fqg_ctx* c, DevBuf& b, size_t bytes) {
@@ -296,6 +303,46 @@ int grid_for_waves(fqg_ctx* c, uint64_t n_records) {
   uint64_t want = (n_records + (kBlock / kWave) - 1) / (kBlock / kWave);
   uint64_t cap = (uint64_t)c->cu_count * 8;
   return (int)std::max<uint64_t>(1, std::min(want, cap));
+}
+
+// ---- what fqg_bam_add_tags and fqg_bam2fastq (`name`) share --------------------------------------
+// The input side: the argument checks, then `begin()` (the call's own checks; its result and its last output
+// cleared), the offsets, and the stream on the device at a 16-byte boundary (the tiles are staged with 16-byte
+// loads) with its offsets in c->bam_off.  *d_buf: the stream there; nothing is copied for a call without records.
+template <class Begin>
+int bam_input(fqg_ctx* c, const char* name, bool have_args, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets,
+              uint64_t n_records, Begin begin, const uint8_t** d_buf) {
+  if (!c || !have_args || (n_records && (!stream || !offsets))) return FQG_ERR_ARG;
+  if (mem != FQG_MEM_HOST && mem != FQG_MEM_DEVICE) return FQG_ERR_ARG;
+  if (n_records >= 0x7FFFFFFFull) return fail(c, FQG_ERR_ARG, (std::string(name) + ": more than 2^31 alignments in one call").c_str());
+  NEED(begin());
+  HIP_TRY(c, hipSetDevice(c->device));
+  *d_buf = nullptr;
+  if (!n_records) return 0;
+  const uint32_t n = (uint32_t)n_records;
+  for (uint32_t k = 0; k < n; ++k)  // (a tile is the span from its first record to the end of its last)
+    if (offsets[k] + 36 > nbytes || (k && offsets[k] <= offsets[k - 1]))
+      return fail(c, FQG_ERR_ARG, (std::string(name) + ": offsets must ascend and lie inside the stream (fqg_bam_index_records)").c_str());
+  if (mem == FQG_MEM_HOST || ((uintptr_t)stream & 15u)) {
+    NEED(ensure(c, c->bam_in, nbytes + 64));
+    HIP_TRY(c, hipMemcpyAsync(c->bam_in.p, stream, nbytes, mem == FQG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    *d_buf = (const uint8_t*)c->bam_in.p;
+  } else *d_buf = (const uint8_t*)stream;
+  NEED(ensure(c, c->bam_off, (size_t)n * 8));
+  HIP_TRY(c, hipMemcpyAsync(c->bam_off.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// Records per tile and the two LDS areas: what the mean record needs (a tile that does not fit takes the slow path);
+// small areas let more wavefronts share a CU.  out_per_rec: the output bytes a record is expected to make, with its
+// margin (a guess: sizes are not known yet).  `env`: the variable that asks for smaller tiles (measurement).
+//   fqg_bam_add_tags  out_cap = (uint32_t)(1.15 * (mean_in + 64 + (tx_tag ? 40 : 0)) * T) + 256, in 16s, at most 28 KiB
+//   fqg_bam2fastq     out_cap = (uint32_t)(2.3 * mean_in * T) + 32 * streams + 256, in 16s, at most 36 KiB
+void bam_tile_shape(BamTiles& A, uint32_t in_lds, uint32_t out_lds, double mean_in, double out_per_rec, uint32_t pad, const char* env) {
+  A.T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)in_lds - 64.0) / (1.1 * mean_in + 1.0))));
+  if (const char* e = getenv(env)) A.T = (uint32_t)std::max(1, std::min<int>((int)A.T, atoi(e)));
+  A.in_cap = std::min<uint32_t>(in_lds, ((uint32_t)(1.15 * mean_in * A.T) + 256u + 15u) & ~15u);
+  A.out_cap = std::min<uint32_t>(out_lds, ((uint32_t)(out_per_rec * A.T) + pad + 256u + 15u) & ~15u);
 }
 
 }  // namespace
@@ -410,8 +457,8 @@ void fqg_close(fqg_ctx* c) {
   release(c->umi_entries[1]);
   release(c->bc_status);
   release(c->bc_tile_big);
-  for (DevBuf* b : {&c->bt_in, &c->bt_off, &c->bt_tables, &c->bt_rec, &c->bt_size, &c->bt_local, &c->bt_sums, &c->bt_call,
-                    &c->bt_out, &c->b2f_in, &c->b2f_off, &c->b2f_size, &c->b2f_local, &c->b2f_sums, &c->b2f_call, &c->b2f_out})
+  for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call, &c->bt_out,
+                    &c->b2f_call, &c->b2f_out})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);

@@ -1,11 +1,5 @@
 // fqg_bam2fastq_abi.inc - fqg_bam2fastq / fqg_bam2fastq_output (include/fqg.h), included by fqg_abi.hip
 
-#define B2F_NEED(rc_) \
-  do {                \
-    int r__ = (rc_);  \
-    if (r__) return r__; \
-  } while (0)
-
 extern "C++" {
 namespace {
 // the three launches over alignments [0, n) of a stream that is on the device already; with a finding nothing is emitted
@@ -16,25 +10,21 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   const uint64_t nb = ((uint64_t)n + kScan64Span - 1) / kScan64Span;
   const size_t size_stride = (((size_t)n * 4) + 255) & ~(size_t)255, local_stride = (((size_t)n * 8) + 255) & ~(size_t)255;
   const size_t sums_stride = (((size_t)nb * 8) + 64 + 255) & ~(size_t)255;
-  B2F_NEED(ensure(c, c->b2f_size, size_stride * ns));
-  B2F_NEED(ensure(c, c->b2f_local, local_stride * ns));
-  B2F_NEED(ensure(c, c->b2f_sums, sums_stride * ns));
-  B2F_NEED(ensure(c, c->b2f_call, sizeof(B2fCall) + 8 * kB2fStreams + 64));
+  NEED(ensure(c, c->bam_size, size_stride * ns));
+  NEED(ensure(c, c->bam_local, local_stride * ns));
+  NEED(ensure(c, c->bam_sums, sums_stride * ns));
+  NEED(ensure(c, c->b2f_call, sizeof(B2fCall) + 8 * kB2fStreams + 64));
   memset(h_call, 0xFF, sizeof(*h_call));
   B2fCall* d_call = (B2fCall*)c->b2f_call.p;
   unsigned long long* d_total = (unsigned long long*)((char*)c->b2f_call.p + sizeof(B2fCall));
   HIP_TRY(c, hipMemcpyAsync(d_call, h_call, sizeof(*h_call), hipMemcpyHostToDevice, st));
-  // records per tile and the two LDS areas: what the mean record needs (a tile that does not fit takes the slow
-  // path); the FASTQ text of a fastq2bam record is about twice its bytes (the names repeat in every stream)
+  // (the FASTQ text of a fastq2bam record is about twice its bytes: the names repeat in every stream)
   B2fTiles A;
   memset(&A, 0, sizeof(A));
-  A.T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)kB2fInCap - 64.0) / (1.1 * mean_in + 1.0))));
-  if (const char* e = getenv("FQGPU_B2F_T")) A.T = (uint32_t)std::max(1, std::min<int>((int)A.T, atoi(e)));  // (measurement: smaller tiles)
-  A.in_cap = std::min<uint32_t>(kB2fInCap, ((uint32_t)(1.15 * mean_in * A.T) + 256u + 15u) & ~15u);
-  A.out_cap = std::min<uint32_t>(kB2fOutCap, ((uint32_t)(2.3 * mean_in * A.T) + 16u * 2u * (uint32_t)ns + 256u + 15u) & ~15u);
+  bam_tile_shape(A, kB2fInCap, kB2fOutCap, mean_in, 2.3 * mean_in, 16u * 2u * (uint32_t)ns, "FQGPU_B2F_T");
   A.buf = d_buf;
   A.nbytes = nbytes;
-  A.offs = (const unsigned long long*)c->b2f_off.p;
+  A.offs = (const unsigned long long*)c->bam_off.p;
   A.n = n;
   A.tenx = prm->tenx ? 1 : 0;
   A.n_streams = ns;
@@ -42,9 +32,9 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   B2fScan S;
   memset(&S, 0, sizeof(S));
   for (int s = 0; s < ns; ++s) {
-    A.size[s] = (uint32_t*)((char*)c->b2f_size.p + size_stride * s);
-    A.local[s] = (const unsigned long long*)((char*)c->b2f_local.p + local_stride * s);
-    A.sums[s] = (const unsigned long long*)((char*)c->b2f_sums.p + sums_stride * s);
+    A.size[s] = (uint32_t*)((char*)c->bam_size.p + size_stride * s);
+    A.local[s] = (const unsigned long long*)((char*)c->bam_local.p + local_stride * s);
+    A.sums[s] = (const unsigned long long*)((char*)c->bam_sums.p + sums_stride * s);
     S.in[s] = A.size[s];
     S.local[s] = (unsigned long long*)A.local[s];
     S.sums[s] = (unsigned long long*)A.sums[s];
@@ -75,7 +65,7 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
     c->b2f_out_at[s] = at;
     at += ((size_t)h_total[s] + 64 + 255) & ~(size_t)255;
   }
-  B2F_NEED(ensure(c, c->b2f_out, at + 64));
+  NEED(ensure(c, c->b2f_out, at + 64));
   for (int s = 0; s < ns; ++s) A.out[s] = (uint8_t*)c->b2f_out.p + c->b2f_out_at[s];
   {
     ProfScope ps(c, "k_b2f_emit");
@@ -91,34 +81,19 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
 
 int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets, uint64_t n_records,
                   const fqg_b2f_params* prm, fqg_b2f_result* out) {
-  if (!c || !out || !prm || (n_records && (!stream || !offsets))) return FQG_ERR_ARG;
-  if (mem != FQG_MEM_HOST && mem != FQG_MEM_DEVICE) return FQG_ERR_ARG;
-  if (n_records >= 0x7FFFFFFFull) return fail(c, FQG_ERR_ARG, "fqg_bam2fastq: more than 2^31 alignments in one call");
-  memset(out, 0, sizeof(*out));
-  out->warn_record = FQG_B2F_UNUSED;
-  for (int s = 0; s < FQG_B2F_STREAMS; ++s) {
-    out->first_record[s] = FQG_B2F_UNUSED;
-    c->b2f_out_bytes[s] = 0;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
+  const uint8_t* d_buf;
+  auto begin = [&] {
+    memset(out, 0, sizeof(*out));
+    out->warn_record = FQG_B2F_UNUSED;
+    for (int s = 0; s < FQG_B2F_STREAMS; ++s) out->first_record[s] = FQG_B2F_UNUSED, c->b2f_out_bytes[s] = 0;
+    return 0;
+  };
+  NEED(bam_input(c, "fqg_bam2fastq", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
   if (!n_records) return 0;
   const uint32_t n = (uint32_t)n_records;
-  hipStream_t st = c->stream;
-  for (uint32_t k = 0; k < n; ++k)  // (a tile is the span from its first record to the end of its last)
-    if (offsets[k] + 36 > nbytes || (k && offsets[k] <= offsets[k - 1]))
-      return fail(c, FQG_ERR_ARG, "fqg_bam2fastq: offsets must ascend and lie inside the stream (fqg_bam_index_records)");
-  // the stream on the device, at a 16-byte boundary (the tiles are staged with 16-byte loads)
-  const uint8_t* d_buf;
-  if (mem == FQG_MEM_HOST || ((uintptr_t)stream & 15u)) {
-    B2F_NEED(ensure(c, c->b2f_in, nbytes + 64));
-    HIP_TRY(c, hipMemcpyAsync(c->b2f_in.p, stream, nbytes, mem == FQG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    d_buf = (const uint8_t*)c->b2f_in.p;
-  } else d_buf = (const uint8_t*)stream;
-  B2F_NEED(ensure(c, c->b2f_off, (size_t)n * 8));
-  HIP_TRY(c, hipMemcpyAsync(c->b2f_off.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, st));
   const double mean_in = (double)(nbytes - offsets[0]) / (double)n;
   B2fCall call;
-  B2F_NEED(b2f_run(c, d_buf, nbytes, n, mean_in, prm, out, &call));
+  NEED(b2f_run(c, d_buf, nbytes, n, mean_in, prm, out, &call));
   if (call.first_finding != ~0ull) {
     // as the reference's exit at that alignment: the result and the streams are those of the alignments in front of it
     const uint64_t k = call.first_finding >> 32;
@@ -126,7 +101,7 @@ int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
     const uint64_t aux = call.first_finding & 0xFFFFFFFull;
     if (k) {
       B2fCall before;
-      B2F_NEED(b2f_run(c, d_buf, nbytes, (uint32_t)k, mean_in, prm, out, &before));
+      NEED(b2f_run(c, d_buf, nbytes, (uint32_t)k, mean_in, prm, out, &before));
       if (before.first_finding != ~0ull) return fail(c, FQG_ERR_ARG, "fqg_bam2fastq: the two passes disagree");
     }
     out->n_alignments = k;
@@ -145,4 +120,3 @@ int fqg_bam2fastq_output(fqg_ctx* c, int stream_id, void* host_dst, uint64_t nby
   if (nbytes) HIP_TRY(c, hipMemcpy(host_dst, (const char*)c->b2f_out.p + c->b2f_out_at[stream_id], nbytes, hipMemcpyDeviceToHost));
   return 0;
 }
-#undef B2F_NEED

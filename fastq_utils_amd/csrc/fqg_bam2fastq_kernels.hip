@@ -4,18 +4,17 @@
 // `on` / `op` that sh/fastq2bam wrote, the barcodes from CR/CY, RX/QX (UB/UY), BC/QT; a BAM of any other origin gives
 // its name, its bases (4 bits -> "=ACMGRSVTWYHKDBN") and its qualities (+33).
 //
-// Input: the inflated BAM stream and the offset of every alignment (fqg_bam_index_records), as for bam_add_tags, and
-// the same tile scheme (fqg_bamtags_kernels.hip):
-//   k_b2f_tile<false>  one wavefront per tile of T consecutive alignments, whose bytes are ONE span of the stream: the
-//               span is copied to LDS with 16-byte loads, every lane walks the aux area of ITS alignment once, decides
-//               the routing and writes the bytes its record adds to every stream
+// Input: the inflated BAM stream and the offset of every alignment (fqg_bam_index_records), as for bam_add_tags, walked
+// in the same tiles (the frame: fqg_bam_tile.h):
+//   k_b2f_tile<false>  every lane walks the aux area of ITS alignment once in the staged span, decides the routing and
+//               writes the bytes its record adds to every stream
 //   scan        one 64-bit exclusive prefix per stream, all streams in one launch pair (k_b2f_scan_a / _b)
-//   k_b2f_tile<true>   the same tiles again: the lane writes its FASTQ records into LDS images of the tile's output
-//               span of every stream, and the images go out with 16-byte stores
+//   k_b2f_tile<true>   the same tiles again: the lane writes its FASTQ records into the LDS images of the tile's output
+//               span of every stream
 //   Tiles that do not fit LDS (reads of thousands of bases) read the stream itself, and every lane writes its records
 //   straight to the output.
 // BGZF, the option table, the messages and the gzip writers are host work (host/bam2fastq.cpp).
-#include "fqg_device.h"
+#include "fqg_bam_tile.h"
 
 namespace fqg {
 
@@ -31,12 +30,7 @@ struct B2fCall {
   unsigned long long warn_record;              // first alignment without `on` (not secondary)
   unsigned long long first_record[kB2fStreams];  // first alignment that writes to the stream
 };
-struct B2fTiles {
-  const uint8_t* buf;
-  uint64_t nbytes;
-  const unsigned long long* offs;
-  uint32_t n, T;
-  uint32_t in_cap, out_cap;
+struct B2fTiles : BamTiles {
   int32_t tenx, n_streams;
   uint32_t* size[kB2fStreams];                  // pass 1 writes, pass 2 reads
   const unsigned long long* local[kB2fStreams];  // exclusive prefix of size[s]: local part + span sums
@@ -72,9 +66,6 @@ __device__ __forceinline__ uint32_t b2f_type2size(uint32_t t) {  // bam_aux_type
   if (t == 'I' || t == 'i' || t == 'f' || t == 'F') return 4;
   return 0;
 }
-__device__ __forceinline__ uint32_t b2f_ld32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 
 // The core fields and bam_aux_get's walk (bam_aux.c, __skip_tag: the type is upper-cased, so `d` has size 0), once for
 // all ten names.  rec[0 .. len) is the record; nothing outside it is read.  A walk, a C string or a read that would
@@ -85,9 +76,9 @@ __device__ __forceinline__ void b2f_parse(const uint8_t* rec, uint32_t len, B2fR
 #pragma unroll
   for (int t = 0; t < T_COUNT; ++t) r.tag[t] = 0;
   const uint32_t l_qname = rec[12];
-  const uint32_t flag_nc = b2f_ld32(rec + 16);
+  const uint32_t flag_nc = bam_ld32(rec + 16);
   r.flag = flag_nc >> 16;
-  r.l_qseq = b2f_ld32(rec + 20);
+  r.l_qseq = bam_ld32(rec + 20);
   r.seq = r.qual = 0;
   if (r.flag & 0x100u) return;  // BAM_FSECONDARY: counted, never looked at (:257)
   const uint64_t seq_at = 36ull + l_qname + 4ull * (flag_nc & 0xFFFFu);
@@ -141,7 +132,7 @@ __device__ __forceinline__ void b2f_parse(const uint8_t* rec, uint32_t len, B2fR
         bad = true;
         break;
       }
-      const int32_t cnt = (int32_t)b2f_ld32(rec + s + 1);
+      const int32_t cnt = (int32_t)bam_ld32(rec + s + 1);
       const uint64_t to = (uint64_t)s + 5ull + (uint64_t)b2f_type2size(rec[s]) * (uint64_t)(uint32_t)cnt;
       if (cnt < 0 || to > len) {
         bad = true;
@@ -341,30 +332,19 @@ __device__ __forceinline__ void b2f_records(const uint8_t* rec, B2fRec& r, int t
   }
 }
 
-// One wavefront per tile of A.T consecutive alignments, one lane per alignment.  EMIT = false: what every alignment
-// adds to every stream, the findings, who writes first (pass 1).  EMIT = true: the FASTQ records (pass 2, after the
-// scans).  Both read the tile's bytes once, as one span, through LDS; a tile that does not fit there works on the
-// stream itself.
+// EMIT = false: what every alignment adds to every stream, the findings, who writes first (pass 1).  EMIT = true: the
+// FASTQ records (pass 2, after the scans).  A tile whose span or output images do not fit LDS works on the stream itself.
 template <bool EMIT>
 __global__ __launch_bounds__(kWave) void k_b2f_tile(B2fTiles A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_b2f[];
   uint8_t* s_in = s_b2f;
   uint8_t* s_out = s_b2f + A.in_cap + 32;
   const int lane = (int)threadIdx.x;
-  const uint32_t i0 = blockIdx.x * A.T;
-  if (i0 >= A.n) return;
-  const uint32_t Tn = A.n - i0 < A.T ? A.n - i0 : A.T;
-  const bool valid = (uint32_t)lane < Tn;
-  const uint32_t i = i0 + (valid ? (uint32_t)lane : Tn - 1);
-  const uint64_t in_off = A.offs[i];
-  const uint64_t in0 = rfl64(in_off);
-  const uint32_t in_skew = (uint32_t)(in0 & 15u);  // (the stream starts at a 16-byte boundary)
-  // the tile's span: up to the end of its last record, which only the record itself tells (its start + 36 lies inside
-  // the stream: the caller's offsets were checked)
-  const uint64_t last_off = rl64(in_off, (int)Tn - 1);
-  const uint32_t last_block = b2f_ld32(A.buf + last_off);
-  uint64_t in_end = last_off + 4ull + last_block;
-  if (in_end > A.nbytes) in_end = A.nbytes;
+  BamTileView v;
+  if (!bam_tile_view(A, lane, v)) return;
+  const uint32_t i0 = v.i0, Tn = v.Tn, i = v.i;
+  const bool valid = v.valid;
+  const uint64_t in_off = v.in_off;
   // the output spans of the tile, stream by stream, one behind the other in LDS at 16-byte boundaries + their skew
   uint64_t out_off[kB2fStreams];
   uint32_t img_at[kB2fStreams], img_len[kB2fStreams], img_skew[kB2fStreams];
@@ -376,52 +356,22 @@ __global__ __launch_bounds__(kWave) void k_b2f_tile(B2fTiles A) {
       img_at[s] = img_len[s] = img_skew[s] = 0;
       if (s < A.n_streams) {
         out_off[s] = A.local[s][i] + A.sums[s][i / kScan64Span];
-        const uint64_t o0 = rfl64(out_off[s]);
-        const uint64_t oe = rl64(out_off[s] + A.size[s][i], (int)Tn - 1);
-        img_skew[s] = (uint32_t)((uintptr_t)(A.out[s] + o0) & 15u);
-        const uint64_t len = oe - o0;
-        img_len[s] = len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len;
+        const BamImage im = bam_tile_image(A.out[s], out_off[s], A.size[s][i], Tn);
+        img_skew[s] = im.skew;
+        img_len[s] = im.len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)im.len;
         img_at[s] = out_need;
-        const uint64_t need = (uint64_t)out_need + ((img_skew[s] + len + 15ull) & ~15ull);
+        const uint64_t need = (uint64_t)out_need + ((img_skew[s] + im.len + 15ull) & ~15ull);
         out_need = need > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)need;
       }
     }
   }
-  const bool fits = in_skew + (in_end - in0) + 16 <= (uint64_t)A.in_cap && (!EMIT || (uint64_t)out_need + 16 <= (uint64_t)A.out_cap);
+  const bool fits = v.in_skew + (v.in_end - v.in0) + 16 <= (uint64_t)A.in_cap && (!EMIT || (uint64_t)out_need + 16 <= (uint64_t)A.out_cap);
   const uint8_t* rec;  // the lane's record, in LDS or in the stream
   uint64_t lim;        // the end of what may be read, as a stream offset
   if (fits) {
-    const uint32_t span = in_skew + (uint32_t)(in_end - in0);
-    const uint64_t base = in0 - in_skew;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t units = (span + 15u) >> 4;
-    // whole 16-byte units that lie inside the stream: 8 loads in flight per lane; the last unit(s) of the stream byte by byte
-    const uint64_t safe_units = A.nbytes > base ? (A.nbytes - base) >> 4 : 0;
-    for (uint32_t u0 = 0; u0 < units; u0 += 8 * kWave) {
-      u32x4 v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        uint32_t u = u0 + j * kWave + (uint32_t)lane;
-        u = u < units ? u : units - 1;
-        if ((uint64_t)u < safe_units) v[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(A.buf + base + 16ull * u));
-        else {
-          uint32_t t[4] = {0, 0, 0, 0};  // (unrolled: the words stay in registers)
-#pragma unroll
-          for (int b = 0; b < 16; ++b)
-            if (base + 16ull * u + (uint64_t)b < A.nbytes) t[b >> 2] |= (uint32_t)A.buf[base + 16ull * u + (uint64_t)b] << (8 * (b & 3));
-          v[j] = u32x4{t[0], t[1], t[2], t[3]};
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t u = u0 + j * kWave + (uint32_t)lane;
-        if (u < units) *reinterpret_cast<u32x4*>(s_in + 16u * u) = v[j];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    const uint64_t base = bam_tile_stage(A, v, lane, s_in);
     rec = s_in + (uint32_t)(in_off - base);
-    lim = in_end;
+    lim = v.in_end;
   } else {
     rec = A.buf + in_off;
     lim = A.nbytes;
@@ -431,7 +381,7 @@ __global__ __launch_bounds__(kWave) void k_b2f_tile(B2fTiles A) {
   r.finding = r.aux = 0;
   r.flag = 0x100u;  // (a record that is not parsed writes nothing)
   r.len = 0;
-  const uint32_t block = in_off + 4 <= lim ? b2f_ld32(rec) : 0u;
+  const uint32_t block = in_off + 4 <= lim ? bam_ld32(rec) : 0u;
   if (block < 32u || in_off + 4ull + block > lim) r.finding = (uint32_t)FQG_E_B2F_AUX;
   else b2f_parse(rec, 4u + block, r);
   bool no_on = false;

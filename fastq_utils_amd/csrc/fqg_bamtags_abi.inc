@@ -1,37 +1,19 @@
 // fqg_bamtags_abi.inc - fqg_bam_add_tags / fqg_bam_add_tags_output (include/fqg.h), included by fqg_abi.hip
 
-#define BT_NEED(rc_) \
-  do {               \
-    int r__ = (rc_); \
-    if (r__) return r__; \
-  } while (0)
-
 int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets, uint64_t n_records,
                      const fqg_bam_tags_params* prm, fqg_bam_tags_result* out) {
-  if (!c || !out || !prm || (n_records && (!stream || !offsets))) return FQG_ERR_ARG;
-  if (mem != FQG_MEM_HOST && mem != FQG_MEM_DEVICE) return FQG_ERR_ARG;
-  if (n_records >= 0x7FFFFFFFull) return fail(c, FQG_ERR_ARG, "fqg_bam_add_tags: more than 2^31 alignments in one call");
-  if (prm->n_targets && (!prm->tx_off || !prm->tx_len || !prm->gx_off || !prm->gx_len || !prm->names)) return FQG_ERR_ARG;
-  memset(out, 0, sizeof(*out));
-  out->n_alignments = n_records;
-  c->bt_out_bytes = 0;
-  HIP_TRY(c, hipSetDevice(c->device));
+  const uint8_t* d_buf;
+  auto begin = [&] {
+    if (prm->n_targets && (!prm->tx_off || !prm->tx_len || !prm->gx_off || !prm->gx_len || !prm->names)) return (int)FQG_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    out->n_alignments = n_records;
+    c->bt_out_bytes = 0;
+    return 0;
+  };
+  NEED(bam_input(c, "fqg_bam_add_tags", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
   if (!n_records) return 0;
   const uint32_t n = (uint32_t)n_records;
   hipStream_t st = c->stream;
-  for (uint32_t k = 0; k < n; ++k)  // (a tile is the span from its first record to the end of its last)
-    if (offsets[k] + 36 > nbytes || (k && offsets[k] <= offsets[k - 1]))
-      return fail(c, FQG_ERR_ARG, "fqg_bam_add_tags: offsets must ascend and lie inside the stream (fqg_bam_index_records)");
-
-  // the stream on the device, at a 16-byte boundary (the tiles are staged with 16-byte loads)
-  const uint8_t* d_buf;
-  if (mem == FQG_MEM_HOST || ((uintptr_t)stream & 15u)) {
-    BT_NEED(ensure(c, c->bt_in, nbytes + 64));
-    HIP_TRY(c, hipMemcpyAsync(c->bt_in.p, stream, nbytes, mem == FQG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    d_buf = (const uint8_t*)c->bt_in.p;
-  } else d_buf = (const uint8_t*)stream;
-  BT_NEED(ensure(c, c->bt_off, (size_t)n * 8));
-  HIP_TRY(c, hipMemcpyAsync(c->bt_off.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, st));
 
   BtParams P;
   memset(&P, 0, sizeof(P));
@@ -39,7 +21,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
   P.tx_tag = prm->tx_tag;
   P.n_targets = prm->n_targets;
   const size_t nt = prm->n_targets;
-  BT_NEED(ensure(c, c->bt_tables, nt * 16 + prm->names_bytes + 64));
+  NEED(ensure(c, c->bt_tables, nt * 16 + prm->names_bytes + 64));
   {
     uint32_t* t = (uint32_t*)c->bt_tables.p;
     if (nt) {
@@ -63,34 +45,28 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
   }
 
   const uint64_t nb = ((uint64_t)n + kScan64Span - 1) / kScan64Span;
-  BT_NEED(ensure(c, c->bt_size, (size_t)n * 4));
-  BT_NEED(ensure(c, c->bt_local, (size_t)n * 8));
-  BT_NEED(ensure(c, c->bt_sums, (size_t)nb * 8 + 64));
-  BT_NEED(ensure(c, c->bt_call, sizeof(BtCall) + 16));
+  NEED(ensure(c, c->bam_size, (size_t)n * 4));
+  NEED(ensure(c, c->bam_local, (size_t)n * 8));
+  NEED(ensure(c, c->bam_sums, (size_t)nb * 8 + 64));
+  NEED(ensure(c, c->bt_call, sizeof(BtCall) + 16));
   BtCall h_call;
   memset(&h_call, 0, sizeof(h_call));
   h_call.first_finding = ~0ull;
   BtCall* d_call = (BtCall*)c->bt_call.p;
   unsigned long long* d_total = (unsigned long long*)((char*)c->bt_call.p + sizeof(BtCall));
   HIP_TRY(c, hipMemcpyAsync(d_call, &h_call, sizeof(h_call), hipMemcpyHostToDevice, st));
-  // records per tile and the two LDS areas: what the mean record needs (a tile that does not fit takes the slow
-  // path); small areas let more wavefronts share a CU
   const double mean_in = (double)(nbytes - offsets[0]) / (double)n;
-  const double mean_out = mean_in + 16.0 * 4 + (prm->tx_tag ? 40.0 : 0.0);  // (a guess: sizes are not known yet)
   BtTiles A;
   memset(&A, 0, sizeof(A));
-  A.T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)kBtInCap - 64.0) / (1.1 * mean_in + 1.0))));
-  if (const char* e = getenv("FQGPU_BT_T")) A.T = (uint32_t)std::max(1, std::min<int>((int)A.T, atoi(e)));  // (measurement: smaller tiles)
-  A.in_cap = std::min<uint32_t>(kBtInCap, ((uint32_t)(1.15 * mean_in * A.T) + 256u + 15u) & ~15u);
-  A.out_cap = std::min<uint32_t>(kBtOutCap, ((uint32_t)(1.15 * mean_out * A.T) + 256u + 15u) & ~15u);
+  bam_tile_shape(A, kBtInCap, kBtOutCap, mean_in, 1.15 * (mean_in + 16.0 * 4 + (prm->tx_tag ? 40.0 : 0.0)), 0, "FQGPU_BT_T");
   const unsigned lds = A.in_cap + A.out_cap + 64;
   A.buf = d_buf;
   A.nbytes = nbytes;
-  A.offs = (const unsigned long long*)c->bt_off.p;
+  A.offs = (const unsigned long long*)c->bam_off.p;
   A.n = n;
-  A.new_size = (uint32_t*)c->bt_size.p;
-  A.out_local = (const unsigned long long*)c->bt_local.p;
-  A.out_sums = (const unsigned long long*)c->bt_sums.p;
+  A.new_size = (uint32_t*)c->bam_size.p;
+  A.out_local = (const unsigned long long*)c->bam_local.p;
+  A.out_sums = (const unsigned long long*)c->bam_sums.p;
   A.P = P;
   A.call = d_call;
   const unsigned grid = (n + A.T - 1) / A.T;
@@ -100,9 +76,9 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
   }
   {
     ProfScope ps(c, "k_bt_scan");
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, st, (const uint32_t*)c->bt_size.p, (uint64_t)n,
-                       (unsigned long long*)c->bt_local.p, (unsigned long long*)c->bt_sums.p);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, (unsigned long long*)c->bt_sums.p, nb, d_total);
+    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, st, (const uint32_t*)c->bam_size.p, (uint64_t)n,
+                       (unsigned long long*)c->bam_local.p, (unsigned long long*)c->bam_sums.p);
+    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, (unsigned long long*)c->bam_sums.p, nb, d_total);
   }
   unsigned long long h_total = 0;
   HIP_TRY(c, hipMemcpyAsync(&h_call, d_call, sizeof(h_call), hipMemcpyDeviceToHost, st));
@@ -115,7 +91,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     return 0;  // (nothing is written for a stream the reference has no defined output for)
   }
   out->out_bytes = h_total;
-  BT_NEED(ensure(c, c->bt_out, (size_t)h_total + 64));
+  NEED(ensure(c, c->bt_out, (size_t)h_total + 64));
   A.out = (uint8_t*)c->bt_out.p;
   {
     ProfScope ps(c, "k_bt_emit");
@@ -134,4 +110,3 @@ int fqg_bam_add_tags_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) {
   if (nbytes) HIP_TRY(c, hipMemcpy(host_dst, c->bt_out.p, nbytes, hipMemcpyDeviceToHost));
   return 0;
 }
-#undef BT_NEED

@@ -3,17 +3,18 @@
 // get_barcodes :43-99) become aux tags at the end of every alignment record (bam_aux_append: tag, 'Z', value, NUL):
 // RX or UB (--10x), CR, BC, and with --tx the reference's name (tx) and its gene (GX, --tx_2_gx).
 //
-// Input: the inflated BAM stream and the offset of every alignment (fqg_bam_index_records), as for bam_umi_count.
-//   k_bt_tile<false>  one wavefront per tile of T consecutive alignments, whose bytes are ONE span of the stream: the
-//               span is copied to LDS with 16-byte loads, every lane runs get_barcodes on the name of ITS alignment
-//               there and writes the size the record grows to
+// Input: the inflated BAM stream and the offset of every alignment (fqg_bam_index_records), as for bam_umi_count,
+// walked in tiles of T consecutive alignments, one wavefront per tile and one lane per alignment (the frame:
+// fqg_bam_tile.h):
+//   k_bt_tile<false>  every lane runs get_barcodes on the name of ITS alignment in the staged span and writes the size
+//               the record grows to
 //   scan        64-bit exclusive prefix of the new record sizes (k_scan64_a / _b)
 //   k_bt_tile<true>   the same tiles again: the lane parses the name once more (cheaper than keeping what pass 1
-//               found), rebuilds its record in an LDS image of the tile's OUTPUT span (block_size patched, tags
-//               appended), and the image goes out with 16-byte stores.
+//               found) and rebuilds its record in the LDS image of the tile's OUTPUT span (block_size patched, tags
+//               appended)
 //   Tiles that do not fit LDS (long reads) read the stream itself and are copied record by record.
 // Everything else of the program is host work: BGZF, the header (copied verbatim), the transcript -> gene map.
-#include "fqg_device.h"
+#include "fqg_bam_tile.h"
 
 namespace fqg {
 
@@ -103,12 +104,7 @@ __device__ __forceinline__ void bt_copy(BtLds dst, BtLds src, uint32_t n) {
   for (; i < n; ++i) dst[i] = src[i];
 }
 
-struct BtTiles {
-  const uint8_t* buf;
-  uint64_t nbytes;
-  const unsigned long long* offs;
-  uint32_t n, T;                  // alignments; per tile
-  uint32_t in_cap, out_cap;       // LDS bytes of the two areas (dynamic shared memory: in_cap + out_cap + 64)
+struct BtTiles : BamTiles {
   uint32_t* new_size;             // pass 1 writes, pass 2 reads
   const unsigned long long* out_local;  // exclusive prefix of new_size: local part + span sums
   const unsigned long long* out_sums;
@@ -173,73 +169,36 @@ __device__ __forceinline__ void bt_tags(const BtParams& P, const BtRec& r, int32
   }
 }
 
-// One wavefront per tile of A.T consecutive alignments, one lane per alignment.  EMIT = false: the new record sizes
-// (pass 1).  EMIT = true: the records with their tags (pass 2, after the scan of the sizes).  Both read the tile's
-// bytes once, as one span, through LDS; a tile that does not fit there (long reads) works on the stream itself.
+// EMIT = false: the new record sizes (pass 1).  EMIT = true: the records with their tags (pass 2, after the scan of the
+// sizes).  A tile whose span or output image does not fit LDS (long reads) works on the stream itself.
 template <bool EMIT>
 __global__ __launch_bounds__(kWave) void k_bt_tile(BtTiles A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_bt[];
   uint8_t* s_in = s_bt;
   uint8_t* s_out = s_bt + A.in_cap + 32;
   const int lane = (int)threadIdx.x;
-  const uint32_t i0 = blockIdx.x * A.T;
-  if (i0 >= A.n) return;
-  const uint32_t Tn = A.n - i0 < A.T ? A.n - i0 : A.T;
-  const bool valid = (uint32_t)lane < Tn;
-  const uint32_t i = i0 + (valid ? (uint32_t)lane : Tn - 1);
-  const uint64_t in_off = A.offs[i];
-  const uint64_t in0 = rfl64(in_off);
-  // the tile's span: up to the end of its last record, which only the record itself tells
-  uint64_t out_off = 0, out0 = 0, out_end = 0;
+  BamTileView v;
+  if (!bam_tile_view(A, lane, v)) return;
+  const uint32_t Tn = v.Tn, i = v.i;
+  const bool valid = v.valid;
+  const uint64_t in_off = v.in_off;
+  uint64_t out_off = 0;
   uint32_t out_len = 0;
+  BamImage im = {0, 0, 0};
   if (EMIT) {
     out_len = A.new_size[i];
     out_off = A.out_local[i] + A.out_sums[i / kScan64Span];
-    out0 = rfl64(out_off);
-    out_end = rl64(out_off + out_len, (int)Tn - 1);
+    im = bam_tile_image(A.out, out_off, out_len, Tn);
   }
-  const uint32_t in_skew = (uint32_t)(in0 & 15u);  // (the stream starts at a 16-byte boundary)
-  const uint32_t out_skew = EMIT ? (uint32_t)((uintptr_t)(A.out + out0) & 15u) : 0u;
-  // bound of the span before the last record's length is known: its start + 4 (the length field) is inside for sure;
-  // the true end follows from the staged length field
-  const uint64_t last_off = rl64(in_off, (int)Tn - 1);
-  uint32_t last_block = 0;
-  if (last_off + 4 <= A.nbytes) __builtin_memcpy(&last_block, A.buf + last_off, 4);
-  const uint64_t in_end = last_off + 4ull + last_block;
-  const bool fits = in_skew + (in_end - in0) + 16 <= (uint64_t)A.in_cap &&
-                    (!EMIT || out_skew + (out_end - out0) + 16 <= (uint64_t)A.out_cap);
+  // (a last record that leaves the stream: no span is staged, the lanes read the stream itself, zeros behind its end)
+  const bool fits = v.inside && v.in_skew + (v.in_end - v.in0) + 16 <= (uint64_t)A.in_cap &&
+                    (!EMIT || im.skew + im.len + 16 <= (uint64_t)A.out_cap);
   uint32_t block = 0;
   int32_t tid = -1;
   BtRec r;
   uint32_t finding = 0, add = 0;
   if (fits) {
-    const uint32_t span = in_skew + (uint32_t)(in_end - in0);
-    const uint64_t base = in0 - in_skew;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t units = (span + 15u) >> 4;
-    // whole 16-byte units that lie inside the stream: 8 loads in flight per lane; the last unit(s) of the stream byte by byte
-    const uint64_t safe_units = A.nbytes > base ? (A.nbytes - base) >> 4 : 0;
-    for (uint32_t u0 = 0; u0 < units; u0 += 8 * kWave) {
-      u32x4 v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        uint32_t u = u0 + j * kWave + (uint32_t)lane;
-        u = u < units ? u : units - 1;
-        if ((uint64_t)u < safe_units) v[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(A.buf + base + 16ull * u));
-        else {
-          u32x4 t = {0, 0, 0, 0};
-          for (uint64_t b = 0; base + 16ull * u + b < A.nbytes && b < 16; ++b) reinterpret_cast<uint8_t*>(&t)[b] = A.buf[base + 16ull * u + b];
-          v[j] = t;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t u = u0 + j * kWave + (uint32_t)lane;
-        if (u < units) *reinterpret_cast<u32x4*>(s_in + 16u * u) = v[j];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    const uint64_t base = bam_tile_stage(A, v, lane, s_in);
     const BtLds img = (BtLds)s_in;  // img[k] = stream byte base + k
     block = *(__attribute__((address_space(3))) bt_u32*)(img + (uint32_t)(in_off - base));
     tid = (int32_t) * (__attribute__((address_space(3))) bt_u32*)(img + (uint32_t)(in_off - base) + 4);
@@ -247,7 +206,7 @@ __global__ __launch_bounds__(kWave) void k_bt_tile(BtTiles A) {
     if (EMIT) {
       if (valid) {
         const BtLds src = img + (uint32_t)(in_off - base);
-        BtLds dst = (BtLds)s_out + out_skew + (uint32_t)(out_off - out0);
+        BtLds dst = (BtLds)s_out + im.skew + (uint32_t)(out_off - im.first);
         const uint32_t in_len = 4u + block;
         bt_copy(dst, src, in_len);
         bt_st4(dst, out_len - 4u);  // block_size
@@ -294,11 +253,11 @@ __global__ __launch_bounds__(kWave) void k_bt_tile(BtTiles A) {
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      emit_flush(s_out, out_skew, (uint32_t)(out_end - out0), A.out + out0, lane);
+      emit_flush(s_out, im.skew, (uint32_t)im.len, A.out + im.first, lane);
     }
   } else {
-    __builtin_memcpy(&block, A.buf + in_off, 4);
-    __builtin_memcpy(&tid, A.buf + in_off + 4, 4);
+    block = bam_ld32(A.buf + in_off);
+    tid = (int32_t)bam_ld32(A.buf + in_off + 4);
     const uint8_t* gb = A.buf;
     const uint64_t nbytes = A.nbytes;
     add = bt_growth(A.P,

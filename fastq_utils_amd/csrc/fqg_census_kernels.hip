@@ -12,6 +12,7 @@
 // (cell, UMI) (rocPRIM radix sort, fqg_abi.hip) and k_census_* turn the sorted pairs into one line per cell: reads and
 // distinct UMIs - bam_umi_count's per-cell totals before a gene tag exists.
 #include "fqg_device.h"
+#include "fqg_tile.h"
 
 namespace fqg {
 

@@ -10,6 +10,7 @@
 // 16-byte stores.  The decision is recomputed by the emit kernel (a few LDS reads) rather than
 // stored.  Tiles that do not fit LDS (long reads) go through the *_direct paths.
 #include "fqg_device.h"
+#include "fqg_tile.h"
 
 namespace fqg {
 

@@ -30,6 +30,7 @@
 // The UMI container is a set, as src/range_list.h:150-162 documents it; the reference's RL_Tree
 // implementation loses and invents members when ids arrive out of order.
 #include "fqg_device.h"
+#include "fqg_tile.h"
 
 namespace fqg {
 

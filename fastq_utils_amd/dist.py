@@ -501,15 +501,13 @@ def bam_split(stream):
 
     from . import abi as A
 
-    L = A.load()
     buf = (C.c_char * len(stream)).from_buffer_copy(stream)
-    n, used = C.c_uint64(), C.c_uint64()
-    if L.fqg_bam_index_records(buf, len(stream), None, 0, C.byref(n), C.byref(used)) != 0:
-        raise ValueError("not a BAM stream")
-    offs = np.zeros(max(1, n.value), dtype=np.uint64)
-    L.fqg_bam_index_records(buf, len(stream), offs.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n), C.byref(used))
-    offs = offs[:n.value]
-    return stream[:int(offs[0]) if n.value else used.value], offs, used.value
+    try:
+        offs, n, used = A._bam_offsets(buf, len(stream))
+    except A.FqgError:
+        raise ValueError("not a BAM stream") from None
+    offs = np.frombuffer(offs, dtype=np.uint64, count=n)
+    return stream[:int(offs[0]) if n else used], offs, used
 
 
 def umi_replayed_names(ctx, info):

@@ -10,7 +10,7 @@
 //   GPU    everything per alignment: the aux walk, the routing, base decode, quality shift, read-name repair
 // There is no CPU path for the record work: without a GPU the program fails before it converts anything.
 // One device (FQGPU_DEVICE); FQGPU_DEVICES is not looked at.
-#include "fq_parallel.h"
+#include "bam_input.h"
 #include <errno.h>
 #include <getopt.h>
 #include <stdint.h>
@@ -26,31 +26,11 @@
 #include "../../include/fqg.h"
 
 namespace {
+using namespace fqbam;
 
 const char kVersion[] = "0.25.3";
 const char kUsage[] = "Usage: bam2fastq --bam in.bam --out fastq_prefix [--verbose --10x|-X]";
 fqg_ctx* g_ctx = nullptr;
-
-// (as the other drop-in programs leave: everything flushed, without exit()'s hooks - see bam_add_tags.cpp)
-[[noreturn]] void leave(int code) {
-  fflush(nullptr);
-  if (getenv("FQGPU_PLAIN_EXIT")) exit(code);
-  _exit(code);
-}
-
-#define PRINT_ERROR(...)          \
-  do {                            \
-    fprintf(stderr, "\nERROR: "); \
-    fprintf(stderr, __VA_ARGS__); \
-    fprintf(stderr, "\n");        \
-  } while (0)
-
-bool read_all(FILE* f, std::vector<uint8_t>& raw) {
-  uint8_t buf[1 << 16];
-  size_t k;
-  while ((k = fread(buf, 1, sizeof(buf), f)) > 0) raw.insert(raw.end(), buf, buf + k);
-  return !ferror(f);
-}
 
 size_t piece_bytes() {  // FQGPU_CHUNK_MB: the size of the pieces in which the stream goes to the GPU
   const char* e = getenv("FQGPU_CHUNK_MB");
@@ -124,20 +104,12 @@ int main(int argc, char* argv[]) {
     PRINT_ERROR("no usable MI355X device (fqg_open: %d); this program has no CPU path", rc);
     leave(2);
   }
-  std::vector<uint8_t> raw, stream;
-  if (!read_all(in, raw) || !fqhost::bgzf_inflate_parallel(raw, stream)) {
-    PRINT_ERROR("%s is not a readable BGZF / BAM file", bam_file);
-    leave(2);
-  }
-  raw.clear();
-  raw.shrink_to_fit();
-  uint64_t n_rec = 0, used = 0;
-  if (fqg_bam_index_records(stream.data(), stream.size(), nullptr, 0, &n_rec, &used) != 0) {
-    PRINT_ERROR("%s is not a BAM file", bam_file);
-    leave(2);
-  }
-  std::vector<uint64_t> offsets(n_rec ? n_rec : 1);
-  fqg_bam_index_records(stream.data(), stream.size(), offsets.data(), n_rec, &n_rec, &used);  // (a record cut short ends the loop, :249)
+  BamInput bam;
+  bam.inflate(in, bam_file);
+  bam.index(bam_file);  // (a record cut short ends the loop, :249)
+  const std::vector<uint8_t>& stream = bam.stream;
+  const std::vector<uint64_t>& offsets = bam.offsets;
+  const uint64_t n_rec = bam.n_rec, used = bam.used;
 
   Outputs outs;
   outs.prefix = out_file_prefix;

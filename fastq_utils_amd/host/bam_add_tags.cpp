@@ -9,7 +9,7 @@
 //          (written as read), the transcript -> gene map (:203-232) resolved once per reference of the header
 //   GPU    everything per alignment: get_barcodes on the name, the new tags, the rewritten record stream
 // There is no CPU path for the record work: without a GPU the program fails before it reads the input.
-#include "fq_parallel.h"
+#include "bam_input.h"
 #include <errno.h>
 #include <getopt.h>
 #include <stdint.h>
@@ -25,6 +25,7 @@
 #include "../../include/fqg.h"
 
 namespace {
+using namespace fqbam;
 
 const char kVersion[] = "0.25.3";
 const char kUsage[] =
@@ -32,35 +33,12 @@ const char kUsage[] =
 constexpr size_t kMaxFeatLen = 50;  // MAX_FEAT_LEN, src/bam_add_tags.c:36
 fqg_ctx* g_ctx = nullptr;
 
-// How the program leaves: with everything it wrote flushed, and WITHOUT exit()'s hooks - the HIP runtime tears itself
-// down in one of them, and now and then that ended a run that had printed all it had to print with a segmentation
-// fault (status 139 instead of 0: seen once in 300 runs of the GPU suite).  The other drop-in programs leave the same way.
-[[noreturn]] static void leave(int code) {
-  fflush(nullptr);
-  if (getenv("FQGPU_PLAIN_EXIT")) exit(code);  // (tools/exit_stress.py: does the process survive exit()'s hooks?)
-  _exit(code);
-}
-
-#define PRINT_ERROR(...)             \
-  do {                               \
-    fprintf(stderr, "\nERROR: ");    \
-    fprintf(stderr, __VA_ARGS__);    \
-    fprintf(stderr, "\n");           \
-  } while (0)
-
 void print_usage(int error) {  // :101-108
   if (error > 0) {
     PRINT_ERROR("%s", kUsage);
     leave(error);
   }
   fprintf(stderr, "%s\n", kUsage);
-}
-
-bool read_all(FILE* f, std::vector<uint8_t>& raw) {
-  uint8_t buf[1 << 16];
-  size_t k;
-  while ((k = fread(buf, 1, sizeof(buf), f)) > 0) raw.insert(raw.end(), buf, buf + k);
-  return !ferror(f);
 }
 
 }  // namespace
@@ -149,20 +127,12 @@ int main(int argc, char* argv[]) {
     PRINT_ERROR("no usable MI355X device (fqg_open: %d); this program has no CPU path", rc);
     leave(2);
   }
-  std::vector<uint8_t> raw, stream;
-  if (!read_all(in, raw) || !fqhost::bgzf_inflate_parallel(raw, stream)) {
-    PRINT_ERROR("%s is not a readable BGZF / BAM file", inbam_file);
-    leave(2);
-  }
-  raw.clear();
-  raw.shrink_to_fit();
-  uint64_t n_rec = 0, used = 0;
-  if (fqg_bam_index_records(stream.data(), stream.size(), nullptr, 0, &n_rec, &used) != 0) {
-    PRINT_ERROR("%s is not a BAM file", inbam_file);
-    leave(2);
-  }
-  std::vector<uint64_t> offsets(n_rec ? n_rec : 1);
-  fqg_bam_index_records(stream.data(), stream.size(), offsets.data(), n_rec, &n_rec, &used);
+  BamInput bam;
+  bam.inflate(in, inbam_file);
+  bam.index(inbam_file);
+  const std::vector<uint8_t>& stream = bam.stream;
+  const std::vector<uint64_t>& offsets = bam.offsets;
+  const uint64_t n_rec = bam.n_rec, used = bam.used;
   const uint64_t header_end = n_rec ? offsets[0] : used;
   if (header_end > stream.size()) {
     PRINT_ERROR("%s is not a BAM file", inbam_file);

@@ -9,7 +9,7 @@
 //   GPU    everything per alignment: filters, aux tags, barcode packing, the label maps, the
 //          (cell, feature, UMI) set, float32 counters, which lines each cell prints
 // There is no CPU path for the record work: without a GPU the program fails at start-up.
-#include "fq_parallel.h"
+#include "bam_input.h"
 #include <errno.h>
 #include <getopt.h>
 #include <stdint.h>
@@ -26,25 +26,10 @@
 #include "umi_multi.h"
 
 namespace {
+using namespace fqbam;
 
 const char kVersion[] = "0.25.3";
 fqg_ctx* g_ctx = nullptr;
-
-// How the program leaves: with everything it wrote flushed, and WITHOUT exit()'s hooks - the HIP runtime tears itself
-// down in one of them, and now and then that ended a run that had printed all it had to print with a segmentation
-// fault (status 139 instead of 0: seen once in 300 runs of the GPU suite).  The other drop-in programs leave the same way.
-[[noreturn]] static void leave(int code) {
-  fflush(nullptr);
-  if (getenv("FQGPU_PLAIN_EXIT")) exit(code);  // (tools/exit_stress.py: does the process survive exit()'s hooks?)
-  _exit(code);
-}
-
-#define PRINT_ERROR(...)             \
-  do {                               \
-    fprintf(stderr, "\nERROR: ");    \
-    fprintf(stderr, __VA_ARGS__);    \
-    fprintf(stderr, "\n");           \
-  } while (0)
 
 [[noreturn]] void die_lib(const char* what, int rc) {
   PRINT_ERROR("GPU library failure in %s (%d): %s", what, rc, g_ctx ? fqg_last_error(g_ctx) : "no context");
@@ -83,14 +68,6 @@ std::vector<uint64_t> load_whitelist(const char* file) {
   fclose(fd);
   fprintf(stderr, "Loading whitelist from %s...done.\n", file);
   return v;
-}
-
-// the whole file, BGZF members inflated back to back (SAM/BAM specification, section 4.1)
-bool read_all(FILE* f, std::vector<uint8_t>& raw) {
-  uint8_t buf[1 << 16];
-  size_t k;
-  while ((k = fread(buf, 1, sizeof(buf), f)) > 0) raw.insert(raw.end(), buf, buf + k);
-  return !ferror(f);
 }
 
 void write_rows(const std::string& file, const std::vector<char>& names, uint64_t n) {  // write_map2fileL :271-290
@@ -212,13 +189,8 @@ int main(int argc, char* argv[]) {
     PRINT_ERROR("no usable MI355X device (fqg_open: %d); this program has no CPU path", rc);
     leave(2);
   }
-  std::vector<uint8_t> raw, stream;
-  if (!read_all(in, raw) || !fqhost::bgzf_inflate_parallel(raw, stream)) {
-    PRINT_ERROR("%s is not a readable BGZF / BAM file", bam_file);
-    leave(2);
-  }
-  raw.clear();
-  raw.shrink_to_fit();
+  BamInput bam;
+  bam.inflate(in, bam_file);
   fprintf(stderr, "Processing %s\n", bam_file);
 
   const char kHdr[] = "%%MatrixMarket matrix coordinate real general\n";  // the reference prints both percent signs
@@ -242,14 +214,10 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "Cells processed\n");
   }
 
-  uint64_t n_rec = 0, used = 0;
-  std::vector<uint64_t> offsets;
-  if (fqg_bam_index_records(stream.data(), stream.size(), nullptr, 0, &n_rec, &used) != 0) {
-    PRINT_ERROR("%s is not a BAM file", bam_file);
-    leave(2);
-  }
-  offsets.resize(n_rec ? n_rec : 1);
-  fqg_bam_index_records(stream.data(), stream.size(), offsets.data(), n_rec, &n_rec, &used);
+  bam.index(bam_file);
+  const std::vector<uint8_t>& stream = bam.stream;
+  const std::vector<uint64_t>& offsets = bam.offsets;
+  const uint64_t n_rec = bam.n_rec, used = bam.used;
 
   fqg_umi_params prm;
   memset(&prm, 0, sizeof(prm));

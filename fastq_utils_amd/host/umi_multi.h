@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/fqg.h"
+#include "bam_input.h"
 
 namespace fqhost {
 
@@ -111,9 +112,7 @@ struct Shard {
 
 inline bool index_records(Shard& s) {
   uint64_t n = 0, used = 0;
-  if (fqg_bam_index_records(s.buf.data(), s.buf.size(), nullptr, 0, &n, &used) != 0) return false;
-  s.offs.assign(n ? n : 1, 0);
-  return fqg_bam_index_records(s.buf.data(), s.buf.size(), s.offs.data(), n, &n, &used) == 0 && (s.offs.resize(n), true);
+  return fqbam::index_records(s.buf.data(), s.buf.size(), s.offs, &n, &used) && (s.offs.resize(n), true);
 }
 
 inline bool count(Shard& s, const fqg_umi_params& prm, bool want_lists) {

@@ -132,6 +132,42 @@ def test_both_paths_are_taken(ctx):
     check(ctx.bam2fastq(longest), b2f.convert(longest))
 
 
+_EDGES = {}
+
+
+def edge_case(n, rem):
+    """(stream of n short alignments whose last record's aux is padded until len(stream) % 16 == rem, what the oracle
+    makes of it): computed once, shared"""
+    if (n, rem) not in _EDGES:
+        rng = np.random.default_rng(16 * n + rem)
+        recs = [b2f_gen.fastq2bam_record(rng, i, sample=i % 3 == 0) if i % 4 else b2f_gen.plain_record(rng, i) for i in range(n - 1)]
+        for pad in range(16):
+            stream = b2f_gen.stream(recs + [b2f_gen.fastq2bam_record(np.random.default_rng(n), n - 1, extra=bamgen.aux_z(b"XA", b"x" * pad))])
+            if len(stream) % 16 == rem:
+                break
+        assert len(stream) % 16 == rem
+        _EDGES[(n, rem)] = (stream, b2f.convert(stream))
+    return _EDGES[(n, rem)]
+
+
+@pytest.mark.parametrize("resident", [False, True], ids=["host", "device+5"])
+@pytest.mark.parametrize("rem", [0, 1, 15])
+@pytest.mark.parametrize("n", [1, 64, 65])
+def test_staging_edges(ctx, n, rem, resident):
+    """the tile's span ends with the stream, 0, 1 and 15 bytes behind a 16-byte boundary: the last unit of the staging
+    loop, read byte by byte; one tile, a full one, a full one and one alignment"""
+    stream, want = edge_case(n, rem)
+    if resident:
+        import torch
+        t = torch.zeros(len(stream) + 64, dtype=torch.uint8, device="cuda:0")
+        t[5:5 + len(stream)] = torch.frombuffer(bytearray(stream), dtype=torch.uint8).to("cuda:0")
+        got = ctx.bam2fastq(t.data_ptr() + 5, offsets=b2f.record_offsets(stream), nbytes=len(stream))
+    else:
+        got = ctx.bam2fastq(stream)
+    assert want["n_alignments"] == n and any(want["streams"])
+    check(got, want)
+
+
 def test_device_resident_stream_offsets_and_first_alignment(ctx):
     import torch
     stream, _ = case(5000, 1, 7)

@@ -120,13 +120,104 @@ def test_device_resident_stream(ctx):
     for shift in (0, pad):
         t = torch.zeros(len(stream) + 64, dtype=torch.uint8, device="cuda:0")
         t[shift:shift + len(stream)] = torch.frombuffer(bytearray(stream), dtype=torch.uint8).to("cuda:0")
-        offs = []
-        p = bto.parse_header(stream)[1]
-        while p + 4 <= len(stream):
-            offs.append(p)
-            p += 4 + struct.unpack_from("<i", stream, p)[0]
-        got = ctx.bam_add_tags(t.data_ptr() + shift, tx_tag=True, targets=names, offsets=offs, nbytes=len(stream))
+        got = ctx.bam_add_tags(t.data_ptr() + shift, tx_tag=True, targets=names, offsets=record_offsets(stream), nbytes=len(stream))
         assert got["code"] == 0 and got["records"] == want
+
+
+def record_offsets(stream):
+    offs, p = [], bto.parse_header(stream)[1]
+    while p + 4 <= len(stream):
+        offs.append(p)
+        p += 4 + struct.unpack_from("<i", stream, p)[0]
+    return offs
+
+
+def test_both_paths_are_taken(ctx):
+    """The LDS areas are sized by the mean record (bam_tile_shape, fqg_abi.hip).  65 alignments, the last a read of
+    8 000 bases or more: as sized by default (a mean record of some hundred bytes: tiles of many alignments) the tile
+    of the long read does not fit LDS and the others do; with FQGPU_BT_T=1 every alignment is a tile of its own."""
+    stream, names = make_stream(np.random.default_rng(65), 65, long_every=65)
+    want, n = oracle_records(stream, tx_tag=True)
+    assert n == 65 and max(np.diff(record_offsets(stream) + [len(stream)])) >= 8000 * 3 // 2
+    got = ctx.bam_add_tags(stream, tx_tag=True, targets=names)
+    assert got["code"] == 0 and got["records"] == want
+    os.environ["FQGPU_BT_T"] = "1"
+    try:
+        got = ctx.bam_add_tags(stream, tx_tag=True, targets=names)
+    finally:
+        del os.environ["FQGPU_BT_T"]
+    assert got["code"] == 0 and got["records"] == want
+
+
+EDGE_NAMES = [b"TX0", b"TX1"]
+_EDGES = {}
+
+
+def edge_case(n, rem):
+    """(stream of n short alignments whose last record's aux is padded until len(stream) % 16 == rem, the oracle's
+    records): computed once, shared"""
+    if (n, rem) not in _EDGES:
+        recs = [bamgen.record(b"STAGS_CELL=ACGTAC_UMI=GT%d_SAMPLE=_ETAGS_r%d" % (i % 7, i), bamgen.aux_int(b"XI", i & 127), tid=i % 3 - 1,
+                              seq_len=i % 5) for i in range(n - 1)]
+        head = bamgen.header(tuple((nm, 1000) for nm in EDGE_NAMES)) + b"".join(recs)
+        for pad in range(16):
+            stream = head + bamgen.record(b"STAGS_CELL=AC_UMI=G_SAMPLE=T_ETAGS_last", bamgen.aux_z(b"XA", b"x" * pad), tid=1, seq_len=3)
+            if len(stream) % 16 == rem:
+                break
+        assert len(stream) % 16 == rem
+        _EDGES[(n, rem)] = (stream, oracle_records(stream, tx_tag=True)[0])
+    return _EDGES[(n, rem)]
+
+
+@pytest.mark.parametrize("resident", [False, True], ids=["host", "device+5"])
+@pytest.mark.parametrize("rem", [0, 1, 15])
+@pytest.mark.parametrize("n", [1, 64, 65])
+def test_staging_edges(ctx, n, rem, resident):
+    """the tile's span ends with the stream, 0, 1 and 15 bytes behind a 16-byte boundary: the last unit of the staging
+    loop, read byte by byte; one tile, a full one, a full one and one alignment"""
+    stream, want = edge_case(n, rem)
+    if resident:
+        import torch
+        t = torch.zeros(len(stream) + 64, dtype=torch.uint8, device="cuda:0")
+        t[5:5 + len(stream)] = torch.frombuffer(bytearray(stream), dtype=torch.uint8).to("cuda:0")
+        got = ctx.bam_add_tags(t.data_ptr() + 5, tx_tag=True, targets=EDGE_NAMES, offsets=record_offsets(stream), nbytes=len(stream))
+    else:
+        got = ctx.bam_add_tags(stream, tx_tag=True, targets=EDGE_NAMES)
+    assert got["code"] == 0 and got["n_alignments"] == n and got["n_tagged"] == n
+    assert got["records"] == want
+
+
+def test_bam2fastq_does_not_disturb_the_last_result_nor_the_reverse(ctx):
+    """fqg_bam_add_tags and fqg_bam2fastq share their scratch memory, not their results: each _output call gives what
+    the last call of ITS kind produced, whatever ran in between"""
+    import ctypes as C
+
+    from fastq_utils_amd import abi
+    from tests import b2f_gen
+    from tests import bam2fastq_oracle as b2f
+    L = abi.load()
+    tags_stream, want_tags = edge_case(65, 1)
+    rng = np.random.default_rng(3)
+    fq_stream = b2f_gen.stream([b2f_gen.fastq2bam_record(rng, i, sample=True) for i in range(200)])
+    want_fq = b2f.convert(fq_stream)
+
+    def tags_output(n):
+        dst = C.create_string_buffer(max(1, n))
+        ctx._check(L.fqg_bam_add_tags_output(ctx.h, dst, n))
+        return dst.raw[:n]
+
+    def fq_output(s, n):
+        dst = C.create_string_buffer(max(1, n))
+        ctx._check(L.fqg_bam2fastq_output(ctx.h, s, dst, n))
+        return dst.raw[:n]
+
+    a = ctx.bam_add_tags(tags_stream, tx_tag=True, targets=EDGE_NAMES, want_output=False)
+    b = ctx.bam2fastq(fq_stream)
+    assert a["code"] == 0 and b["code"] == 0 and any(b["out_bytes"])
+    assert tags_output(a["out_bytes"]) == want_tags
+    assert ctx.bam_add_tags(tags_stream, tx_tag=True, targets=EDGE_NAMES)["records"] == want_tags
+    for s in range(6):
+        assert fq_output(s, b["out_bytes"][s]) == bytes(want_fq["streams"][s]), s
 
 
 def test_names_the_reference_has_no_defined_output_for(ctx):
