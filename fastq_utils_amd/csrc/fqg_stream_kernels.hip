@@ -30,6 +30,7 @@
 // what must be exact are the line index, the quality range (hull of the boot range, of verified
 // per-chunk ranges and of redone chunks) and the image flags that force the two-pass / exact path.
 #include "fqg_device.h"
+#include "fqg_type_spans.h"
 
 namespace fqg {
 
@@ -166,27 +167,6 @@ __device__ __forceinline__ void queue_suspect(const StreamOut& o, CallState* cs,
 constexpr int kHalves = 2;
 constexpr int kLaneBytes = 32;
 constexpr int kHalfBytes = kWave * kLaneBytes;  // 2 KiB
-
-__device__ __forceinline__ uint32_t prefix_xor32(uint32_t x) {
-  x ^= x << 1;
-  x ^= x << 2;
-  x ^= x << 4;
-  x ^= x << 8;
-  x ^= x << 16;
-  return x;
-}
-
-// masks of the bytes on sequence (M1) and quality (M3) lines; t0 = type of the first byte
-__device__ __forceinline__ void type_masks32(uint32_t nl, uint32_t t0, uint32_t& M1, uint32_t& M3) {
-  const uint32_t e = nl << 1;
-  const uint32_t P = prefix_xor32(e);        // bit 0 of the running newline count
-  const uint32_t Q = prefix_xor32(e & ~P);   // bit 1 (carry when bit 0 wraps)
-  const uint32_t a0 = 0u - (t0 & 1u), a1 = 0u - ((t0 >> 1) & 1u);
-  const uint32_t L = P ^ a0;
-  const uint32_t Hh = Q ^ a1 ^ (P & a0);
-  M1 = ~Hh & L;
-  M3 = Hh & L;
-}
 
 struct Piece32 {
   uint4 a, b;  // bytes 0..15, 16..31
@@ -390,7 +370,19 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
         found = true;
       }
     }
+    // The type masks are spans between a lane's first three newlines (fqg_type_spans.h).  A chunk with a lane of four or
+    // more newlines in 32 bytes - reads under 25 bases - makes no class tests here and queues nothing: it stays
+    // kInfoUnknown, and k_stream_chunks sends it to the redo list, where the two-pass kernel repeats the checks exactly.
+    // (`found` and t0 stand: the name capture below does not use the masks.)
+    uint32_t M1[kHalves], M3[kHalves];
+    bool dense = false;
     if (found) {
+      uint32_t over = 0;
+#pragma unroll
+      for (int k = 0; k < kHalves; ++k) over |= type_spans32(nl[k], t0 + ex[k], M1[k], M3[k]);  // (the newline bytes are in neither mask)
+      dense = __ballot(over != 0) != 0;
+    }
+    if (found && !dense) {
       info = t0;
       uint32_t lo = boot_lo, hi = boot_hi;
       if (lo > hi || lo > 127u) {
@@ -405,19 +397,17 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
       bool any_viol = false;
 #pragma unroll
       for (int k = 0; k < kHalves; ++k) {
-        uint32_t M1, M3;
-        type_masks32(nl[k], t0 + ex[k], M1, M3);
         const uint4 &a = v[k].a, &b = v[k].b;
         const uint32_t inv = pack_marks16(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w)) |
                              (pack_marks16(not_acgtn7(b.x), not_acgtn7(b.y), not_acgtn7(b.z), not_acgtn7(b.w)) << 16);
-        const uint32_t bad = (ABL & 8u) ? 0u : inv & M1 & ~nl[k];
+        const uint32_t bad = (ABL & 8u) ? 0u : inv & M1[k];
         if (bad) queue_suspect(o, cs, wb + (uint64_t)k * kHalfBytes + (uint32_t)__builtin_ctz(bad));
         const uint32_t okq =
             pack_marks16(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
                          in_range7a(a.w, lo_add, hihb, khv)) |
             (pack_marks16(in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv), in_range7a(b.z, lo_add, hihb, khv),
                           in_range7a(b.w, lo_add, hihb, khv)) << 16);
-        const uint32_t qm = (ABL & 16u) ? 0u : M3 & ~nl[k];
+        const uint32_t qm = (ABL & 16u) ? 0u : M3[k];
         if (__ballot((qm & ~okq) != 0)) {  // rare: exact range of this slice's quality bytes
           any_viol = true;
           qrange_accum(a, qm & 0xFFFFu, q);
