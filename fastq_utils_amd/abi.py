@@ -35,7 +35,7 @@ EXPORTS = [
     "fqg_frame_retain", "fqg_frame_release", "fqg_frame_n_records", "fqg_frame_make_current", "fqg_index_create",
     "fqg_index_destroy", "fqg_index_insert_unique", "fqg_index_match_delete", "fqg_index_probe_delete",
     "fqg_index_alive", "fqg_index_n_frames", "fqg_index_frame", "fqg_index_names_captured", "fqg_index_expect_lookups", "fqg_records_gather",
-    "fqg_records_gather_output", "fqg_names_compare",
+    "fqg_records_gather_output", "fqg_records_split", "fqg_records_split_output", "fqg_records_split_info", "fqg_names_compare",
     "fqg_barcodes_transform", "fqg_barcodes_output", "fqg_barcodes_output_begin", "fqg_barcodes_output_wait", "fqg_records_filter", "fqg_records_filter_output",
     "fqg_whitelist_create", "fqg_whitelist_destroy", "fqg_barcodes_whitelist",
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
@@ -249,6 +249,9 @@ def load():
     L.fqg_index_names_captured.restype = u64
     L.fqg_records_gather.argtypes = [vp, vp, C.POINTER(u64), u64, C.POINTER(u64)]
     L.fqg_records_gather_output.argtypes = [vp, vp, u64]
+    L.fqg_records_split.argtypes = [vp, vp, u64, u64, C.POINTER(u64)]
+    L.fqg_records_split_output.argtypes = [vp, C.c_int, vp, u64]
+    L.fqg_records_split_info.argtypes = [vp, C.POINTER(u64)]
     L.fqg_index_frame.argtypes = [vp, u64]
     L.fqg_index_frame.restype = vp
     L.fqg_frame_make_current.argtypes = [vp, vp]
@@ -781,6 +784,28 @@ class Context:
         dst = C.create_string_buffer(max(1, nb.value))
         self._check(load().fqg_records_gather_output(self.h, dst, nb.value))
         return nb.value, dst.raw[:nb.value]
+
+    def records_split(self, frame_handle, first_record, n_records, want_output=False):
+        """fqg_records_split: records first_record + 2k of a frame to stream 0, first_record + 2k + 1 to stream 1; returns
+        the two byte counts and, with want_output, the two texts"""
+        nb = (C.c_uint64 * 2)()
+        h = frame_handle.h if hasattr(frame_handle, "h") else frame_handle
+        self._check(load().fqg_records_split(self.h, h, first_record, n_records, nb))
+        sizes = (int(nb[0]), int(nb[1]))
+        if not want_output:
+            return sizes, None
+        return sizes, tuple(self.records_split_output(w, sizes[w]) for w in (0, 1))
+
+    def records_split_output(self, which, nbytes):
+        dst = C.create_string_buffer(max(1, nbytes))
+        self._check(load().fqg_records_split_output(self.h, which, dst, nbytes))
+        return dst.raw[:nbytes]
+
+    def records_split_info(self):
+        """how the last records_split ran: tiles, tiles on the direct path, wavefronts of the tile kernel, records per tile"""
+        v = (C.c_uint64 * 4)()
+        self._check(load().fqg_records_split_info(self.h, v))
+        return {"tiles": int(v[0]), "big_tiles": int(v[1]), "grid": int(v[2]), "T": int(v[3])}
 
     def frame_make_current(self, frame_handle):
         h = frame_handle.h if hasattr(frame_handle, "h") else frame_handle

@@ -24,6 +24,7 @@
 #include "fqg_barcode_kernels.hip"
 #include "fqg_census_kernels.hip"
 #include "fqg_filter_kernels.hip"
+#include "fqg_split_kernels.hip"
 #include "fqg_umi_kernels.hip"
 #include "fqg_umi_rl_kernels.hip"
 #include "fqg_umi_cell_kernels.hip"
@@ -151,6 +152,7 @@ struct fqg_ctx {
   BcCall* d_bcall = nullptr;
   BcCall* h_bcall = nullptr;  // pinned
   uint64_t bc_out_bytes[3] = {0, 0, 0};
+  uint64_t split_info[4] = {0, 0, 0, 0};  // of the last fqg_records_split: tiles, tiles on the direct path, emit grid, T
   DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
   DevBuf bt_tables, bt_call, bt_out;  // fqg_bam_add_tags
   uint64_t bt_out_bytes = 0;
@@ -2838,5 +2840,6 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 #include "fqg_fp_abi.inc"
 #include "fqg_bamtags_abi.inc"
 #include "fqg_bam2fastq_abi.inc"
+#include "fqg_split_abi.inc"
 
 }  // extern "C"

@@ -1,0 +1,129 @@
+// fqg_split_abi.inc - fqg_records_split / fqg_records_split_output / fqg_records_split_info (include/fqg.h), included by
+// fqg_abi.hip
+
+extern "C++" {
+namespace {
+// FQGPU_SPLIT_T: records per tile (even, 2..64; measurement and tests only - results do not depend on it)
+unsigned split_env_T() {
+  static const unsigned v = [] {
+    const char* e = getenv("FQGPU_SPLIT_T");
+    const long t = e ? atol(e) : 0;
+    return (unsigned)(t >= 2 && t <= 64 ? t & ~1l : 0);
+  }();
+  return v;
+}
+}  // namespace
+}  // extern "C++"
+
+int fqg_records_split(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record, uint64_t n_rec, uint64_t out_bytes[2]) {
+  if (!c || !frame || !out_bytes) return FQG_ERR_ARG;
+  if (c->out_pending) {  // (a copy of the previous output is still on its way: this call writes the same buffers)
+    const int rcw = fqg_barcodes_output_wait(c);
+    if (rcw) return rcw;
+  }
+  out_bytes[0] = out_bytes[1] = 0;
+  c->bc_out_bytes[0] = c->bc_out_bytes[1] = c->bc_out_bytes[2] = 0;
+  c->split_info[0] = c->split_info[1] = c->split_info[2] = c->split_info[3] = 0;
+  if (n_rec & 1) return fail(c, FQG_ERR_ARG, "fqg_records_split: an odd number of records");
+  if (first_record > frame->fv.n_records || n_rec > frame->fv.n_records - first_record)
+    return fail(c, FQG_ERR_ARG, "fqg_records_split: records beyond the frame");
+  if (!n_rec) return 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t np = n_rec / 2, nb = (np + kScan64Span - 1) / kScan64Span;
+  SplitArgs A;
+  memset(&A, 0, sizeof(A));
+  A.fv = frame->fv;
+  A.first = first_record;
+  A.n_rec = n_rec;
+  A.has_nul = (frame->flags & kFlagNul) ? 1 : 0;  // lines are C strings then (bc_clip_nul)
+  {
+    // the LDS budget of a wavefront is the record filters' (bc_tile_for, FQGPU_BC_LDS); it holds the tile's span and,
+    // behind it, the two images - together the span's bytes again
+    BcParams F;
+    memset(&F, 0, sizeof(F));
+    F.f[1].fv = frame->fv;
+    F.f[1].step = 1;
+    F.f[1].present = 1;
+    F.n_inputs = 1;
+    F.emit[1] = 1;
+    const BcTile tc = bc_tile_for(F, 24576u);
+    const unsigned budget = tc.in_cap + tc.out_cap;
+    const double rec = (double)frame->fv.nbytes / (double)frame->fv.n_records;
+    unsigned T = (unsigned)std::max(2.0, std::min(((double)budget - 160.0) / (2.12 * rec + 2.0), 64.0)) & ~1u;
+    if (split_env_T()) T = split_env_T();
+    A.T = T;
+    A.in_cap = ((unsigned)(1.06 * rec * T + 96.0) + 15u) & ~15u;
+    if (2u * A.in_cap + kSplitOutSlack > budget) A.in_cap = ((budget - kSplitOutSlack) / 2) & ~15u;
+    A.out_cap = std::min(A.in_cap + kSplitOutSlack, budget - A.in_cap) & ~15u;
+  }
+  const uint64_t n_tiles = (n_rec + A.T - 1) / A.T;
+  int rc;
+  for (int s = 0; s < 2; ++s) {
+    if ((rc = ensure(c, c->bc_len[1 + s], np * 4))) return rc;
+    if ((rc = ensure(c, c->bc_off[1 + s], np * 8))) return rc;
+    if ((rc = ensure(c, c->bc_sum[1 + s], nb * 8 + 32))) return rc;
+    A.len[s] = (uint32_t*)c->bc_len[1 + s].p;
+    A.local[s] = (unsigned long long*)c->bc_off[1 + s].p;
+    A.sums[s] = (unsigned long long*)c->bc_sum[1 + s].p;
+  }
+  if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
+  A.total = (unsigned long long*)c->bc_sum[1].p + nb;  // (two words behind stream 0's span sums)
+  A.tile_big = (uint8_t*)c->bc_tile_big.p;
+  A.n_big = &c->d_bcall->big;
+  BcCall z;
+  memset(&z, 0, sizeof(z));
+  *c->h_bcall = z;
+  HIP_TRY(c, hipMemcpyAsync(c->d_bcall, c->h_bcall, sizeof(BcCall), hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, "k_split_plan");
+    const unsigned grid = (unsigned)std::min<uint64_t>((n_rec + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 32);
+    hipLaunchKernelGGL(k_split_lens, dim3(grid), dim3(kBlock), 0, c->stream, A);
+    hipLaunchKernelGGL(k_split_scan_a, dim3((unsigned)nb, 2), dim3(kBlock), 0, c->stream, A);
+    hipLaunchKernelGGL(k_split_scan_b, dim3(1, 2), dim3(kBlock), 0, c->stream, A, nb);
+    hipLaunchKernelGGL(k_split_tile_flags, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[2], A.total, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  const uint64_t total[2] = {c->h_scalar[2], c->h_scalar[3]};
+  const uint64_t n_big = c->h_bcall->big;
+  for (int s = 0; s < 2; ++s) {
+    if ((rc = ensure(c, c->bc_out[1 + s], total[s] + 64))) return rc;
+    A.out[s] = (uint8_t*)c->bc_out[1 + s].p;
+  }
+  unsigned grid_t = 0;
+  {
+    ProfScope ps(c, "k_split_emit");
+    if (n_big < n_tiles) {
+      const unsigned lds = A.in_cap + A.out_cap;
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_split_emit_tile, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+      grid_t = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)per_cu * (uint64_t)c->cu_count);
+      hipLaunchKernelGGL(k_split_emit_tile, dim3(grid_t), dim3(kWave), lds, c->stream, A);
+    }
+    if (n_big) {
+      const unsigned grid_e = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 3) / 4, (uint64_t)c->cu_count * 16));
+      hipLaunchKernelGGL(k_split_emit_direct, dim3(grid_e), dim3(kBlock), 0, c->stream, A);
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  for (int s = 0; s < 2; ++s) c->bc_out_bytes[1 + s] = out_bytes[s] = total[s];
+  c->split_info[0] = n_tiles;
+  c->split_info[1] = n_big;
+  c->split_info[2] = grid_t;
+  c->split_info[3] = A.T;
+  return 0;
+}
+
+int fqg_records_split_output(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
+  if (!c || which < 0 || which > 1) return FQG_ERR_ARG;
+  return fqg_barcodes_output(c, 1 + which, host_dst, nbytes);
+}
+
+int fqg_records_split_info(const fqg_ctx* c, uint64_t info[4]) {
+  if (!c || !info) return FQG_ERR_ARG;
+  for (int i = 0; i < 4; ++i) info[i] = c->split_info[i];
+  return 0;
+}

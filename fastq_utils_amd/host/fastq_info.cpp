@@ -17,6 +17,7 @@
 #include <chrono>
 
 #include "fq_common.h"
+#include "fq_interleaved.h"
 #include "fq_multi.h"
 #include "fq_names_multi.h"
 #include "fq_ordered.h"
@@ -556,58 +557,9 @@ void run_interleaved(const char* path, Stats& S) {
     LIB(fqg_names_compare(g_ctx, fr, &pr.st, nullptr, nullptr, &cr));
     fqg_frame_release(fr);
   }
-  // order inside pair k: read m1, read m2, name m1, name m2, names equal, validate m1, validate m2
-  uint64_t best_pair = ~0ull;
-  int best_stage = 99;
-  auto offer = [&](uint64_t pair, int stage) {
-    if (pair < best_pair || (pair == best_pair && stage < best_stage)) {
-      best_pair = pair;
-      best_stage = stage;
-    }
-  };
-  const bool trunc = r.code == FQG_E_TRUNCATED || r.code == FQG_E_LINE_TOO_LONG;
-  uint64_t trunc_rec = trunc ? r.record : ~0ull;
-  if (trunc) offer(r.record / 2, r.record % 2 == 0 ? 0 : 2);
-  else if (r.code == FQG_E_HDR1_AT) offer(r.record / 2, r.record % 2 == 0 ? 3 : 4);
-  else if (r.code) offer(r.record / 2, r.record % 2 == 0 ? 6 : 7);
-  if (r.tail_lines > 0) {  // an incomplete last record, even when an earlier record has a finding
-    offer(n / 2, n % 2 == 0 ? 0 : 2);
-    if (trunc_rec == ~0ull) trunc_rec = n;
-  } else if (n % 2 == 1) {
-    offer(n / 2, 1);  // a first mate without a second one
-  }
-  if (cr.code == FQG_E_WRONG_HEADER) {
-    const RecordText t = locate_record(in.data(), in.size(), cr.record);
-    offer(cr.record / 2, (!t.l[0].empty() && t.l[0][0] != '@') ? 3 : 4);
-  }
-  if (cr.code == FQG_E_UNPAIRED) offer(cr.record / 2, 5);
-  // format lines: printed by the first fastq_get_readname call, i.e. for mate 1 of pair 0
-  if (n >= 2 && !(best_pair == 0 && best_stage <= 3)) print_probe(pr);
-  if (best_pair != ~0ull) {
-    ticker(1, best_pair, 50000, 2);
-    const uint64_t k = best_pair;
-    const unsigned long cline_pair = 4 * (2 * k + 2);
-    switch (best_stage) {
-      case 0:
-      case 2:
-        if (r.code == FQG_E_LINE_TOO_LONG) fail_too_long(path, r.record);
-        fail_truncated(path, 4 * (best_pair * 2 + (best_stage == 2 ? 1 : 0)));
-      case 1:
-        FQ_PRINT_ERROR("Error in file %s: line %lu: file truncated?", path, (unsigned long)(4 * n));
-        fqhost::leave(kExitFormat);
-      case 3:
-        fail_wrong_header(path, cline_pair, locate_record(in.data(), in.size(), 2 * k).l[0]);
-      case 4:
-        fail_wrong_header(path, cline_pair, locate_record(in.data(), in.size(), 2 * k + 1).l[0]);
-      case 5:
-        FQ_PRINT_ERROR("Error in file %s: line %lu: unpaired read - %s", path, cline_pair,
-                       canonical_name(locate_record(in.data(), in.size(), 2 * k).l[0], pr.st).c_str());
-        fqhost::leave(kExitFormat);
-      default:
-        print_validation_error(path, cline_pair, r, locate_record(in.data(), in.size(), r.record));
-        fqhost::leave(kExitFormat);
-    }
-  }
+  // which finding of which pair comes first: fq_interleaved.h
+  bool probe_pending = true;
+  interleaved_findings(InterleavedImage{path, in.data(), in.size(), n, true, 0}, r, cr, pr, probe_pending);
   ticker(1, n / 2, 50000, 2);
   printf("\n");
   fqg_file_stats fs;

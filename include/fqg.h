@@ -453,6 +453,19 @@ int fqg_records_filter_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
 int fqg_records_gather(fqg_ctx *ctx, const fqg_frame *frame, const uint64_t *records, uint64_t n, uint64_t *out_bytes);
 int fqg_records_gather_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
 
+/* ---- de-interleave (fastq_split_interleaved) ------------------------------------------------------
+ * The output side of fastq_split_interleaved (src/fastq_split_interleaved.c:83-87): records first_record + 2k of a
+ * retained frame go to stream 0 and records first_record + 2k + 1 to stream 1, both in frame order, each written as
+ * fastq_write_entry writes it (src/fastq.c:265-272: in an image with NUL bytes a line ends at its first NUL; a last
+ * line without a newline stays without one).  n_records must be even and the range inside the frame (FQG_ERR_ARG
+ * otherwise); 0 records give 0 bytes twice.  The text stays on the device until fqg_records_split_output (which: 0 or
+ * 1) copies it.  fqg_records_split_info tells how the last call ran: info[0] tiles, info[1] tiles that took the direct
+ * path (they do not fit LDS, or the image holds NUL bytes), info[2] wavefronts of the tile kernel, info[3] records per
+ * tile. */
+int fqg_records_split(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_record, uint64_t n_records, uint64_t out_bytes[2]);
+int fqg_records_split_output(fqg_ctx *ctx, int which, void *host_dst, uint64_t nbytes);
+int fqg_records_split_info(const fqg_ctx *ctx, uint64_t info[4]);
+
 /* ---- UMI counting (bam_umi_count) ---------------------------------------------------------------
  * Replaces the alignment loop of bam_umi_count (src/bam_umi_count.c:942-1060: filters, aux tags,
  * char2uint_64 :364-382, the label maps :143-260, process_entry :444-509) and the output decisions

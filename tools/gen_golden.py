@@ -776,6 +776,84 @@ def gen_bam2fastq():
     print("bam2fastq invocations:", len(out), "by exit status:", by)
 
 
+# ---- fastq_split_interleaved (run_tests.sh:31-40) -------------------------------------------------------------------
+def build_ref_split_interleaved(tmp):
+    """the reference's fastq_split_interleaved, compiled as oracle/Makefile compiles the other FASTQ programs, into `tmp`
+    (outside the repository)"""
+    exe = os.path.join(tmp, "fastq_split_interleaved")
+    src = os.path.join(REF, "src")
+    subprocess.run(["gcc", "-O3", "-w", "-I" + src, "-o", exe, os.path.join(src, "fastq_split_interleaved.c"), os.path.join(src, "fastq.c"),
+                    os.path.join(src, "hash.c"), "-lz"], check=True)
+    return exe
+
+
+def split_interleaved_jobs(small):
+    """argument lists; OUT stands for the output prefix, GEN/<name> for a large seeded input made next to it"""
+    d = lambda n: "data/" + n
+    jobs = [[d("casava.1.8i.fastq.gz"), "OUT"], [d("casava.1.8i_e1.fastq.gz"), "OUT"],           # run_tests.sh:31-33
+            [d("casava.1.8i.fastq.gz"), "a1", "a2"], [], [d("one.fastq.gz"), "OUT"],               # :34-36
+            [d("test_e1.fastq.gz")], [d("test_21_2.fastq.gz"), "OUT"], [d("inter.fastq.gz"), "OUT"]]  # :37-40
+    seen = {tuple(j) for j in jobs}
+    for n in sorted(os.listdir(DATA)):  # every fixture: most of them fail, and every finding's wording is pinned
+        if n.endswith(".fastq.gz") and (d(n), "OUT") not in seen and n not in small:
+            jobs.append([d(n), "OUT"])
+    jobs += [[d(n), "OUT"] for n in sorted(small)]
+    jobs += [[d("no_such_file.fastq.gz"), "OUT"], [d("empty.fastq"), "OUT"], [d("inter.fastq.gz"), "no/such/folder/x"],
+             [d("inter.fastq.gz"), "OUT", "extra", "more"]]
+    jobs += [["GEN/big_clean.fastq", "OUT"], ["GEN/big_mismatch.fastq", "OUT"], ["GEN/big_trunc.fastq", "OUT"]]
+    return jobs
+
+
+def gen_split_interleaved():
+    import hashlib
+    import tempfile
+
+    sys.path.insert(0, REPO)
+    from tests import split_gen
+    small = {}
+    for n, raw in split_gen.small_files().items():
+        small[n + ".fastq.gz"] = raw
+        with open(os.path.join(DATA, n + ".fastq.gz"), "wb") as f:
+            f.write(gzip.compress(raw, 9, mtime=0))
+    big = split_gen.big_files()
+    out = []
+    with tempfile.TemporaryDirectory() as build:
+        exe = build_ref_split_interleaved(build)
+        for args in split_interleaved_jobs(small):
+            with tempfile.TemporaryDirectory(dir=GOLD) as tmp:
+                rel = os.path.relpath(tmp, GOLD)
+                real = []
+                for a in args:
+                    if a.startswith("GEN/"):
+                        with open(os.path.join(tmp, a[4:]), "wb") as f:
+                            f.write(big[a[4:]])
+                        a = rel + "/" + a[4:]
+                    real.append(rel + "/o" if a == "OUT" else a)
+                before = set(os.listdir(tmp))
+                p = subprocess.run(["fastq_split_interleaved"] + real, executable=exe, cwd=GOLD, capture_output=True, timeout=600,
+                                   stdin=subprocess.DEVNULL)
+                entry = {"args": args, "exit": p.returncode, "stdout": p.stdout.decode("latin-1"),
+                         "stderr": p.stderr.decode("latin-1").replace(rel + "/", "SCRATCH/"), "files": {}}
+                for n in sorted(set(os.listdir(tmp)) - before):
+                    if p.returncode != 0:   # (left through exit(), never closed: what they hold is not defined)
+                        entry["files"][n] = None
+                        continue
+                    data = gzip.decompress(open(os.path.join(tmp, n), "rb").read())
+                    entry["files"][n] = {"bytes": len(data), "sha256": hashlib.sha256(data).hexdigest()}
+                    if len(data) < 4096:
+                        entry["files"][n]["content"] = data.decode("latin-1")
+                out.append(entry)
+    for n in ("a1_1.fastq.gz", "a1_2.fastq.gz"):  # (nothing is written for a wrong argc; should that ever change)
+        if os.path.exists(os.path.join(GOLD, n)):
+            os.remove(os.path.join(GOLD, n))
+    with open(os.path.join(GOLD, "split_interleaved.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    by = {}
+    for o in out:
+        by[o["exit"]] = by.get(o["exit"], 0) + 1
+    print("fastq_split_interleaved invocations:", len(out), "by exit status:", by)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("all", "fastq_info"):
@@ -792,3 +870,5 @@ if __name__ == "__main__":
         gen_bam_tags()
     if which in ("all", "bam2fastq"):
         gen_bam2fastq()
+    if which in ("all", "split_interleaved"):
+        gen_split_interleaved()
