@@ -43,6 +43,16 @@ struct DevBuf {
   size_t cap = 0;
 };
 
+// The text a call produced, on the device until an `_output` call copies it (fqg_text_out.inc): up to FQG_B2F_STREAMS
+// streams behind each other in one block.
+struct OutText {
+  DevBuf buf;
+  uint64_t at[FQG_B2F_STREAMS] = {}, bytes[FQG_B2F_STREAMS] = {};  // per stream: where it starts, what was produced
+  hipStream_t copy_stream = nullptr;  // text_copy_begin: device-to-host copies beside the next piece's upload
+  hipEvent_t ready = nullptr;         // ... recorded on the context's stream where the output was produced
+  bool pending = false;
+};
+
 struct ProfEvent {
   int slot;
   hipEvent_t a, b;
@@ -89,9 +99,6 @@ inline int measure_int(const char* name) {
 struct fqg_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
-  hipStream_t out_stream = nullptr;   // fqg_barcodes_output_begin: device-to-host copies beside the next piece's upload
-  hipEvent_t out_ready = nullptr;     // ... recorded on `stream` where the output was produced
-  bool out_pending = false;
   hipStream_t stream = nullptr;
   std::string err;
   int cu_count = 256;
@@ -148,16 +155,16 @@ struct fqg_ctx {
   bool frame_img_owned = false;  // the frame's image lives in `image` (host input), not with the caller
   bool frame_borrowed = false;   // the current frame is a retained frame made current again (fqg_frame_make_current)
   uint32_t frame_flags = 0;      // kFlagNul / kFlagCr of the framed image
-  DevBuf bc_status, bc_len[3], bc_off[3], bc_sum[3], bc_out[3], bc_tile_big;
+  DevBuf bc_status, bc_len[3], bc_off[3], bc_sum[3], bc_tile_big;
   BcCall* d_bcall = nullptr;
   BcCall* h_bcall = nullptr;  // pinned
-  uint64_t bc_out_bytes[3] = {0, 0, 0};
+  // the text of the last transform (streams 0..2), filter or gather (1), split (1, 2); of the last fqg_bam_add_tags;
+  // of the last fqg_bam2fastq - three stores: the text of a BAM call survives a FASTQ-side call and the other way round
+  OutText bc_text, bt_text, b2f_text;
   uint64_t split_info[4] = {0, 0, 0, 0};  // of the last fqg_records_split: tiles, tiles on the direct path, emit grid, T
   DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
-  DevBuf bt_tables, bt_call, bt_out;  // fqg_bam_add_tags
-  uint64_t bt_out_bytes = 0;
-  DevBuf b2f_call, b2f_out;  // fqg_bam2fastq
-  uint64_t b2f_out_at[6] = {0, 0, 0, 0, 0, 0}, b2f_out_bytes[6] = {0, 0, 0, 0, 0, 0};
+  DevBuf bt_tables, bt_call;  // fqg_bam_add_tags
+  DevBuf b2f_call;            // fqg_bam2fastq
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
 
@@ -278,6 +285,8 @@ struct ProfScope {
 };
 
 void umi_drop_state(fqg_ctx* c);  // fqg_umi_abi.inc
+
+#include "fqg_text_out.inc"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the FUNCTION ON A DEVICE, not to a context: two contexts of one
 // device (FQGPU_DEVICES=0,0,0) share it.  The largest size asked for so far is kept per (device, kernel) for the whole
@@ -459,14 +468,13 @@ void fqg_close(fqg_ctx* c) {
   release(c->umi_entries[1]);
   release(c->bc_status);
   release(c->bc_tile_big);
-  for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call, &c->bt_out,
-                    &c->b2f_call, &c->b2f_out})
+  for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call,
+                    &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
     release(c->bc_off[i]);
     release(c->bc_sum[i]);
-    release(c->bc_out[i]);
   }
   if (c->d_bcall) (void)hipFree(c->d_bcall);
   if (c->h_bcall) (void)hipHostFree(c->h_bcall);
@@ -475,11 +483,11 @@ void fqg_close(fqg_ctx* c) {
   if (c->d_cs) (void)hipFree(c->d_cs);
   if (c->h_cs) (void)hipHostFree(c->h_cs);
   if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-  if (c->out_stream) {
-    (void)hipStreamSynchronize(c->out_stream);
-    (void)hipStreamDestroy(c->out_stream);
+  if (c->bc_text.copy_stream) {
+    (void)hipStreamSynchronize(c->bc_text.copy_stream);
+    (void)hipStreamDestroy(c->bc_text.copy_stream);
   }
-  if (c->out_ready) (void)hipEventDestroy(c->out_ready);
+  if (c->bc_text.ready) (void)hipEventDestroy(c->bc_text.ready);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -518,10 +526,7 @@ void fqg_host_free(fqg_ctx* c, void* p) {
 int fqg_release_scratch(fqg_ctx* c) {
   if (!c) return FQG_ERR_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (c->out_pending) {
-    const int rcw = fqg_barcodes_output_wait(c);
-    if (rcw) return rcw;
-  }
+  NEED(text_wait(c, c->bc_text));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (DevBuf* b : {&c->image, &c->tile_counts, &c->tile_local, &c->span_sums, &c->line_end, &c->records, &c->suspect, &c->list,
                     &c->stage, &c->cinfo, &c->queue, &c->redo, &c->lines_slow, &c->build_keys[0], &c->build_keys[1],
@@ -532,9 +537,8 @@ int fqg_release_scratch(fqg_ctx* c) {
     release(c->bc_len[i]);
     release(c->bc_off[i]);
     release(c->bc_sum[i]);
-    release(c->bc_out[i]);
-    c->bc_out_bytes[i] = 0;
   }
+  text_release(c->bc_text);  // (the BAM calls' text stays)
   c->frame_valid = false;
   c->frame_borrowed = false;
   c->lazy.pending = false;
@@ -2164,12 +2168,8 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
                            const uint64_t first_record[6], const fqg_barcode_params* bp, uint64_t n_iter,
                            uint64_t first_read_number, fqg_barcode_result* out) {
   if (!c || !frames || !states || !first_record || !bp || !out) return FQG_ERR_ARG;
-  if (c->out_pending) {  // (a copy of the previous output is still on its way: this call writes the same buffers)
-    const int rcw = fqg_barcodes_output_wait(c);
-    if (rcw) return rcw;
-  }
+  NEED(text_begin(c, c->bc_text));
   memset(out, 0, sizeof(*out));
-  c->bc_out_bytes[0] = c->bc_out_bytes[1] = c->bc_out_bytes[2] = 0;
   c->bc_status_valid = 0;
   HIP_TRY(c, hipSetDevice(c->device));
   BcParams P;
@@ -2179,37 +2179,25 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
   if (!n_iter) return 0;
 
   if ((rc = ensure(c, c->bc_status, n_iter))) return rc;
-  const uint64_t nb = (n_iter + kScan64Span - 1) / kScan64Span;
   for (int i = 0; i < 3; ++i) {
     if ((rc = ensure(c, c->bc_len[i], n_iter * 4))) return rc;
     if ((rc = ensure(c, c->bc_off[i], n_iter * 8))) return rc;
-    if ((rc = ensure(c, c->bc_sum[i], nb * 8))) return rc;
+    if ((rc = ensure(c, c->bc_sum[i], scan64_spans(n_iter) * 8))) return rc;
   }
-  BcCall z;
-  memset(&z, 0, sizeof(z));
-  z.first_finding = z.first_discard = ~0ull;
-  *c->h_bcall = z;
-  HIP_TRY(c, hipMemcpyAsync(c->d_bcall, c->h_bcall, sizeof(BcCall), hipMemcpyHostToDevice, c->stream));
+  NEED(bcall_reset(c, ~0ull));
   const BcTile tc = bc_tile_for(P);
   int file_mask = 0;  // the usual sets of inputs have kernels of their own (bc_has)
   for (int x = 1; x < kBcFiles; ++x)
     if (P.f[x].present) file_mask |= 1 << x;
   const uint64_t n_tiles = (n_iter + tc.T - 1) / tc.T;
   if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
-  // persistent grids: exactly the wavefronts that are resident at once (tiles are dealt round-robin,
-  // so a wavefront that starts late would do its whole share after the others have finished)
-  auto resident = [&](const void* kernel, unsigned lds) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    return (unsigned)per_cu * (unsigned)c->cu_count;
-  };
   {
     ProfScope ps(c, "k_bc_plan");
 #define FQG_PLAN_TILE(MASK)                                                                                       \
   do {                                                                                                            \
     const unsigned plan_lds = tc.plan_cap;                                                                        \
     const uint64_t plan_tiles = (n_tiles + tc.plan_m - 1) / tc.plan_m;                                            \
-    const unsigned grid = (unsigned)std::min<uint64_t>(plan_tiles, resident((const void*)k_bc_plan_tile<MASK>, plan_lds)); \
+    const unsigned grid = (unsigned)std::min<uint64_t>(plan_tiles, resident_waves(c, (const void*)k_bc_plan_tile<MASK>, plan_lds)); \
     hipLaunchKernelGGL(k_bc_plan_tile<MASK>, dim3(grid), dim3(kWave), plan_lds, c->stream, P, tc, n_iter,          \
                        (uint8_t*)c->bc_status.p, (uint32_t*)c->bc_len[0].p, (uint32_t*)c->bc_len[1].p,            \
                        (uint32_t*)c->bc_len[2].p, (uint8_t*)c->bc_tile_big.p, c->d_bcall);                         \
@@ -2231,9 +2219,7 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
   // finding - the emit kernels look for those - can only lie in what is emitted)
   if (inter && c->h_bcall->first_discard < n_done) n_done = c->h_bcall->first_discard + 1;
   out->n_done = n_done;
-  unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->d_bcall) + sizeof(BcCall));
-  unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_bcall) + sizeof(BcCall));
-  const uint64_t nb_done = (n_done + kScan64Span - 1) / kScan64Span;
+  unsigned long long *d_tot = bcall_totals(c->d_bcall), *h_tot = bcall_totals(c->h_bcall);
   {
     ProfScope ps(c, "k_bc_scan");
     if (n_done != n_iter) {  // (the plan counted the discards of all n_iter iterations)
@@ -2244,33 +2230,30 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
     HIP_TRY(c, hipMemsetAsync(d_tot, 0, 3 * sizeof(unsigned long long), c->stream));
     for (int i = 0; i < 3; ++i) {
       if (P.out_sam ? i != 0 : !P.emit[i]) continue;  // outputs that are not produced have no lengths
-      hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb_done), dim3(kBlock), 0, c->stream, (const uint32_t*)c->bc_len[i].p,
-                         n_done, (unsigned long long*)c->bc_off[i].p, (unsigned long long*)c->bc_sum[i].p);
-      hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->bc_sum[i].p, nb_done,
-                         d_tot + i);
+      scan64(c, c->bc_len[i].p, c->bc_off[i].p, c->bc_sum[i].p, d_tot + i, n_done);
     }
   }
   HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall) + 64, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   out->n_discarded = c->h_bcall->discarded;
   out->n_short = c->h_bcall->short_warnings;
-  for (int i = 0; i < 3; ++i) {
-    out->out_bytes[i] = h_tot[i];
-    c->bc_out_bytes[i] = h_tot[i];
-    if ((rc = ensure(c, c->bc_out[i], std::max<uint64_t>(h_tot[i], 16)))) return rc;
-  }
+  uint64_t totals[3] = {h_tot[0], h_tot[1], h_tot[2]};
+  uint8_t* text[3];
+  for (int i = 0; i < 3; ++i) out->out_bytes[i] = totals[i];
+  NEED(text_reserve(c, c->bc_text, totals, 3, text));
+  text_publish(c->bc_text, totals, 3);
   {
     ProfScope ps(c, "k_bc_emit");
     EmitOut eo[3];
     for (int i = 0; i < 3; ++i)
       eo[i] = EmitOut{(const uint32_t*)c->bc_len[i].p, (const unsigned long long*)c->bc_off[i].p,
-                      (const unsigned long long*)c->bc_sum[i].p, (uint8_t*)c->bc_out[i].p};
+                      (const unsigned long long*)c->bc_sum[i].p, text[i]};
     const uint64_t n_tiles_done = (n_done + tc.T - 1) / tc.T;
     const unsigned lds = tc.in_cap + tc.out_cap;
     unsigned grid_t = 1;
 #define FQG_EMIT_TILE(SAM, MASK)                                                                                  \
   do {                                                                                                            \
-    grid_t = (unsigned)std::min<uint64_t>(n_tiles_done, resident((const void*)k_bc_emit_tile<SAM, MASK>, lds));    \
+    grid_t = (unsigned)std::min<uint64_t>(n_tiles_done, resident_waves(c, (const void*)k_bc_emit_tile<SAM, MASK>, lds)); \
     hipLaunchKernelGGL((k_bc_emit_tile<SAM, MASK>), dim3(grid_t), dim3(kWave), lds, c->stream, P, tc, n_done,      \
                        (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo[0], eo[1], eo[2],      \
                        c->d_bcall);                                                                                \
@@ -2317,9 +2300,9 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
         HIP_TRY(c, hipMemcpy(&off, (const unsigned long long*)c->bc_off[i].p + k, 8, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(&sum, (const unsigned long long*)c->bc_sum[i].p + k / kScan64Span, 8, hipMemcpyDeviceToHost));
       }
-      out->out_bytes[i] = off + sum;
-      c->bc_out_bytes[i] = off + sum;
+      out->out_bytes[i] = totals[i] = off + sum;
     }
+    text_publish(c->bc_text, totals, 3);
     if (k) {
       HIP_TRY(c, hipMemsetAsync(&c->d_bcall->discarded, 0, 2 * sizeof(unsigned long long), c->stream));
       hipLaunchKernelGGL(k_bc_count, dim3((unsigned)std::min<uint64_t>((k + kBlock - 1) / kBlock, 2048)), dim3(kBlock), 0,
@@ -2453,15 +2436,13 @@ int fqg_census_finish(fqg_ctx* c, fqg_census* z, uint64_t* n_pairs, uint64_t* n_
     if (rocprim::radix_sort_pairs(z->tmp.p, tmp_bytes, um, um2, ce, ce2, n, 0, ub, c->stream) != hipSuccess ||
         rocprim::radix_sort_pairs(z->tmp.p, tmp_bytes, ce2, ce, um2, um, n, 0, cb, c->stream) != hipSuccess)
       return fail(c, FQG_ERR_HIP, "fqg_census_finish: sort");
-    const uint64_t nb = (n + kScan64Span - 1) / kScan64Span;
+    const uint64_t nb = scan64_spans(n);
     if ((rc = ensure(c, z->flag, n * 4)) || (rc = ensure(c, z->local, n * 8)) || (rc = ensure(c, z->sums, nb * 8 + 8))) return rc;
     unsigned long long* d_total = (unsigned long long*)z->sums.p + nb;
     HIP_TRY(c, hipMemsetAsync(d_total, 0, 8, c->stream));
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_census_flags, dim3(grid), dim3(kBlock), 0, c->stream, (const unsigned long long*)ce, n, (uint32_t*)z->flag.p);
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, c->stream, (const uint32_t*)z->flag.p, n,
-                       (unsigned long long*)z->local.p, (unsigned long long*)z->sums.p);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)z->sums.p, nb, d_total);
+    scan64(c, z->flag.p, z->local.p, z->sums.p, d_total, n);
     unsigned long long cells = 0;
     HIP_TRY(c, hipMemcpyAsync(&cells, d_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2583,12 +2564,8 @@ int fqg_barcodes_whitelist(fqg_ctx* c, const fqg_frame* frame, uint64_t first, u
 int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record, uint64_t n_rec,
                        const fqg_filter_params* fp, fqg_filter_result* out) {
   if (!c || !frame || !fp || !out) return FQG_ERR_ARG;
-  if (c->out_pending) {  // (a copy of the previous output is still on its way: this call writes the same buffers)
-    const int rcw = fqg_barcodes_output_wait(c);
-    if (rcw) return rcw;
-  }
+  NEED(text_begin(c, c->bc_text));
   memset(out, 0, sizeof(*out));
-  c->bc_out_bytes[0] = c->bc_out_bytes[1] = c->bc_out_bytes[2] = 0;
   if (fp->mode != FQG_FILTER_N && fp->mode != FQG_FILTER_POLY_AT) return fail(c, FQG_ERR_ARG, "fqg_records_filter: unknown mode");
   if (first_record + n_rec > frame->fv.n_records) return fail(c, FQG_ERR_ARG, "fqg_records_filter: records beyond the frame");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2609,28 +2586,18 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   P.min_poly = fp->min_poly_at_len;
   P.min_len = (uint64_t)fp->min_len;
   int rc;
-  const uint64_t nb = (n_rec + kScan64Span - 1) / kScan64Span;
   if ((rc = ensure(c, c->bc_status, n_rec))) return rc;
   if ((rc = ensure(c, c->bc_len[1], n_rec * 4))) return rc;
   if ((rc = ensure(c, c->bc_off[1], n_rec * 8))) return rc;
-  if ((rc = ensure(c, c->bc_sum[1], nb * 8))) return rc;
-  BcCall z;
-  memset(&z, 0, sizeof(z));
-  *c->h_bcall = z;
-  HIP_TRY(c, hipMemcpyAsync(c->d_bcall, c->h_bcall, sizeof(BcCall), hipMemcpyHostToDevice, c->stream));
+  if ((rc = ensure(c, c->bc_sum[1], scan64_spans(n_rec) * 8))) return rc;
+  NEED(bcall_reset(c, 0));
   // (the tiles are the EMIT kernel's alone now - the plan works record by record - and that kernel likes 24 KiB per
   // wavefront better than the 20 KiB it shared with a staging plan: tools/tiles_lds_sweep.sh)
   BcTile tc = bc_tile_for(F, 24576u);
   tc.plan_m = 1;
   const uint64_t n_tiles = (n_rec + tc.T - 1) / tc.T;
   if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
-  auto resident = [&](const void* kernel, unsigned lds) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    return (unsigned)per_cu * (unsigned)c->cu_count;
-  };
-  unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->d_bcall) + sizeof(BcCall));
-  unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_bcall) + sizeof(BcCall));
+  unsigned long long *d_tot = bcall_totals(c->d_bcall), *h_tot = bcall_totals(c->h_bcall);
   {
     ProfScope ps(c, "k_rf_plan");
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 32));
@@ -2646,9 +2613,7 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   {
     // (the plan kernels count what they drop and trim; the tile flags come behind the scan, whose offsets they use)
     ProfScope ps(c, "k_rf_scan");
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, c->stream, (const uint32_t*)c->bc_len[1].p, n_rec,
-                       (unsigned long long*)c->bc_off[1].p, (unsigned long long*)c->bc_sum[1].p);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->bc_sum[1].p, nb, d_tot + 1);
+    scan64(c, c->bc_len[1].p, c->bc_off[1].p, c->bc_sum[1].p, d_tot + 1, n_rec);
     hipLaunchKernelGGL(k_rf_tile_flags, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, F, tc, n_rec,
                        (const uint32_t*)c->bc_len[1].p, (const unsigned long long*)c->bc_off[1].p,
                        (const unsigned long long*)c->bc_sum[1].p, (uint8_t*)c->bc_tile_big.p, c->d_bcall);
@@ -2659,14 +2624,16 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   out->n_trimmed = c->h_bcall->short_warnings;
   out->n_kept = n_rec - out->n_discarded;
   out->out_bytes = h_tot[1];
-  c->bc_out_bytes[1] = h_tot[1];
-  if ((rc = ensure(c, c->bc_out[1], std::max<uint64_t>(h_tot[1], 16)))) return rc;
+  const uint64_t totals[2] = {0, h_tot[1]};  // (stream 1, as the transform's read1)
+  uint8_t* text[2];
+  NEED(text_reserve(c, c->bc_text, totals, 2, text));
+  text_publish(c->bc_text, totals, 2);
   if (h_tot[1]) {
     ProfScope ps(c, "k_rf_emit");
     const EmitOut eo{(const uint32_t*)c->bc_len[1].p, (const unsigned long long*)c->bc_off[1].p,
-                     (const unsigned long long*)c->bc_sum[1].p, (uint8_t*)c->bc_out[1].p};
+                     (const unsigned long long*)c->bc_sum[1].p, text[1]};
     const unsigned lds = tc.in_cap + tc.out_cap;
-    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, resident((const void*)k_rf_emit_tile, lds));
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_rf_emit_tile, lds));
     hipLaunchKernelGGL(k_rf_emit_tile, dim3(grid), dim3(kWave), lds, c->stream, F, P, tc, n_rec,
                        (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo);
     if (c->h_bcall->big) {
@@ -2681,56 +2648,30 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
 }
 
 int fqg_barcodes_output(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
-  if (!c || which < 0 || which > 2 || (!host_dst && nbytes)) return FQG_ERR_ARG;
-  if (nbytes > c->bc_out_bytes[which]) return fail(c, FQG_ERR_ARG, "fqg_barcodes_output: more than was produced");
-  if (!nbytes) return 0;
-  HIP_TRY(c, hipMemcpyAsync(host_dst, c->bc_out[which].p, nbytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return 0;
+  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
+  return text_copy(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output: more than was produced");
 }
 
-int fqg_barcodes_output_wait(fqg_ctx* c) {
-  if (!c) return FQG_ERR_ARG;
-  if (!c->out_pending) return 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipStreamSynchronize(c->out_stream));
-  c->out_pending = false;
-  return 0;
-}
+int fqg_barcodes_output_wait(fqg_ctx* c) { return c ? text_wait(c, c->bc_text) : (int)FQG_ERR_ARG; }
 
 int fqg_barcodes_output_begin(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
-  if (!c || which < 0 || which > 2 || (!host_dst && nbytes)) return FQG_ERR_ARG;
-  if (nbytes > c->bc_out_bytes[which]) return fail(c, FQG_ERR_ARG, "fqg_barcodes_output_begin: more than was produced");
-  if (!nbytes) return 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->out_stream) {
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->out_ready, hipEventDisableTiming));
-  }
-  HIP_TRY(c, hipEventRecord(c->out_ready, c->stream));  // (what produced the text has been launched on `stream`)
-  HIP_TRY(c, hipStreamWaitEvent(c->out_stream, c->out_ready, 0));
-  HIP_TRY(c, hipMemcpyAsync(host_dst, c->bc_out[which].p, nbytes, hipMemcpyDeviceToHost, c->out_stream));
-  c->out_pending = true;
-  return 0;
+  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
+  return text_copy_begin(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output_begin: more than was produced");
 }
 
 int fqg_records_filter_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) { return fqg_barcodes_output(c, 1, host_dst, nbytes); }
 
 int fqg_records_gather(fqg_ctx* c, const fqg_frame* frame, const uint64_t* records, uint64_t n, uint64_t* out_bytes) {
   if (!c || !frame || !out_bytes || (!records && n)) return FQG_ERR_ARG;
-  if (c->out_pending) {  // (a copy of the previous output is still on its way: this call writes the same buffers)
-    const int rcw = fqg_barcodes_output_wait(c);
-    if (rcw) return rcw;
-  }
+  NEED(text_begin(c, c->bc_text));
   *out_bytes = 0;
-  c->bc_out_bytes[0] = c->bc_out_bytes[1] = c->bc_out_bytes[2] = 0;
   if (!n) return 0;
   for (uint64_t k = 0; k < n; ++k)
     if (records[k] >= frame->fv.n_records) return fail(c, FQG_ERR_ARG, "fqg_records_gather: record outside the frame");
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   const bool nul = (frame->flags & kFlagNul) != 0;
-  const uint64_t nb = (n + kScan64Span - 1) / kScan64Span;
+  const uint64_t nb = scan64_spans(n);
   if ((rc = ensure(c, c->bc_off[1], n * 8))) return rc;     // the list
   if ((rc = ensure(c, c->bc_len[1], n * 4))) return rc;
   if ((rc = ensure(c, c->bc_off[2], n * 8))) return rc;     // local offsets
@@ -2745,14 +2686,13 @@ int fqg_records_gather(fqg_ctx* c, const fqg_frame* frame, const uint64_t* recor
     else
       hipLaunchKernelGGL(k_gather_lens, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, frame->fv,
                          (const unsigned long long*)c->bc_off[1].p, n, (uint32_t*)c->bc_len[1].p);
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, c->stream, (const uint32_t*)c->bc_len[1].p, n,
-                       (unsigned long long*)c->bc_off[2].p, (unsigned long long*)c->bc_sum[1].p);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, c->stream, (unsigned long long*)c->bc_sum[1].p, nb, d_tot);
+    scan64(c, c->bc_len[1].p, c->bc_off[2].p, c->bc_sum[1].p, d_tot, n);
   }
   HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[2], d_tot, 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint64_t total = c->h_scalar[2];
-  if ((rc = ensure(c, c->bc_out[1], total + 64))) return rc;
+  const uint64_t total = c->h_scalar[2], totals[2] = {0, total};  // (stream 1, as the filter)
+  uint8_t* text[2];
+  NEED(text_reserve(c, c->bc_text, totals, 2, text));
   {
     ProfScope ps(c, "k_gather_copy");
     const unsigned grid = (unsigned)std::min<uint64_t>((n + 4 * kWave - 1) / (4 * kWave), (uint64_t)c->cu_count * 16);
@@ -2760,15 +2700,15 @@ int fqg_records_gather(fqg_ctx* c, const fqg_frame* frame, const uint64_t* recor
       hipLaunchKernelGGL(k_gather_copy_nul, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)c->cu_count * 16)), dim3(kBlock), 0,
                          c->stream, frame->fv, (const unsigned long long*)c->bc_off[1].p, n,
                          (const unsigned long long*)c->bc_off[2].p, (const unsigned long long*)c->bc_sum[1].p,
-                         (uint8_t*)c->bc_out[1].p);
+                         text[1]);
     else
       hipLaunchKernelGGL(k_gather_copy, dim3(grid), dim3(kBlock), 0, c->stream, frame->fv,
                          (const unsigned long long*)c->bc_off[1].p, n, (const unsigned long long*)c->bc_off[2].p,
-                         (const unsigned long long*)c->bc_sum[1].p, (const uint32_t*)c->bc_len[1].p, (uint8_t*)c->bc_out[1].p);
+                         (const unsigned long long*)c->bc_sum[1].p, (const uint32_t*)c->bc_len[1].p, text[1]);
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  c->bc_out_bytes[1] = total;
+  text_publish(c->bc_text, totals, 2);
   *out_bytes = total;
   return 0;
 }

@@ -7,7 +7,7 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
             fqg_b2f_result* out, B2fCall* h_call) {
   hipStream_t st = c->stream;
   const int ns = prm->tenx ? 3 : kB2fStreams;
-  const uint64_t nb = ((uint64_t)n + kScan64Span - 1) / kScan64Span;
+  const uint64_t nb = scan64_spans(n);
   const size_t size_stride = (((size_t)n * 4) + 255) & ~(size_t)255, local_stride = (((size_t)n * 8) + 255) & ~(size_t)255;
   const size_t sums_stride = (((size_t)nb * 8) + 64 + 255) & ~(size_t)255;
   NEED(ensure(c, c->bam_size, size_stride * ns));
@@ -29,8 +29,7 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   A.tenx = prm->tenx ? 1 : 0;
   A.n_streams = ns;
   A.call = d_call;
-  B2fScan S;
-  memset(&S, 0, sizeof(S));
+  Scan64 S{};
   for (int s = 0; s < ns; ++s) {
     A.size[s] = (uint32_t*)((char*)c->bam_size.p + size_stride * s);
     A.local[s] = (const unsigned long long*)((char*)c->bam_local.p + local_stride * s);
@@ -47,10 +46,9 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   }
   {
     ProfScope ps(c, "k_b2f_scan");
-    hipLaunchKernelGGL(k_b2f_scan_a, dim3((unsigned)nb, (unsigned)ns), dim3(kBlock), 0, st, S, (uint64_t)n);
-    hipLaunchKernelGGL(k_b2f_scan_b, dim3(1, (unsigned)ns), dim3(kBlock), 0, st, S, nb);
+    scan64(c, S, ns, n);
   }
-  unsigned long long h_total[kB2fStreams] = {0, 0, 0, 0, 0, 0};
+  uint64_t h_total[kB2fStreams] = {0, 0, 0, 0, 0, 0};
   HIP_TRY(c, hipMemcpyAsync(h_call, d_call, sizeof(*h_call), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(h_total, d_total, 8 * (size_t)ns, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -58,22 +56,18 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   if (h_call->first_finding != ~0ull) return 0;  // (the caller runs the alignments in front of the finding again)
   out->n_alignments = n;
   out->warn_record = h_call->warn_record;
-  size_t at = 0;
   for (int s = 0; s < ns; ++s) {
     out->out_bytes[s] = h_total[s];
     out->first_record[s] = h_call->first_record[s];
-    c->b2f_out_at[s] = at;
-    at += ((size_t)h_total[s] + 64 + 255) & ~(size_t)255;
   }
-  NEED(ensure(c, c->b2f_out, at + 64));
-  for (int s = 0; s < ns; ++s) A.out[s] = (uint8_t*)c->b2f_out.p + c->b2f_out_at[s];
+  NEED(text_reserve(c, c->b2f_text, h_total, ns, A.out));
   {
     ProfScope ps(c, "k_b2f_emit");
     hipLaunchKernelGGL(k_b2f_tile<true>, dim3(grid), dim3(kWave), A.in_cap + A.out_cap + 64, st, A);
   }
   HIP_TRY(c, hipStreamSynchronize(st));
   HIP_TRY(c, hipGetLastError());
-  for (int s = 0; s < ns; ++s) c->b2f_out_bytes[s] = h_total[s];
+  text_publish(c->b2f_text, h_total, ns);
   return 0;
 }
 }  // namespace
@@ -85,8 +79,8 @@ int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   auto begin = [&] {
     memset(out, 0, sizeof(*out));
     out->warn_record = FQG_B2F_UNUSED;
-    for (int s = 0; s < FQG_B2F_STREAMS; ++s) out->first_record[s] = FQG_B2F_UNUSED, c->b2f_out_bytes[s] = 0;
-    return 0;
+    for (int s = 0; s < FQG_B2F_STREAMS; ++s) out->first_record[s] = FQG_B2F_UNUSED;
+    return text_begin(c, c->b2f_text);
   };
   NEED(bam_input(c, "fqg_bam2fastq", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
   if (!n_records) return 0;
@@ -114,9 +108,6 @@ int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
 }
 
 int fqg_bam2fastq_output(fqg_ctx* c, int stream_id, void* host_dst, uint64_t nbytes) {
-  if (!c || stream_id < 0 || stream_id >= FQG_B2F_STREAMS || (nbytes && !host_dst)) return FQG_ERR_ARG;
-  if (nbytes > c->b2f_out_bytes[stream_id]) return fail(c, FQG_ERR_ARG, "fqg_bam2fastq_output: more than the last call produced");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (nbytes) HIP_TRY(c, hipMemcpy(host_dst, (const char*)c->b2f_out.p + c->b2f_out_at[stream_id], nbytes, hipMemcpyDeviceToHost));
-  return 0;
+  if (!c) return FQG_ERR_ARG;
+  return text_copy(c, c->b2f_text, stream_id, host_dst, nbytes, "fqg_bam2fastq_output: more than the last call produced");
 }

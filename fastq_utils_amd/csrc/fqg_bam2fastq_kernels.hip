@@ -8,7 +8,7 @@
 // in the same tiles (the frame: fqg_bam_tile.h):
 //   k_b2f_tile<false>  every lane walks the aux area of ITS alignment once in the staged span, decides the routing and
 //               writes the bytes its record adds to every stream
-//   scan        one 64-bit exclusive prefix per stream, all streams in one launch pair (k_b2f_scan_a / _b)
+//   scan        one 64-bit exclusive prefix per stream, all streams in one launch pair (k_scan64_a / _b)
 //   k_b2f_tile<true>   the same tiles again: the lane writes its FASTQ records into the LDS images of the tile's output
 //               span of every stream
 //   Tiles that do not fit LDS (reads of thousands of bases) read the stream itself, and every lane writes its records
@@ -38,18 +38,6 @@ struct B2fTiles : BamTiles {
   uint8_t* out[kB2fStreams];
   B2fCall* call;
 };
-struct B2fScan {
-  const uint32_t* in[kB2fStreams];
-  unsigned long long* local[kB2fStreams];
-  unsigned long long* sums[kB2fStreams];
-  unsigned long long* total;  // [kB2fStreams]
-};
-__global__ __launch_bounds__(kBlock) void k_b2f_scan_a(B2fScan t, uint64_t n) {
-  scan64_a_body(t.in[blockIdx.y], n, t.local[blockIdx.y], t.sums[blockIdx.y]);
-}
-__global__ __launch_bounds__(kBlock) void k_b2f_scan_b(B2fScan t, uint64_t nb) {
-  scan64_b_body(t.sums[blockIdx.y], nb, t.total + blockIdx.y);
-}
 
 // What one alignment is, as far as bam2fastq looks: offsets from the start of the record (its block_size field).
 struct B2fRec {

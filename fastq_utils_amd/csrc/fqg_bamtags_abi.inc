@@ -7,8 +7,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     if (prm->n_targets && (!prm->tx_off || !prm->tx_len || !prm->gx_off || !prm->gx_len || !prm->names)) return (int)FQG_ERR_ARG;
     memset(out, 0, sizeof(*out));
     out->n_alignments = n_records;
-    c->bt_out_bytes = 0;
-    return 0;
+    return text_begin(c, c->bt_text);
   };
   NEED(bam_input(c, "fqg_bam_add_tags", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
   if (!n_records) return 0;
@@ -44,7 +43,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     P.names = (const uint8_t*)(t + 4 * nt);
   }
 
-  const uint64_t nb = ((uint64_t)n + kScan64Span - 1) / kScan64Span;
+  const uint64_t nb = scan64_spans(n);
   NEED(ensure(c, c->bam_size, (size_t)n * 4));
   NEED(ensure(c, c->bam_local, (size_t)n * 8));
   NEED(ensure(c, c->bam_sums, (size_t)nb * 8 + 64));
@@ -76,11 +75,9 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
   }
   {
     ProfScope ps(c, "k_bt_scan");
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, st, (const uint32_t*)c->bam_size.p, (uint64_t)n,
-                       (unsigned long long*)c->bam_local.p, (unsigned long long*)c->bam_sums.p);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, (unsigned long long*)c->bam_sums.p, nb, d_total);
+    scan64(c, c->bam_size.p, c->bam_local.p, c->bam_sums.p, d_total, n);
   }
-  unsigned long long h_total = 0;
+  uint64_t h_total = 0;
   HIP_TRY(c, hipMemcpyAsync(&h_call, d_call, sizeof(h_call), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(&h_total, d_total, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -91,22 +88,18 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     return 0;  // (nothing is written for a stream the reference has no defined output for)
   }
   out->out_bytes = h_total;
-  NEED(ensure(c, c->bt_out, (size_t)h_total + 64));
-  A.out = (uint8_t*)c->bt_out.p;
+  NEED(text_reserve(c, c->bt_text, &h_total, 1, &A.out));
   {
     ProfScope ps(c, "k_bt_emit");
     hipLaunchKernelGGL(k_bt_tile<true>, dim3(grid), dim3(kWave), lds, st, A);
   }
   HIP_TRY(c, hipStreamSynchronize(st));
   HIP_TRY(c, hipGetLastError());
-  c->bt_out_bytes = h_total;
+  text_publish(c->bt_text, &h_total, 1);
   return 0;
 }
 
 int fqg_bam_add_tags_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) {
-  if (!c || (nbytes && !host_dst)) return FQG_ERR_ARG;
-  if (nbytes > c->bt_out_bytes) return fail(c, FQG_ERR_ARG, "fqg_bam_add_tags_output: more than the last call produced");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (nbytes) HIP_TRY(c, hipMemcpy(host_dst, c->bt_out.p, nbytes, hipMemcpyDeviceToHost));
-  return 0;
+  if (!c) return FQG_ERR_ARG;
+  return text_copy(c, c->bt_text, 0, host_dst, nbytes, "fqg_bam_add_tags_output: more than the last call produced");
 }

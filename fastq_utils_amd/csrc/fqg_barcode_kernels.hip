@@ -868,22 +868,6 @@ __global__ __launch_bounds__(kBlock) void k_bc_count(const uint8_t* __restrict__
   }
 }
 
-// the same for three arrays in one launch (blockIdx.y picks the array): bam_umi_count numbers UMIs, cells and features
-// by three such scans, and a launch costs more than the scan of a few million flags
-struct Scan3 {
-  const uint32_t* first[3];          // k_umi_flag3: table -> first record of the key in the slot
-  uint32_t* flag[3];
-  unsigned long long* local[3];
-  unsigned long long* sums[3];
-  unsigned long long* total;         // [3]
-};
-__global__ __launch_bounds__(kBlock) void k_scan64_a3(Scan3 t, uint64_t n) {
-  scan64_a_body(t.flag[blockIdx.y], n, t.local[blockIdx.y], t.sums[blockIdx.y]);
-}
-__global__ __launch_bounds__(kBlock) void k_scan64_b3(Scan3 t, uint64_t nb) {
-  scan64_b_body(t.sums[blockIdx.y], nb, t.total + blockIdx.y);
-}
-
 // ---- emit -----------------------------------------------------------------------------------
 // up to 16 characters of a literal as two 64-bit immediates (no memory access when written)
 constexpr uint64_t lit_pack(const char* s, int n, int from) {

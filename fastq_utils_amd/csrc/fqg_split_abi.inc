@@ -17,19 +17,15 @@ unsigned split_env_T() {
 
 int fqg_records_split(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record, uint64_t n_rec, uint64_t out_bytes[2]) {
   if (!c || !frame || !out_bytes) return FQG_ERR_ARG;
-  if (c->out_pending) {  // (a copy of the previous output is still on its way: this call writes the same buffers)
-    const int rcw = fqg_barcodes_output_wait(c);
-    if (rcw) return rcw;
-  }
+  NEED(text_begin(c, c->bc_text));
   out_bytes[0] = out_bytes[1] = 0;
-  c->bc_out_bytes[0] = c->bc_out_bytes[1] = c->bc_out_bytes[2] = 0;
   c->split_info[0] = c->split_info[1] = c->split_info[2] = c->split_info[3] = 0;
   if (n_rec & 1) return fail(c, FQG_ERR_ARG, "fqg_records_split: an odd number of records");
   if (first_record > frame->fv.n_records || n_rec > frame->fv.n_records - first_record)
     return fail(c, FQG_ERR_ARG, "fqg_records_split: records beyond the frame");
   if (!n_rec) return 0;
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t np = n_rec / 2, nb = (np + kScan64Span - 1) / kScan64Span;
+  const uint64_t np = n_rec / 2, nb = scan64_spans(np);
   SplitArgs A;
   memset(&A, 0, sizeof(A));
   A.fv = frame->fv;
@@ -57,59 +53,53 @@ int fqg_records_split(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record,
     A.out_cap = std::min(A.in_cap + kSplitOutSlack, budget - A.in_cap) & ~15u;
   }
   const uint64_t n_tiles = (n_rec + A.T - 1) / A.T;
-  int rc;
+  Scan64 S{};
   for (int s = 0; s < 2; ++s) {
-    if ((rc = ensure(c, c->bc_len[1 + s], np * 4))) return rc;
-    if ((rc = ensure(c, c->bc_off[1 + s], np * 8))) return rc;
-    if ((rc = ensure(c, c->bc_sum[1 + s], nb * 8 + 32))) return rc;
-    A.len[s] = (uint32_t*)c->bc_len[1 + s].p;
-    A.local[s] = (unsigned long long*)c->bc_off[1 + s].p;
-    A.sums[s] = (unsigned long long*)c->bc_sum[1 + s].p;
+    NEED(ensure(c, c->bc_len[1 + s], np * 4));
+    NEED(ensure(c, c->bc_off[1 + s], np * 8));
+    NEED(ensure(c, c->bc_sum[1 + s], nb * 8 + 32));
+    S.in[s] = A.len[s] = (uint32_t*)c->bc_len[1 + s].p;
+    S.local[s] = A.local[s] = (unsigned long long*)c->bc_off[1 + s].p;
+    S.sums[s] = A.sums[s] = (unsigned long long*)c->bc_sum[1 + s].p;
   }
-  if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
-  A.total = (unsigned long long*)c->bc_sum[1].p + nb;  // (two words behind stream 0's span sums)
+  NEED(ensure(c, c->bc_tile_big, n_tiles));
+  S.total = (unsigned long long*)c->bc_sum[1].p + nb;  // (two words behind stream 0's span sums)
   A.tile_big = (uint8_t*)c->bc_tile_big.p;
   A.n_big = &c->d_bcall->big;
-  BcCall z;
-  memset(&z, 0, sizeof(z));
-  *c->h_bcall = z;
-  HIP_TRY(c, hipMemcpyAsync(c->d_bcall, c->h_bcall, sizeof(BcCall), hipMemcpyHostToDevice, c->stream));
+  NEED(bcall_reset(c, 0));
   {
     ProfScope ps(c, "k_split_plan");
     const unsigned grid = (unsigned)std::min<uint64_t>((n_rec + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 32);
     hipLaunchKernelGGL(k_split_lens, dim3(grid), dim3(kBlock), 0, c->stream, A);
-    hipLaunchKernelGGL(k_split_scan_a, dim3((unsigned)nb, 2), dim3(kBlock), 0, c->stream, A);
-    hipLaunchKernelGGL(k_split_scan_b, dim3(1, 2), dim3(kBlock), 0, c->stream, A, nb);
+    scan64(c, S, 2, np);
     hipLaunchKernelGGL(k_split_tile_flags, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
   }
   HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[2], A.total, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[2], S.total, 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  const uint64_t total[2] = {c->h_scalar[2], c->h_scalar[3]};
+  const uint64_t totals[3] = {0, c->h_scalar[2], c->h_scalar[3]};  // (streams 1 and 2, as the transform's two reads)
   const uint64_t n_big = c->h_bcall->big;
-  for (int s = 0; s < 2; ++s) {
-    if ((rc = ensure(c, c->bc_out[1 + s], total[s] + 64))) return rc;
-    A.out[s] = (uint8_t*)c->bc_out[1 + s].p;
-  }
+  uint8_t* text[3];
+  NEED(text_reserve(c, c->bc_text, totals, 3, text));
+  A.out[0] = text[1], A.out[1] = text[2];
   unsigned grid_t = 0;
   {
     ProfScope ps(c, "k_split_emit");
     if (n_big < n_tiles) {
       const unsigned lds = A.in_cap + A.out_cap;
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_split_emit_tile, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-      grid_t = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)per_cu * (uint64_t)c->cu_count);
+      grid_t = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_split_emit_tile, lds));
       hipLaunchKernelGGL(k_split_emit_tile, dim3(grid_t), dim3(kWave), lds, c->stream, A);
     }
-    if (n_big) {
+    if (n_big) {  // (16 workgroups per CU where the transform's and the filter's direct paths take 8: kept, the kernel sees the grid)
       const unsigned grid_e = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 3) / 4, (uint64_t)c->cu_count * 16));
       hipLaunchKernelGGL(k_split_emit_direct, dim3(grid_e), dim3(kBlock), 0, c->stream, A);
     }
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  for (int s = 0; s < 2; ++s) c->bc_out_bytes[1 + s] = out_bytes[s] = total[s];
+  text_publish(c->bc_text, totals, 3);
+  out_bytes[0] = totals[1], out_bytes[1] = totals[2];
   c->split_info[0] = n_tiles;
   c->split_info[1] = n_big;
   c->split_info[2] = grid_t;

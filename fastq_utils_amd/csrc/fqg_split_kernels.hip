@@ -6,7 +6,7 @@
 // list of records, no per-record length array on the way out.  Same tile scheme as the record filters
 // (fqg_filter_kernels.hip):
 //   k_split_lens        one thread per record: its output bytes, into the array of its stream
-//   k_split_scan_a/_b   the two 64-bit exclusive prefixes in one launch pair
+//   k_scan64_a/_b       the two 64-bit exclusive prefixes in one launch pair
 //   k_split_tile_flags  one thread per tile of T records (T even: a tile holds whole pairs): does its span fit LDS
 //   k_split_emit_tile   one wavefront per tile: the tile's span of the image lands in LDS with aligned 16-byte loads, every
 //                       lane copies its record inside LDS into the image of its stream (the two images lie behind each
@@ -27,7 +27,6 @@ struct SplitArgs {
   uint32_t* len[2];             // per stream: bytes of its p-th record (record first + 2p + stream)
   unsigned long long* local[2]; // ... their exclusive prefix inside a span of kScan64Span
   unsigned long long* sums[2];  // ... and the prefix of the span sums
-  unsigned long long* total;    // [2]
   uint8_t* out[2];
   uint8_t* tile_big;
   unsigned long long* n_big;    // tiles that take the direct path
@@ -65,13 +64,6 @@ __global__ __launch_bounds__(kBlock) void k_split_lens(SplitArgs A) {
     }
     A.len[k & 1][k >> 1] = len;
   }
-}
-
-__global__ __launch_bounds__(kBlock) void k_split_scan_a(SplitArgs A) {
-  scan64_a_body(A.len[blockIdx.y], A.n_rec / 2, A.local[blockIdx.y], A.sums[blockIdx.y]);
-}
-__global__ __launch_bounds__(kBlock) void k_split_scan_b(SplitArgs A, uint64_t nb) {
-  scan64_b_body(A.sums[blockIdx.y], nb, A.total + blockIdx.y);
 }
 
 // bytes the two images of a tile need on top of the span's own (two skews below 16, the second image on a 16-byte

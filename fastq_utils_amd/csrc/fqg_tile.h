@@ -105,13 +105,20 @@ __device__ __forceinline__ void scan64_a_body(const uint32_t* __restrict__ in, u
   }
   if (threadIdx.x == 0) sums[blockIdx.x] = all;
 }
-// one workgroup: exclusive prefix over the span sums, total into *total
-__global__ __launch_bounds__(kBlock) void k_scan64_a(const uint32_t* __restrict__ in, uint64_t n,
-                                                     unsigned long long* __restrict__ local,
-                                                     unsigned long long* __restrict__ sums) {
-  scan64_a_body(in, n, local, sums);
+// The arrays of up to kScan64Streams scans that run as ONE launch pair (blockIdx.y picks the stream): a launch costs more
+// than the scan of a few million lengths.  A single scan fills entry 0.
+constexpr int kScan64Streams = 6;
+struct Scan64 {
+  const uint32_t* in[kScan64Streams];
+  unsigned long long* local[kScan64Streams];  // exclusive prefix inside a span of kScan64Span
+  unsigned long long* sums[kScan64Streams];   // the span sums, then (k_scan64_b) their exclusive prefix
+  unsigned long long* total;                  // [streams]
+};
+__global__ __launch_bounds__(kBlock) void k_scan64_a(Scan64 t, uint64_t n) {  // grid (spans, streams)
+  scan64_a_body(t.in[blockIdx.y], n, t.local[blockIdx.y], t.sums[blockIdx.y]);
 }
 
+// one workgroup: exclusive prefix over the span sums, total into *total
 // (2048 sums per round - eight per thread, a wavefront scan by shuffles, one exchange through LDS: the scan of the
 // 97 656 span sums of 200 M lengths took 0.49 ms as 382 rounds of a 256-wide scan with sixteen barriers each)
 __device__ __forceinline__ void scan64_b_body(unsigned long long* __restrict__ sums, uint64_t nb,
@@ -151,9 +158,8 @@ __device__ __forceinline__ void scan64_b_body(unsigned long long* __restrict__ s
   }
   if (threadIdx.x == 0) *total = carry;
 }
-__global__ __launch_bounds__(kBlock) void k_scan64_b(unsigned long long* __restrict__ sums, uint64_t nb,
-                                                     unsigned long long* __restrict__ total) {
-  scan64_b_body(sums, nb, total);
+__global__ __launch_bounds__(kBlock) void k_scan64_b(Scan64 t, uint64_t nb) {  // grid (1, streams)
+  scan64_b_body(t.sums[blockIdx.y], nb, t.total + blockIdx.y);
 }
 
 // ---- an LDS image to memory ------------------------------------------------------------------

@@ -294,7 +294,7 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   }
 
   // ---- dense ids: flags on the record axis + exclusive prefix ----
-  const uint64_t nb = ((uint64_t)n + kUmiSpan - 1) / kUmiSpan;
+  const uint64_t nb = scan64_spans(n);
   uint32_t* d_flag[3];
   unsigned long long *d_loc[3], *d_span[3], *d_tot = S.get<unsigned long long>(8);
   UMI_NEED(d_tot);
@@ -305,20 +305,20 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
     uint32_t* flags3 = S.get<uint32_t>(3ull * n + 64, 0);
     UMI_NEED(flags3);
     Scan3 t3;
+    Scan64 s3{};
     for (int k = 0; k < 3; ++k) {
       d_flag[k] = flags3 + (uint64_t)k * n;
       d_loc[k] = S.get<unsigned long long>(n);
       d_span[k] = S.get<unsigned long long>(nb);
       UMI_NEED(d_loc[k] && d_span[k]);
       t3.first[k] = firsts[k];
-      t3.flag[k] = d_flag[k];
-      t3.local[k] = d_loc[k];
-      t3.sums[k] = d_span[k];
+      s3.in[k] = t3.flag[k] = d_flag[k];
+      s3.local[k] = d_loc[k];
+      s3.sums[k] = d_span[k];
     }
-    t3.total = d_tot;
+    s3.total = d_tot;
     hipLaunchKernelGGL(k_umi_flag3, dim3(blocks_for(cap), 3), dim3(kBlock), 0, st, t3, cap);
-    hipLaunchKernelGGL(k_scan64_a3, dim3((unsigned)nb, 3), dim3(kBlock), 0, st, t3, (uint64_t)n);
-    hipLaunchKernelGGL(k_scan64_b3, dim3(1, 3), dim3(kBlock), 0, st, t3, nb);
+    scan64(c, s3, 3, n);
   }
   Prefix pu{d_loc[0], d_span[0]}, pc{d_loc[1], d_span[1]}, pf{d_loc[2], d_span[2]};
   UmiIds ids;
@@ -386,7 +386,7 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   uint64_t n_pairs = 0;
   const uint8_t* d_feat_replayed = nullptr;  // (set by the per-cell path when it replays sets)
   const bool unit = h_call.all_unit != 0;
-  const uint64_t nbc = (n_cells + 2 + kUmiSpan - 1) / kUmiSpan;
+  const uint64_t nbc = scan64_spans(n_cells + 2);
   // CR-sorted input with unit increments: one workgroup per cell, LDS (fqg_umi_cell_kernels.hip).  Anything else -
   // unsorted mode, fractional increments, features or cells beyond the key's bit fields - takes the hash tables.
   static const bool force_hash = getenv("FQGPU_UMI_HASH_PATH") != nullptr;
@@ -453,9 +453,7 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
     {
       ProfScope ps(c, "k_rl_detect");
       hipLaunchKernelGGL(k_rl_starts, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)ko, d_sflag);
-      hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nb), dim3(kBlock), 0, st, (const uint32_t*)d_sflag, (uint64_t)n, d_rloc,
-                         d_rspan);
-      hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, d_rspan, nb, d_tot + 6);
+      scan64(c, d_sflag, d_rloc, d_rspan, d_tot + 6, n);
       hipLaunchKernelGGL(k_rl_detect, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)ko, (const uint32_t*)io,
                          (const uint32_t*)d_sflag, Prefix{d_rloc, d_rspan}, (const uint32_t*)ids.umi,
                          (const uint8_t*)d_new, runs, d_flagged, d_fk0, d_rl);
@@ -609,9 +607,7 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   {
     ProfScope ps(c, "k_umi_pairs");
     hipLaunchKernelGGL(k_umi_pairs_count, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, Pt, d_cell_pairs);
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nbc), dim3(kBlock), 0, st, (const uint32_t*)d_cell_pairs,
-                       (uint64_t)(n_cells + 2), d_cloc, d_cspan);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, d_cspan, nbc, d_tot + 3);
+    scan64(c, d_cell_pairs, d_cloc, d_cspan, d_tot + 3, n_cells + 2);
   }
   HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, sizeof(h_tot), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -726,7 +722,7 @@ int fqg_umi_emit(fqg_ctx* c, const uint32_t* feat_remap, uint64_t n_remap, uint3
     hipLaunchKernelGGL(k_umi_emit, dim3(A.n_cells), dim3(kBlock), 0, st, A, us->d_call);
   }
   // close the gaps
-  const uint64_t nbp = (std::max<uint64_t>(n_pairs, 1) + kUmiSpan - 1) / kUmiSpan;
+  const uint64_t nbp = scan64_spans(n_pairs);
   for (int w = 0; w < 2; ++w) {
     ProfScope ps(c, "k_umi_compact");
     uint32_t* fl = S.get<uint32_t>(n_pairs);
@@ -735,8 +731,7 @@ int fqg_umi_emit(fqg_ctx* c, const uint32_t* feat_remap, uint64_t n_remap, uint3
     UMI_NEED(fl && lo && sp);
     const UmiEntry* src = w ? d_sr : d_su;
     hipLaunchKernelGGL(k_umi_entry_flags, dim3(blocks_for(n_pairs)), dim3(kBlock), 0, st, (uint32_t)n_pairs, src, fl);
-    hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nbp), dim3(kBlock), 0, st, (const uint32_t*)fl, n_pairs, lo, sp);
-    hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, sp, nbp, us->d_tot + 4 + w);
+    scan64(c, fl, lo, sp, us->d_tot + 4 + w, n_pairs);
     int rc;
     if ((rc = ensure(c, c->umi_entries[w], (size_t)n_pairs * sizeof(UmiEntry)))) return rc;
     hipLaunchKernelGGL(k_umi_compact, dim3(blocks_for(n_pairs)), dim3(kBlock), 0, st, (uint32_t)n_pairs, src,

@@ -61,9 +61,7 @@
     // pairs grouped by cell (they already are: a prefix over the cells' pair counts gives the compact order)
     {
       ProfScope ps(c, "k_umi_pairs");
-      hipLaunchKernelGGL(k_scan64_a, dim3((unsigned)nbc), dim3(kBlock), 0, st, (const uint32_t*)d_cell_pairs,
-                         (uint64_t)(n_cells + 2), d_cloc, d_cspan);
-      hipLaunchKernelGGL(k_scan64_b, dim3(1), dim3(kBlock), 0, st, d_cspan, nbc, d_tot + 3);
+      scan64(c, d_cell_pairs, d_cloc, d_cspan, d_tot + 3, n_cells + 2);
     }
     RlCall h_rl;
     HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, sizeof(h_tot), hipMemcpyDeviceToHost, st));

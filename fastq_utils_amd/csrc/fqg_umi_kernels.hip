@@ -643,6 +643,11 @@ __global__ __launch_bounds__(kBlock) void k_umi_flag(const uint32_t* __restrict_
   if (f != kNoIdx) flag[f] = 1u;
 }
 
+// the same for the three tables in one launch (blockIdx.y picks the table): bam_umi_count numbers UMIs, cells and features
+struct Scan3 {
+  const uint32_t* first[3];  // table -> first record of the key in the slot
+  uint32_t* flag[3];
+};
 __global__ __launch_bounds__(kBlock) void k_umi_flag3(Scan3 t, uint64_t n_slots) {
   const uint64_t h = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (h >= n_slots) return;
