@@ -41,7 +41,7 @@ EXPORTS = [
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
-    "fqg_bam2fastq", "fqg_bam2fastq_output",
+    "fqg_bam2fastq", "fqg_bam2fastq_output", "fqg_deflate", "fqg_text_deflate", "fqg_deflate_output",
     "fqg_umi_count", "fqg_umi_features", "fqg_umi_record_features", "fqg_umi_replayed_features", "fqg_umi_umis",
     "fqg_umi_cells", "fqg_umi_entries", "fqg_umi_emit",
     "fqg_fp_owner", "fqg_names_fingerprints", "fqg_names_fingerprints_acct", "fqg_names_fingerprints_named", "fqg_frame_name_records", "fqg_frame_names_equal", "fqg_device_alloc", "fqg_device_free",
@@ -50,8 +50,17 @@ EXPORTS = [
 ]
 
 
+GZ_MEMBER_TEXT = 65280  # FQG_GZ_MEMBER_TEXT
+TEXT_RECORDS, TEXT_BAM2FASTQ = 0, 1  # FQG_TEXT_*: the store fqg_text_deflate reads
+
+
 class LibraryMissing(RuntimeError):
     pass
+
+
+class DeflateResult(C.Structure):
+    _fields_ = [("text_bytes", C.c_uint64), ("n_members", C.c_uint64), ("gz_bytes", C.c_uint64),
+                ("tail_bytes", C.c_uint64)]
 
 
 class FileState(C.Structure):
@@ -309,6 +318,9 @@ def load():
     L.fqg_bam_add_tags_output.argtypes = [vp, vp, u64]
     L.fqg_bam2fastq.argtypes = [vp, vp, u64, C.c_int, C.POINTER(u64), u64, C.POINTER(B2fParams), C.POINTER(B2fResult)]
     L.fqg_bam2fastq_output.argtypes = [vp, C.c_int, vp, u64]
+    L.fqg_deflate.argtypes = [vp, vp, u64, vp, u64, C.c_int, C.c_int, C.POINTER(DeflateResult)]
+    L.fqg_text_deflate.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, C.POINTER(DeflateResult)]
+    L.fqg_deflate_output.argtypes = [vp, vp, u64]
     L.fqg_umi_emit.argtypes = [vp, C.POINTER(C.c_uint32), u64, C.c_uint32, C.POINTER(UmiResult)]
     L.fqg_umi_features.argtypes = [vp, vp, u64]
     L.fqg_umi_cells.argtypes = [vp, C.POINTER(u64), u64]
@@ -976,6 +988,38 @@ class Context:
             if r.out_bytes[s]:
                 self._check(L.fqg_bam2fastq_output(self.h, s, dst, r.out_bytes[s]))
             out["streams"].append(dst.raw[:r.out_bytes[s]])
+        return out
+
+    def deflate(self, src, carry=b"", final=True, nbytes=None, want_output=True):
+        """fqg_deflate: the text carry + src (bytes, or an int device pointer with `nbytes`) as gzip members of
+        GZ_MEMBER_TEXT bytes of text each.  Returns the result fields and, with want_output, `members` (the gzip bytes)
+        and `tail` (the text that did not fill a member; empty with final)."""
+        host = isinstance(src, (bytes, bytearray))
+        if host:
+            buf = C.create_string_buffer(bytes(src), max(1, len(src)))
+            nbytes = len(src)
+        r = DeflateResult()
+        self._check(load().fqg_deflate(self.h, bytes(carry), len(carry), buf if host else C.c_void_p(int(src)), nbytes,
+                                       MEM_HOST if host else MEM_DEVICE, int(final), C.byref(r)))
+        return self._deflate_result(r, want_output)
+
+    def text_deflate(self, store, stream, carry=b"", final=True, want_output=True):
+        """fqg_text_deflate: the same for carry + the whole of stream `stream` of the text a producer call left on the
+        device (store: TEXT_RECORDS or TEXT_BAM2FASTQ)"""
+        r = DeflateResult()
+        self._check(load().fqg_text_deflate(self.h, store, stream, bytes(carry), len(carry), int(final), C.byref(r)))
+        return self._deflate_result(r, want_output)
+
+    def deflate_output(self, nbytes):
+        dst = C.create_string_buffer(max(1, nbytes))
+        self._check(load().fqg_deflate_output(self.h, dst, nbytes))
+        return dst.raw[:nbytes]
+
+    def _deflate_result(self, r, want_output):
+        out = {k: int(getattr(r, k)) for k, _ in DeflateResult._fields_}
+        if want_output:
+            both = self.deflate_output(out["gz_bytes"] + out["tail_bytes"])
+            out["members"], out["tail"] = both[:out["gz_bytes"]], both[out["gz_bytes"]:]
         return out
 
     @staticmethod

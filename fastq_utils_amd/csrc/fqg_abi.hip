@@ -30,6 +30,7 @@
 #include "fqg_umi_cell_kernels.hip"
 #include "fqg_bamtags_kernels.hip"
 #include "fqg_bam2fastq_kernels.hip"
+#include "fqg_deflate_kernels.hip"
 
 using namespace fqg;
 
@@ -165,6 +166,11 @@ struct fqg_ctx {
   DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
   DevBuf bt_tables, bt_call;  // fqg_bam_add_tags
   DevBuf b2f_call;            // fqg_bam2fastq
+  // fqg_deflate / fqg_text_deflate: the members (and the text behind them) of the last call in a store of their own, and
+  // the call's scratch - uploaded source and carry, member slots, their sizes and the sizes' scan, the token arena, tables
+  OutText gz_text;
+  DevBuf gz_in, gz_carry, gz_slots, gz_sizes, gz_off, gz_sums, gz_toks, gz_tab;
+  bool gz_tab_ready = false;
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
 
@@ -469,7 +475,8 @@ void fqg_close(fqg_ctx* c) {
   release(c->bc_status);
   release(c->bc_tile_big);
   for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call,
-                    &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf})
+                    &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf, &c->gz_text.buf, &c->gz_in, &c->gz_carry,
+                    &c->gz_slots, &c->gz_sizes, &c->gz_off, &c->gz_sums, &c->gz_toks, &c->gz_tab})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
@@ -2781,5 +2788,6 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 #include "fqg_bamtags_abi.inc"
 #include "fqg_bam2fastq_abi.inc"
 #include "fqg_split_abi.inc"
+#include "fqg_deflate_abi.inc"
 
 }  // extern "C"

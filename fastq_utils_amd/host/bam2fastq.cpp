@@ -58,6 +58,7 @@ struct Outputs {
       PRINT_ERROR("Unable to open %s", n.c_str());
       leave(1);
     }
+    gz[s].device(FQ_GZIP_DEVICE(g_ctx));
     is_open[s] = true;
     fprintf(stderr, "opening %s\n", n.c_str());
   }
@@ -188,6 +189,13 @@ int main(int argc, char* argv[]) {
     }
     for (int s = 0; s < n_streams; ++s) {
       if (!res.out_bytes[s]) continue;
+      if (outs.gz[s].on_device()) {  // (FQGPU_GZIP_GPU=1: compressed where it lies)
+        if (!outs.gz[s].write_device(FQG_TEXT_BAM2FASTQ, s)) {
+          PRINT_ERROR("Failed to write %s", outs.gz[s].error().c_str());
+          leave(2);
+        }
+        continue;
+      }
       text.resize(res.out_bytes[s]);
       rc = fqg_bam2fastq_output(g_ctx, s, text.data(), res.out_bytes[s]);
       if (rc != 0) {

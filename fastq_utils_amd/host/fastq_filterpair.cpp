@@ -32,6 +32,7 @@ Out* open_out(const char* path) {
     FQ_PRINT_ERROR("Unable to open %s", path);
     fqhost::leave(kExitParams);
   }
+  g->device(FQ_GZIP_DEVICE(g_ctx));
   return g;
 }
 
@@ -40,9 +41,15 @@ void emit(const fqg_frame* frame, const std::vector<uint64_t>& list, Out* out, s
   if (list.empty()) return;
   uint64_t bytes = 0;
   LIB(fqg_records_gather(g_ctx, frame, list.data(), list.size(), &bytes));
-  if (host.size() < bytes) host.resize(bytes);
-  LIB(fqg_records_gather_output(g_ctx, host.data(), bytes));
-  if (!out->write(host.data(), bytes)) {
+  bool ok;
+  if (out->on_device()) {  // (FQGPU_GZIP_GPU=1: compressed where it lies)
+    ok = out->write_device(FQG_TEXT_RECORDS, 1);
+  } else {
+    if (host.size() < bytes) host.resize(bytes);
+    LIB(fqg_records_gather_output(g_ctx, host.data(), bytes));
+    ok = out->write(host.data(), bytes);
+  }
+  if (!ok) {
     FQ_PRINT_ERROR("%s.\n", out->error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
     fqhost::leave(kExitSys);
   }

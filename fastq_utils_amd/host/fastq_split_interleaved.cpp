@@ -31,11 +31,12 @@ Out* open_out(const std::string& path) {
     FQ_PRINT_ERROR("Unable to open %s", path.c_str());
     fqhost::leave(kExitParams);
   }
+  g->device(FQ_GZIP_DEVICE(g_ctx));
   return g;
 }
 
-void write_out(Out* out, const char* text, uint64_t n) {
-  if (!out->write(text, n)) {
+void written(Out* out, bool ok) {
+  if (!ok) {
     FQ_PRINT_ERROR("%s.\n", out->error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
     fqhost::leave(kExitSys);
   }
@@ -111,11 +112,15 @@ int main(int argc, char** argv) {
     if (n) {
       uint64_t bytes[2] = {0, 0};
       LIB(fqg_records_split(g_ctx, fr, 0, n, bytes));
-      for (int s = 0; s < 2; ++s) {
-        if (host[s].size() < bytes[s]) host[s].resize(bytes[s]);
-        LIB(fqg_records_split_output(g_ctx, s, host[s].data(), bytes[s]));
+      if (w[0]->on_device()) {  // (FQGPU_GZIP_GPU=1: both texts are compressed where they lie)
+        for (int s = 0; s < 2; ++s) written(w[s], w[s]->write_device(FQG_TEXT_RECORDS, 1 + s));
+      } else {
+        for (int s = 0; s < 2; ++s) {
+          if (host[s].size() < bytes[s]) host[s].resize(bytes[s]);
+          LIB(fqg_records_split_output(g_ctx, s, host[s].data(), bytes[s]));
+        }
+        for (int s = 0; s < 2; ++s) written(w[s], w[s]->write(host[s].data(), bytes[s]));
       }
-      for (int s = 0; s < 2; ++s) write_out(w[s], host[s].data(), bytes[s]);
     }
     if (fr) fqg_frame_release(fr);
     ticker(pair_base + 1, pair_base + n / 2, 50000, 2);  // PRINT_READS_PROCESSED(cline / 4, 100000) behind every pair

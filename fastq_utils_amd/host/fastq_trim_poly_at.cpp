@@ -101,21 +101,25 @@ int main(int argc, char** argv) {
   fp.mode = FQG_FILTER_POLY_AT;
   fp.min_poly_at_len = min_poly_at_len;
   fp.min_len = min_len;
+  out.device(FQ_GZIP_DEVICE(ctx));  // (FQGPU_GZIP_GPU=1: the kept records are compressed where they lie)
+  auto written = [&](bool ok) {
+    if (!ok) {
+      FQ_PRINT_ERROR("%s.\n", out.error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
+      fqhost::leave(kExitSys);
+    }
+  };
+  std::function<void(size_t)> on_device;
+  if (out.on_device()) on_device = [&](size_t) { written(out.write_device(FQG_TEXT_RECORDS, 1)); };
   const FilterTotals t = run_filter(
-      ctx, file, fp,
-      [&](const char* text, size_t n) {
-        if (!out.write(text, n)) {
-          FQ_PRINT_ERROR("%s.\n", out.error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
-          fqhost::leave(kExitSys);
-        }
-      },
+      ctx, file, fp, [&](const char* text, size_t n) { written(out.write(text, n)); },
       [](unsigned long before, unsigned long after) {
         // PRINT_READS_PROCESSED(fdi->cline / 4, 100000) after every record
         for (unsigned long c = (before / 100000 + 1) * 100000; c <= after; c += 100000) {
           fprintf(stderr, "\b\b\b\b\b\b\b\b\b\b\b\b\b\b\b%lu", c);
           fflush(stderr);
         }
-      });
+      },
+      on_device);
   FQ_PRINT_INFO("Reads processed: %ld", (long)t.processed);
   FQ_PRINT_INFO("Reads trimmed: %ld", (long)t.trimmed);
   FQ_PRINT_INFO("Reads discarded: %ld", (long)t.discarded);

@@ -22,10 +22,12 @@ struct FilterTotals {
   unsigned long processed = 0, trimmed = 0, discarded = 0;
 };
 
-// sink(text, bytes): the kept records of one piece; progress(before, after): records read so far
+// sink(text, bytes): the kept records of one piece; progress(before, after): records read so far.  device_sink (may be
+// empty): called INSTEAD of the copy and the sink - the text is on the device, stream 1 of FQG_TEXT_RECORDS
 inline FilterTotals run_filter(fqg_ctx* ctx, const char* path, const fqg_filter_params& fp,
                                const std::function<void(const char*, size_t)>& sink,
-                               const std::function<void(unsigned long, unsigned long)>& progress) {
+                               const std::function<void(unsigned long, unsigned long)>& progress,
+                               const std::function<void(size_t)>& device_sink = nullptr) {
   auto lib = [&](int rc, const char* what) {
     if (rc != 0) {
       FQ_PRINT_ERROR("GPU library failure in %s (%d): %s", what, rc, fqg_last_error(ctx));
@@ -60,7 +62,9 @@ inline FilterTotals run_filter(fqg_ctx* ctx, const char* path, const fqg_filter_
       lib(fqg_frame_retain(ctx, &frame), "fqg_frame_retain");
       fqg_filter_result fr;
       lib(fqg_records_filter(ctx, frame, 0, r.n_records, &fp, &fr), "fqg_records_filter");
-      if (fr.out_bytes) {
+      if (fr.out_bytes && device_sink) {
+        device_sink(fr.out_bytes);
+      } else if (fr.out_bytes) {
         if (host.size() < fr.out_bytes) host.resize(fr.out_bytes);
         lib(fqg_records_filter_output(ctx, host.data(), fr.out_bytes), "fqg_records_filter_output");
         sink(host.data(), fr.out_bytes);

@@ -28,9 +28,21 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/fqg.h"
 #include "fq_fastdeflate.h"
 
 namespace fqhost {
+
+// The device compressor (fqg_deflate, include/fqg.h) as GzipMembers calls it: a program that links libfqgpu.so fills it
+// with gzip_device(ctx); this header names no symbol of the library, so the host-only checks link without it.
+struct GzipDevice {
+  fqg_ctx* ctx = nullptr;
+  int (*deflate)(fqg_ctx*, const void*, uint64_t, const void*, uint64_t, int, int, fqg_deflate_result*) = nullptr;
+  int (*text_deflate)(fqg_ctx*, int, int, const void*, uint64_t, int, fqg_deflate_result*) = nullptr;
+  int (*output)(fqg_ctx*, void*, uint64_t) = nullptr;
+  const char* (*last_error)(const fqg_ctx*) = nullptr;
+};
+#define FQ_GZIP_DEVICE(ctx) (fqhost::GzipDevice{(ctx), fqg_deflate, fqg_text_deflate, fqg_deflate_output, fqg_last_error})
 
 // the cores this process may run on (a container's share of the machine: more threads than that only take turns)
 inline unsigned usable_cores() {
@@ -168,6 +180,9 @@ class GzipMembers {
     // FQGPU_GZIP_FAST=1: the members from fq_fastdeflate.h instead of zlib's - three times as fast as the reference's
     // level 4 and a tenth larger (zlib level 1's size class)
     if (const char* e = getenv("FQGPU_GZIP_FAST")) fast_ = atoi(e) != 0;
+    // FQGPU_GZIP_GPU=1: the members from the device compressor, FQG_GZ_MEMBER_TEXT bytes of text each - in the programs
+    // that hand their context over (device()); it then takes precedence over the two above
+    if (const char* e = getenv("FQGPU_GZIP_GPU")) gpu_ = atoi(e) != 0;
     if (path[0] == '-' && path[1] == 0) {
       f_ = stdout;
       name_ = "<fd:1>";  // (what zlib's gzdopen calls it in its messages)
@@ -181,6 +196,16 @@ class GzipMembers {
   // what gzerror() would say about the write that failed (zlib's gz_error: "<path>: <text>", the text being
   // strerror(errno) for a failed write(2) and "out of memory" for a failed deflate)
   const std::string& error() const { return err_; }
+  // Device mode (FQGPU_GZIP_GPU=1 only): every member of this file comes from fqg_deflate / fqg_text_deflate, the last
+  // one included, so the file is a function of the text alone here too.  Text then comes through write_device() only
+  // (write() stays the host compressor's: its members are another size).
+  void device(const GzipDevice& d) {
+    if (gpu_) dev_ = d;
+  }
+  bool on_device() const { return dev_.ctx != nullptr; }
+  // the whole of stream `stream` of store `store` (FQG_TEXT_*), read where it lies on the device: pend_ is the carry, one
+  // copy brings the members and the text that did not fill one, which waits in pend_ again
+  bool write_device(int store, int stream) { return device_members(store, stream, false); }
   // Every member holds exactly 1 MiB of text (the last one the rest), whatever the sizes of the calls: the bytes
   // written are a function of the text alone.  A run that starts over on re-framed input (fq_respawn.h) skips as many
   // bytes of its stdout as the first run wrote - they must be the same bytes, though the two runs cut their input into
@@ -222,8 +247,12 @@ class GzipMembers {
     bool ok = true;
     if (!f_) return true;
     if (!pend_.empty() || !wrote_) {  // the rest - and an empty gzip stream is still a gzip stream
-      std::vector<uint8_t> m;
-      ok = member(pend_.data(), pend_.size(), m) && put(m);
+      if (on_device()) {
+        ok = device_members(-1, 0, true);
+      } else {
+        std::vector<uint8_t> m;
+        ok = member(pend_.data(), pend_.size(), m) && put(m);
+      }
       pend_.clear();
     }
     if (own_) ok = fclose(f_) == 0 && ok;
@@ -242,6 +271,23 @@ class GzipMembers {
     wrote_ = true;
     return true;
   }
+  // pend_ + a stream of a store (store < 0: pend_ alone) through the device compressor; what comes back is written and kept
+  bool device_members(int store, int stream, bool final) {
+    fqg_deflate_result r;
+    int rc = store >= 0 ? dev_.text_deflate(dev_.ctx, store, stream, pend_.data(), pend_.size(), final ? 1 : 0, &r)
+                        : dev_.deflate(dev_.ctx, pend_.data(), pend_.size(), nullptr, 0, FQG_MEM_HOST, final ? 1 : 0, &r);
+    if (rc == 0) {
+      from_device_.resize(r.gz_bytes + r.tail_bytes);
+      rc = dev_.output(dev_.ctx, from_device_.data(), from_device_.size());
+    }
+    if (rc != 0) {
+      err_ = name_ + ": device compressor (" + std::to_string(rc) + "): " + dev_.last_error(dev_.ctx);
+      return false;
+    }
+    pend_.assign(reinterpret_cast<const char*>(from_device_.data()) + r.gz_bytes, r.tail_bytes);
+    from_device_.resize(r.gz_bytes);
+    return from_device_.empty() || put(from_device_);
+  }
   bool member(const char* p, size_t n, std::vector<uint8_t>& out) const {
     if (fast_) return fdef::gzip_member_fast(p, n, out);
     z_stream zs;
@@ -259,8 +305,10 @@ class GzipMembers {
   }
   FILE* f_ = nullptr;
   std::string name_, err_, pend_;
-  bool own_ = false, wrote_ = false, fast_ = false;
+  bool own_ = false, wrote_ = false, fast_ = false, gpu_ = false;
   int level_ = 4;
+  GzipDevice dev_;
+  std::vector<uint8_t> from_device_;
 };
 
 // the whole file, BGZF members inflated back to back (SAM/BAM specification, section 4.1)

@@ -646,6 +646,34 @@ int fqg_bam2fastq(fqg_ctx *ctx, const void *stream, uint64_t nbytes, int mem, co
                   uint64_t n_records, const fqg_b2f_params *params, fqg_b2f_result *out);
 int fqg_bam2fastq_output(fqg_ctx *ctx, int stream_id, void *host_dst, uint64_t nbytes);
 
+/* ---- gzip members compressed on the device ----------------------------------------------------------------
+ * A run of text becomes gzip members (RFC 1952) that lie back to back: every complete FQG_GZ_MEMBER_TEXT bytes, counted
+ * from the start of the text, are one member - a ten-byte header, one final deflate block (dynamic Huffman codes, or
+ * stored where that is no larger: a member of n text bytes has at most n + 23), CRC-32 and ISIZE.  The text is `carry`
+ * (host memory, fewer than FQG_GZ_MEMBER_TEXT bytes: what the previous call left over) followed by [src, src + nbytes)
+ * - or, for fqg_text_deflate, by the whole of one stream of the text a producer call left on the device (read where it
+ * lies; the producer's store is not changed).  With final != 0 the rest of the text becomes a last, shorter member
+ * (an empty text: one member of empty content) and tail_bytes is 0; otherwise the rest, less than a member, is kept as
+ * text behind the members: fqg_deflate_output copies the members and, directly behind them, these tail_bytes, which the
+ * caller hands back as the next call's carry.  The bytes of the members depend on the text and FQG_GZ_MEMBER_TEXT
+ * alone - not on how the text was cut into calls, not on where it lies.  A source in device memory is read in whole
+ * aligned 16-byte words: up to 15 bytes in front of src and up to 15 behind src + nbytes are loaded (never used) when
+ * they share such a word with a byte of the text - a caller who sub-allocates must own those words.  FQG_ERR_ARG (the
+ * result of the previous call then stays as it was): carry_bytes >=
+ * FQG_GZ_MEMBER_TEXT, a store or stream that does not exist, more bytes asked of fqg_deflate_output than gz_bytes +
+ * tail_bytes. */
+#define FQG_GZ_MEMBER_TEXT 65280u
+#define FQG_TEXT_RECORDS 0   /* what fqg_barcodes_transform / fqg_records_filter / _gather / _split produced last */
+#define FQG_TEXT_BAM2FASTQ 1 /* what fqg_bam2fastq produced last */
+typedef struct {
+  uint64_t text_bytes, n_members, gz_bytes, tail_bytes;
+} fqg_deflate_result;
+int fqg_deflate(fqg_ctx *ctx, const void *carry, uint64_t carry_bytes, const void *src, uint64_t nbytes, int mem, int final,
+                fqg_deflate_result *out);
+int fqg_text_deflate(fqg_ctx *ctx, int store, int stream, const void *carry, uint64_t carry_bytes, int final,
+                     fqg_deflate_result *out);
+int fqg_deflate_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif
