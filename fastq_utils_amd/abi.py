@@ -42,6 +42,7 @@ EXPORTS = [
     "fqg_census_pairs", "fqg_census_device_pairs",
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
     "fqg_bam2fastq", "fqg_bam2fastq_output", "fqg_deflate", "fqg_text_deflate", "fqg_deflate_output",
+    "fqg_bgzf_deflate", "fqg_text_bgzf_deflate", "fqg_deflate_output_begin", "fqg_deflate_output_wait",
     "fqg_umi_count", "fqg_umi_features", "fqg_umi_record_features", "fqg_umi_replayed_features", "fqg_umi_umis",
     "fqg_umi_cells", "fqg_umi_entries", "fqg_umi_emit",
     "fqg_fp_owner", "fqg_names_fingerprints", "fqg_names_fingerprints_acct", "fqg_names_fingerprints_named", "fqg_frame_name_records", "fqg_frame_names_equal", "fqg_device_alloc", "fqg_device_free",
@@ -51,7 +52,7 @@ EXPORTS = [
 
 
 GZ_MEMBER_TEXT = 65280  # FQG_GZ_MEMBER_TEXT
-TEXT_RECORDS, TEXT_BAM2FASTQ = 0, 1  # FQG_TEXT_*: the store fqg_text_deflate reads
+TEXT_RECORDS, TEXT_BAM2FASTQ, TEXT_BAM_TAGS = 0, 1, 2  # FQG_TEXT_*: the store fqg_text_deflate reads
 
 
 class LibraryMissing(RuntimeError):
@@ -321,6 +322,10 @@ def load():
     L.fqg_deflate.argtypes = [vp, vp, u64, vp, u64, C.c_int, C.c_int, C.POINTER(DeflateResult)]
     L.fqg_text_deflate.argtypes = [vp, C.c_int, C.c_int, vp, u64, C.c_int, C.POINTER(DeflateResult)]
     L.fqg_deflate_output.argtypes = [vp, vp, u64]
+    L.fqg_bgzf_deflate.argtypes = L.fqg_deflate.argtypes
+    L.fqg_text_bgzf_deflate.argtypes = L.fqg_text_deflate.argtypes
+    L.fqg_deflate_output_begin.argtypes = [vp, vp, u64]
+    L.fqg_deflate_output_wait.argtypes = [vp]
     L.fqg_umi_emit.argtypes = [vp, C.POINTER(C.c_uint32), u64, C.c_uint32, C.POINTER(UmiResult)]
     L.fqg_umi_features.argtypes = [vp, vp, u64]
     L.fqg_umi_cells.argtypes = [vp, C.POINTER(u64), u64]
@@ -591,6 +596,24 @@ class NameIndex:
         if self.h:
             load().fqg_index_destroy(self.h)
             self.h = None
+
+
+class PinnedOutput:
+    """nbytes of pinned host memory of a context (fqg_host_alloc / fqg_host_free) that an asynchronous copy lands in"""
+
+    def __init__(self, ctx, nbytes):
+        self.ctx, self.nbytes = ctx, nbytes
+        self.ptr = load().fqg_host_alloc(ctx.h, max(1, nbytes))
+        if not self.ptr:
+            raise MemoryError("fqg_host_alloc(%d)" % nbytes)
+
+    def bytes(self):
+        return C.string_at(self.ptr, self.nbytes)
+
+    def free(self):
+        if self.ptr:
+            load().fqg_host_free(self.ctx.h, self.ptr)
+            self.ptr = None
 
 
 class Context:
@@ -990,30 +1013,60 @@ class Context:
             out["streams"].append(dst.raw[:r.out_bytes[s]])
         return out
 
-    def deflate(self, src, carry=b"", final=True, nbytes=None, want_output=True):
-        """fqg_deflate: the text carry + src (bytes, or an int device pointer with `nbytes`) as gzip members of
-        GZ_MEMBER_TEXT bytes of text each.  Returns the result fields and, with want_output, `members` (the gzip bytes)
-        and `tail` (the text that did not fill a member; empty with final)."""
+    def _deflate(self, fn, src, carry, final, nbytes, want_output):
         host = isinstance(src, (bytes, bytearray))
         if host:
             buf = C.create_string_buffer(bytes(src), max(1, len(src)))
             nbytes = len(src)
         r = DeflateResult()
-        self._check(load().fqg_deflate(self.h, bytes(carry), len(carry), buf if host else C.c_void_p(int(src)), nbytes,
-                                       MEM_HOST if host else MEM_DEVICE, int(final), C.byref(r)))
+        self._check(fn(self.h, bytes(carry), len(carry), buf if host else C.c_void_p(int(src)), nbytes,
+                       MEM_HOST if host else MEM_DEVICE, int(final), C.byref(r)))
         return self._deflate_result(r, want_output)
+
+    def _text_deflate(self, fn, store, stream, carry, final, want_output):
+        r = DeflateResult()
+        self._check(fn(self.h, store, stream, bytes(carry), len(carry), int(final), C.byref(r)))
+        return self._deflate_result(r, want_output)
+
+    def deflate(self, src, carry=b"", final=True, nbytes=None, want_output=True):
+        """fqg_deflate: the text carry + src (bytes, or an int device pointer with `nbytes`) as gzip members of
+        GZ_MEMBER_TEXT bytes of text each.  Returns the result fields and, with want_output, `members` (the gzip bytes)
+        and `tail` (the text that did not fill a member; empty with final)."""
+        return self._deflate(load().fqg_deflate, src, carry, final, nbytes, want_output)
 
     def text_deflate(self, store, stream, carry=b"", final=True, want_output=True):
         """fqg_text_deflate: the same for carry + the whole of stream `stream` of the text a producer call left on the
-        device (store: TEXT_RECORDS or TEXT_BAM2FASTQ)"""
-        r = DeflateResult()
-        self._check(load().fqg_text_deflate(self.h, store, stream, bytes(carry), len(carry), int(final), C.byref(r)))
-        return self._deflate_result(r, want_output)
+        device (store: TEXT_RECORDS, TEXT_BAM2FASTQ or TEXT_BAM_TAGS)"""
+        return self._text_deflate(load().fqg_text_deflate, store, stream, carry, final, want_output)
+
+    def bgzf_deflate(self, src, carry=b"", final=True, nbytes=None, want_output=True):
+        """fqg_bgzf_deflate: as deflate, the members being BGZF blocks (with final the end-of-file block behind them, counted
+        in gz_bytes); `carry` may have any length."""
+        return self._deflate(load().fqg_bgzf_deflate, src, carry, final, nbytes, want_output)
+
+    def text_bgzf_deflate(self, store, stream, carry=b"", final=True, want_output=True):
+        """fqg_text_bgzf_deflate: as text_deflate, with BGZF blocks"""
+        return self._text_deflate(load().fqg_text_bgzf_deflate, store, stream, carry, final, want_output)
 
     def deflate_output(self, nbytes):
         dst = C.create_string_buffer(max(1, nbytes))
         self._check(load().fqg_deflate_output(self.h, dst, nbytes))
         return dst.raw[:nbytes]
+
+    def deflate_output_begin(self, nbytes):
+        """fqg_deflate_output_begin into pinned memory (fqg_host_alloc: the copy is asynchronous): starts the copy and
+        returns a PinnedOutput; deflate_output_wait, or the next deflate call, completes it - then its bytes() are what
+        deflate_output returns.  free() it when done."""
+        out = PinnedOutput(self, nbytes)
+        try:
+            self._check(load().fqg_deflate_output_begin(self.h, out.ptr, nbytes))
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def deflate_output_wait(self):
+        self._check(load().fqg_deflate_output_wait(self.h))
 
     def _deflate_result(self, r, want_output):
         out = {k: int(getattr(r, k)) for k, _ in DeflateResult._fields_}

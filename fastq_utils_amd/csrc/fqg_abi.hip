@@ -162,6 +162,7 @@ struct fqg_ctx {
   // the text of the last transform (streams 0..2), filter or gather (1), split (1, 2); of the last fqg_bam_add_tags;
   // of the last fqg_bam2fastq - three stores: the text of a BAM call survives a FASTQ-side call and the other way round
   OutText bc_text, bt_text, b2f_text;
+  bool bt_begun = false;  // fqg_bam_add_tags has been called: FQG_TEXT_BAM_TAGS names a store
   uint64_t split_info[4] = {0, 0, 0, 0};  // of the last fqg_records_split: tiles, tiles on the direct path, emit grid, T
   DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
   DevBuf bt_tables, bt_call;  // fqg_bam_add_tags
@@ -490,11 +491,13 @@ void fqg_close(fqg_ctx* c) {
   if (c->d_cs) (void)hipFree(c->d_cs);
   if (c->h_cs) (void)hipHostFree(c->h_cs);
   if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-  if (c->bc_text.copy_stream) {
-    (void)hipStreamSynchronize(c->bc_text.copy_stream);
-    (void)hipStreamDestroy(c->bc_text.copy_stream);
+  for (OutText* o : {&c->bc_text, &c->gz_text}) {
+    if (o->copy_stream) {
+      (void)hipStreamSynchronize(o->copy_stream);
+      (void)hipStreamDestroy(o->copy_stream);
+    }
+    if (o->ready) (void)hipEventDestroy(o->ready);
   }
-  if (c->bc_text.ready) (void)hipEventDestroy(c->bc_text.ready);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }

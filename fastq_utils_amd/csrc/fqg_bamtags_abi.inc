@@ -7,6 +7,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     if (prm->n_targets && (!prm->tx_off || !prm->tx_len || !prm->gx_off || !prm->gx_len || !prm->names)) return (int)FQG_ERR_ARG;
     memset(out, 0, sizeof(*out));
     out->n_alignments = n_records;
+    c->bt_begun = true;
     return text_begin(c, c->bt_text);
   };
   NEED(bam_input(c, "fqg_bam_add_tags", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));

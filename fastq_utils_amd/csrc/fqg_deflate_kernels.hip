@@ -23,6 +23,10 @@
 //
 // k_deflate_gather then packs the slots at the offsets scan64 made of the sizes.  The bytes of a member are a function of
 // its text alone: nothing above looks at the grid, at the member's number or at where the text lies.
+//
+// GzArgs::frame chooses what stands around the deflate block: the ten header bytes of a plain gzip member, or BGZF's
+// eighteen (SAM/BAM specification 4.1: the extra field 'B' 'C' 2 0 BSIZE, BSIZE = the member's bytes - 1).  The block,
+// CRC-32 and ISIZE are the same bytes in both; only the image's first bit (80 or 144) differs.
 #pragma once
 #include "fqg_deflate_codes.h"
 #include "fqg_device.h"
@@ -31,14 +35,18 @@
 namespace fqg {
 
 constexpr uint32_t kGzMember = FQG_GZ_MEMBER_TEXT;
-constexpr uint32_t kGzStride = 65536;     // a member's slot: text + 23 at most, whole 16-byte words
+constexpr uint32_t kGzStride = 65536;     // a member's slot: text + 23 at most (BGZF: + 31), whole 16-byte words
 constexpr uint32_t kGzTextLds = kGzMember + 48;  // skew in front, the words an unaligned read touches behind
 constexpr uint32_t kGzHashBits = 14;
 constexpr uint32_t kGzTokStride = kGzMember + 64;  // tokens of one member (and the end-of-block) per workgroup
 constexpr uint32_t kGzEob = 0xFFFFFFFFu, kGzMatch = 0x80000000u;
 constexpr uint32_t kGzWindow = 32768;
 static_assert(kGzMember % 255 == 0 && kGzMember / 255 == kBlock, "the CRC stripes are 255 bytes per thread");
+constexpr uint32_t kGzFrameGzip = 0, kGzFrameBgzf = 1;
+constexpr uint32_t kGzHeadGzip = 10, kGzHeadBgzf = 18;  // header bytes in front of the deflate block
 static_assert(kGzMember + 23 + 16 <= kGzStride && (1u << kGzHashBits) * 4 == kGzStride, "the member image takes the hash table's place");
+static_assert(kGzMember + (kGzHeadBgzf + 5 + 8) + 16 <= kGzStride && kGzMember + (kGzHeadBgzf + 5 + 8) - 1 <= 0xFFFFu,
+              "a BGZF block fits its slot and BSIZE its sixteen bits");
 
 struct GzTables {
   uint32_t crc[256];
@@ -48,7 +56,8 @@ struct GzTables {
 struct GzArgs {
   const uint8_t* carry;  // text positions [0, carry_bytes)
   const uint8_t* src;    // ... and [carry_bytes, ...)
-  uint32_t carry_bytes;
+  uint64_t carry_bytes;  // (any length: whole members may lie inside it)
+  uint32_t frame;        // kGzFrameGzip or kGzFrameBgzf
   uint64_t member_text;  // bytes that become members
   uint64_t n_members;
   uint8_t* slots;        // n_members x kGzStride
@@ -158,9 +167,13 @@ __global__ __launch_bounds__(kBlock) void k_deflate_members(GzArgs A) {
     const uint64_t L0 = m * kGzMember;
     const uint32_t n = (uint32_t)(A.member_text - L0 < kGzMember ? A.member_text - L0 : kGzMember);
     // ---- stage ----
-    const uintptr_t a0 = (uintptr_t)A.src + (uintptr_t)L0 - (uintptr_t)A.carry_bytes;  // where position L0 lies, or would lie
+    // A member wholly inside the carry is staged from the carry as from a source of its own (16-byte loads, the skew of
+    // where it lies there); the member on the seam takes its carry part byte by byte, as a carry shorter than a member.
+    const bool in_carry = L0 + n <= A.carry_bytes;
+    const uintptr_t a0 = in_carry ? (uintptr_t)A.carry + (uintptr_t)L0
+                                  : (uintptr_t)A.src + (uintptr_t)L0 - (uintptr_t)A.carry_bytes;  // where position L0 lies, or would lie
     const uint32_t skew = (uint32_t)(a0 & 15u);
-    const uint32_t cpart = L0 < A.carry_bytes ? (uint32_t)(A.carry_bytes - L0 < n ? A.carry_bytes - L0 : n) : 0u;
+    const uint32_t cpart = !in_carry && L0 < A.carry_bytes ? (uint32_t)(A.carry_bytes - L0) : 0u;  // (< n)
     if (n > cpart) {
       const uint4* g = reinterpret_cast<const uint4*>(a0 - skew);
       for (uint32_t k = ((skew + cpart) >> 4) + t; k < ((skew + n + 15) >> 4); k += kBlock) gz_lds[k] = g[k];
@@ -336,14 +349,22 @@ __global__ __launch_bounds__(kBlock) void k_deflate_members(GzArgs A) {
       __syncthreads();
     }
     const uint32_t dyn_bytes = (S.hdr.bits + body_bits + 7) >> 3, stored_bytes = 5 + n;
+    const bool bgzf = A.frame == kGzFrameBgzf;
+    const uint32_t head_bytes = bgzf ? kGzHeadBgzf : kGzHeadGzip;
     uint32_t block_bytes;
     if (dyn_bytes <= stored_bytes) {
       block_bytes = dyn_bytes;
-      const uint32_t at0 = 80 + S.hdr.bits;
+      const uint32_t at0 = head_bytes * 8 + S.hdr.bits;
       if (t == 0) {
-        gz_or_bits(hash, 0, 0x00088B1Full, 32);
-        gz_or_bits(hash, 64, 0x0304ull, 16);
-        uint32_t at = 80;
+        if (bgzf) {  // 1f 8b 08 04 | mtime | 00 ff 06 00 | 'B' 'C' 02 00 | BSIZE (with the trailer, below)
+          gz_or_bits(hash, 0, 0x04088B1Full, 32);
+          gz_or_bits(hash, 64, 0x0006FF00ull, 32);
+          gz_or_bits(hash, 96, 0x00024342ull, 32);
+        } else {
+          gz_or_bits(hash, 0, 0x00088B1Full, 32);
+          gz_or_bits(hash, 64, 0x0304ull, 16);
+        }
+        uint32_t at = head_bytes * 8;
         dfl::dc_put_header(S.hdr, true, [&](uint32_t v, uint32_t nbits) {
           gz_or_bits(hash, at, v, nbits);
           at += nbits;
@@ -359,14 +380,22 @@ __global__ __launch_bounds__(kBlock) void k_deflate_members(GzArgs A) {
     } else {
       block_bytes = stored_bytes;
       if (t == 0) {
-        const uint8_t head[15] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 3, 1, (uint8_t)n, (uint8_t)(n >> 8), (uint8_t)~n, (uint8_t)(~n >> 8)};
-        for (int i = 0; i < 15; ++i) img8[i] = head[i];
+        if (bgzf) {
+          const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+          for (int i = 0; i < 16; ++i) img8[i] = head[i];
+        } else {
+          const uint8_t head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 3};
+          for (int i = 0; i < 10; ++i) img8[i] = head[i];
+        }
+        const uint8_t stored[5] = {1, (uint8_t)n, (uint8_t)(n >> 8), (uint8_t)~n, (uint8_t)(~n >> 8)};
+        for (int i = 0; i < 5; ++i) img8[head_bytes + i] = stored[i];
       }
-      for (uint32_t k = t; k < n; k += kBlock) img8[15 + k] = text8[skew + k];
+      for (uint32_t k = t; k < n; k += kBlock) img8[head_bytes + 5 + k] = text8[skew + k];
     }
     __syncthreads();
-    const uint32_t member_bytes = 10 + block_bytes + 8;
-    if (t < 8) img8[10 + block_bytes + t] = (uint8_t)((t < 4 ? S.crc : n) >> (8 * (t & 3)));
+    const uint32_t member_bytes = head_bytes + block_bytes + 8;
+    if (t < 8) img8[head_bytes + block_bytes + t] = (uint8_t)((t < 4 ? S.crc : n) >> (8 * (t & 3)));
+    if (bgzf && (t == 8 || t == 9)) img8[16 + (t - 8)] = (uint8_t)((member_bytes - 1) >> (8 * (t - 8)));
     __syncthreads();
     // ---- flush ----
     {

@@ -5,7 +5,8 @@
 //
 // Same command line, same stderr text, same exit status; the output BAM inflates to the same bytes (BGZF block
 // boundaries and compressed bytes are zlib's business, not the format's).
-//   host   option parsing (getopt_long with the reference's table), BGZF inflate / deflate on all cores, the header
+//   host   option parsing (getopt_long with the reference's table), BGZF inflate / deflate on all cores (the deflate on
+//          the device with FQGPU_GZIP_GPU=1: the records never come back uncompressed), the header
 //          (written as read), the transcript -> gene map (:203-232) resolved once per reference of the header
 //   GPU    everything per alignment: get_barcodes on the name, the new tags, the rewritten record stream
 // There is no CPU path for the record work: without a GPU the program fails before it reads the input.
@@ -213,16 +214,35 @@ int main(int argc, char* argv[]) {
     PRINT_ERROR("%s: alignment %llu: reference id beyond the header's references", inbam_file, (unsigned long long)res.record + 1);
     leave(2);
   }
-  std::vector<uint8_t> recs(res.out_bytes ? res.out_bytes : 1);
-  rc = fqg_bam_add_tags_output(g_ctx, recs.data(), res.out_bytes);
-  if (rc != 0) {
-    PRINT_ERROR("GPU library failure in fqg_bam_add_tags_output (%d): %s", rc, fqg_last_error(g_ctx));
-    leave(2);
+  // FQGPU_GZIP_GPU=1: the header and the records, which lie on the device, become BGZF blocks there (fqg_text_bgzf_deflate:
+  // blocks of FQG_GZ_MEMBER_TEXT bytes and the end-of-file block); what comes back is the file
+  const char* gz_gpu = getenv("FQGPU_GZIP_GPU");
+  std::vector<uint8_t> bgzf;  // the file
+  bool made = true;
+  if (gz_gpu && atoi(gz_gpu) != 0) {
+    fqg_deflate_result dr;
+    rc = fqg_text_bgzf_deflate(g_ctx, FQG_TEXT_BAM_TAGS, 0, stream.data(), header_end, 1, &dr);
+    if (rc != 0) {
+      PRINT_ERROR("GPU library failure in fqg_text_bgzf_deflate (%d): %s", rc, fqg_last_error(g_ctx));
+      leave(2);
+    }
+    bgzf.resize(dr.gz_bytes);
+    rc = fqg_deflate_output(g_ctx, bgzf.data(), dr.gz_bytes);
+    if (rc != 0) {
+      PRINT_ERROR("GPU library failure in fqg_deflate_output (%d): %s", rc, fqg_last_error(g_ctx));
+      leave(2);
+    }
+  } else {
+    std::vector<uint8_t> recs(res.out_bytes ? res.out_bytes : 1);
+    rc = fqg_bam_add_tags_output(g_ctx, recs.data(), res.out_bytes);
+    if (rc != 0) {
+      PRINT_ERROR("GPU library failure in fqg_bam_add_tags_output (%d): %s", rc, fqg_last_error(g_ctx));
+      leave(2);
+    }
+    made = fqhost::bgzf_deflate_parallel({{stream.data(), (size_t)header_end}, {recs.data(), (size_t)res.out_bytes}}, Z_DEFAULT_COMPRESSION,
+                                         bgzf);
   }
-  std::vector<uint8_t> bgzf;
-  if (!fqhost::bgzf_deflate_parallel({{stream.data(), (size_t)header_end}, {recs.data(), (size_t)res.out_bytes}}, Z_DEFAULT_COMPRESSION,
-                                     bgzf) ||
-      fwrite(bgzf.data(), 1, bgzf.size(), out) != bgzf.size() || fflush(out) != 0) {
+  if (!made || fwrite(bgzf.data(), 1, bgzf.size(), out) != bgzf.size() || fflush(out) != 0) {
     PRINT_ERROR("Failed to write %s", outbam_file);
     leave(2);
   }

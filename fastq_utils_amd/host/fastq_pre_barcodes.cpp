@@ -266,6 +266,10 @@ struct BlockRun {
     uint64_t long_line_record = 0;                // ... in this record of the file
     char* out[3] = {nullptr, nullptr, nullptr};   // the text of every output: pinned buffers that go round (OutPool)
     size_t out_cap[3] = {0, 0, 0};
+    // FQGPU_GZIP_GPU=1 on one context: out[which] holds gzip members (gz_bytes) and behind them the text that did not
+    // fill one (tail_bytes), not out_bytes of text
+    bool members[3] = {false, false, false};
+    size_t gz_bytes[3] = {0, 0, 0}, tail_bytes[3] = {0, 0, 0};
     std::string wrong_header;                     // the text of the header line of a FQG_E_WRONG_HEADER finding
     Block b[6];                                   // the context's thread's: given back before the unit is handed over
   };
@@ -350,6 +354,10 @@ struct BlockRun {
     double frame = 0, transform = 0, out = 0;
   };
   std::vector<UnitTimes> T(nd);
+  // The carry chain of the device compressor (docs/host_gzip.md section 3), one per output file: the context's thread's
+  // alone.  With ONE context every unit passes through that thread in unit order (fq_ordered.h), so the tail of unit k is
+  // the carry of unit k + 1; the thread that writes never calls into the context while units are under way.
+  std::string gz_carry[3];
   using UnitRun = OrderedRun<Unit>;
   // (fq_ordered.h: the units to whichever context is free, the results to this thread in unit order)
   UnitRun run(
@@ -437,14 +445,33 @@ struct BlockRun {
           T[di].transform += t3 - t2;
           for (int which = 0; which < 3 && !u.rc; ++which)
             if (u.r.out_bytes[which]) {
-              u.out[which] = out_pool.take(u.r.out_bytes[which], &u.out_cap[which]);
+              size_t bytes = u.r.out_bytes[which];
+              u.members[which] = which > 0 && A.outgz[which].on_device();  // (handed over for one context only: main)
+              if (u.members[which]) {
+                fqg_deflate_result dr;
+                const int rc2 = fqg_text_deflate(c, FQG_TEXT_RECORDS, which, gz_carry[which].data(), gz_carry[which].size(), 0, &dr);
+                if (rc2) {
+                  lib_fail("fqg_text_deflate", rc2);
+                  break;
+                }
+                u.gz_bytes[which] = dr.gz_bytes;
+                u.tail_bytes[which] = dr.tail_bytes;
+                bytes = dr.gz_bytes + dr.tail_bytes;
+              }
+              u.out[which] = out_pool.take(bytes, &u.out_cap[which]);
               if (!u.out[which]) {
                 u.rc = FQG_ERR_NOMEM;
                 u.err = "no pinned memory for the output text";
                 break;
               }
-              const int rc2 = fqg_barcodes_output(c, which, u.out[which], u.r.out_bytes[which]);
-              if (rc2) lib_fail("fqg_barcodes_output", rc2);
+              if (u.members[which]) {
+                const int rc2 = fqg_deflate_output(c, u.out[which], bytes);
+                if (rc2) lib_fail("fqg_deflate_output", rc2);
+                else gz_carry[which].assign(u.out[which] + u.gz_bytes[which], u.tail_bytes[which]);
+              } else {
+                const int rc2 = fqg_barcodes_output(c, which, u.out[which], u.r.out_bytes[which]);
+                if (rc2) lib_fail("fqg_barcodes_output", rc2);
+              }
             }
           if (!u.rc && u.r.code == FQG_E_WRONG_HEADER) {
             const Block& bb = b[u.r.file];
@@ -507,8 +534,12 @@ struct BlockRun {
       first_batch = false;
       for (uint64_t w = 0; w < r.n_short; ++w) fputs("Warning: Read too short - barcode not found\n", stderr);
       if (r.out_bytes[0]) fwrite(u.out[0], 1, r.out_bytes[0], stdout);
+      // (device mode: the members, and the unit's tail for close() - the tail of the LAST unit taken here, whatever the
+      // context's thread went on to compress behind a unit that ends the run)
       for (int which = 1; which < 3; ++which)
-        if (r.out_bytes[which] && !A.outgz[which].write(u.out[which], r.out_bytes[which])) {
+        if (r.out_bytes[which] &&
+            !(u.members[which] ? A.outgz[which].write_members(u.out[which], u.gz_bytes[which], u.out[which] + u.gz_bytes[which], u.tail_bytes[which])
+                               : A.outgz[which].write(u.out[which], r.out_bytes[which]))) {
           run.stop();
           FQ_PRINT_ERROR("%s.\n", A.outgz[which].error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
           fqhost::leave(kExitSys);
@@ -748,6 +779,10 @@ int main(int argc, char** argv) {
           fqhost::leave(kExitParams);
         }
         out_open[x] = true;
+        // FQGPU_GZIP_GPU=1: the device compressor, in the loops that run on ONE context.  Over several contexts unit k
+        // could cut its members only once the text lengths of units 0 .. k - 1 are known (docs/host_gzip.md section 3):
+        // no device is handed over there and the host compressor runs
+        if (devices.size() <= 1) outgz[x].device(FQ_GZIP_DEVICE(g_ctx));
       }
   } else {
     printf("@HD\tVN:1.0 SO:unknown\n");
@@ -771,6 +806,8 @@ int main(int argc, char** argv) {
     int which = 0;
     char* text = nullptr;
     size_t size = 0, cap = 0;
+    bool members = false;  // FQGPU_GZIP_GPU=1: `gz` bytes of gzip members, then size - gz bytes of text that filled none
+    size_t gz = 0;
   };
   struct AsyncOut {
     GzipMembers* gz;
@@ -796,6 +833,7 @@ int main(int argc, char** argv) {
           const auto t0 = std::chrono::steady_clock::now();
           bool ok = true;
           if (j.which == 0) ok = fwrite(j.text, 1, j.size, stdout) == j.size;
+          else if (j.members) ok = gz[j.which].write_members(j.text, j.gz, j.text + j.gz, j.size - j.gz);
           else ok = gz[j.which].write(j.text, j.size);
           {
             std::lock_guard<std::mutex> lk(mu);
@@ -872,12 +910,17 @@ int main(int argc, char** argv) {
     if (file[x]) src[x].use = (has_interleaved && x == P.interleaved[1]) ? 1 : 0;
 
   std::vector<OutJob> in_flight;  // output of the last transform, on its way to the host
+  std::string gz_carry[3];        // device mode: the text the last batch left over, per output file (the carry chain)
   auto land_output = [&] {
     if (in_flight.empty()) return;
     const double t_d = now();
     LIB(fqg_barcodes_output_wait(g_ctx));
+    LIB(fqg_deflate_output_wait(g_ctx));
     const double t_e = now();
-    for (const OutJob& job : in_flight) outq.push(job);
+    for (const OutJob& job : in_flight) {
+      if (job.members) gz_carry[job.which].assign(job.text + job.gz, job.size - job.gz);  // (the tail came with the copy)
+      outq.push(job);
+    }
     in_flight.clear();
     t_fetch += t_e - t_d;
     t_hand += now() - t_e;
@@ -952,10 +995,19 @@ int main(int argc, char** argv) {
     for (int which = 0; which < 3; ++which)
       if (r.out_bytes[which]) {
         const double t_d = now();
-        OutJob job = outq.buffer(g_ctx, r.out_bytes[which]);
+        // device mode: the members and the tail come back instead of the text; the writer gets members to write.  (The
+        // carry is the tail that landed with the previous batch: land_output() has run before this batch's transform.)
+        const bool members = which > 0 && outgz[which].on_device();
+        fqg_deflate_result dr;
+        memset(&dr, 0, sizeof(dr));
+        if (members) LIB(fqg_text_deflate(g_ctx, FQG_TEXT_RECORDS, which, gz_carry[which].data(), gz_carry[which].size(), 0, &dr));
+        OutJob job = outq.buffer(g_ctx, members ? dr.gz_bytes + dr.tail_bytes : r.out_bytes[which]);
         job.which = which;
-        job.size = r.out_bytes[which];
-        LIB(fqg_barcodes_output_begin(g_ctx, which, job.text, job.size));
+        job.size = members ? dr.gz_bytes + dr.tail_bytes : r.out_bytes[which];
+        job.members = members;
+        job.gz = dr.gz_bytes;
+        if (members) LIB(fqg_deflate_output_begin(g_ctx, job.text, job.size));
+        else LIB(fqg_barcodes_output_begin(g_ctx, which, job.text, job.size));
         in_flight.push_back(job);
         t_fetch += now() - t_d;
       }

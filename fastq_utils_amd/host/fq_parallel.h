@@ -198,7 +198,7 @@ class GzipMembers {
   const std::string& error() const { return err_; }
   // Device mode (FQGPU_GZIP_GPU=1 only): every member of this file comes from fqg_deflate / fqg_text_deflate, the last
   // one included, so the file is a function of the text alone here too.  Text then comes through write_device() only
-  // (write() stays the host compressor's: its members are another size).
+  // or, already compressed, through write_members() (write() stays the host compressor's: its members are another size).
   void device(const GzipDevice& d) {
     if (gpu_) dev_ = d;
   }
@@ -206,6 +206,15 @@ class GzipMembers {
   // the whole of stream `stream` of store `store` (FQG_TEXT_*), read where it lies on the device: pend_ is the carry, one
   // copy brings the members and the text that did not fill one, which waits in pend_ again
   bool write_device(int store, int stream) { return device_members(store, stream, false); }
+  // Members somebody else had the device compressor make of pend_ + the next text (a thread that owns the context: this
+  // one calls into no context before close()), and the text that did not fill one: the members are written, the tail is
+  // pend_ from here on.  The caller's carry chain is this file's as long as every call brings the tail of the call whose
+  // carry was the previous tail.
+  bool write_members(const void* gz, size_t n, const char* tail, size_t tail_n) {
+    if (n && !put(static_cast<const uint8_t*>(gz), n)) return false;
+    pend_.assign(tail, tail_n);
+    return true;
+  }
   // Every member holds exactly 1 MiB of text (the last one the rest), whatever the sizes of the calls: the bytes
   // written are a function of the text alone.  A run that starts over on re-framed input (fq_respawn.h) skips as many
   // bytes of its stdout as the first run wrote - they must be the same bytes, though the two runs cut their input into
@@ -263,8 +272,9 @@ class GzipMembers {
   }
 
  private:
-  bool put(const std::vector<uint8_t>& m) {
-    if (fwrite(m.data(), 1, m.size(), f_) != m.size()) {
+  bool put(const std::vector<uint8_t>& m) { return put(m.data(), m.size()); }
+  bool put(const uint8_t* m, size_t n) {
+    if (fwrite(m, 1, n, f_) != n) {
       err_ = name_ + ": " + strerror(errno);
       return false;
     }

@@ -661,10 +661,24 @@ int fqg_bam2fastq_output(fqg_ctx *ctx, int stream_id, void *host_dst, uint64_t n
  * they share such a word with a byte of the text - a caller who sub-allocates must own those words.  FQG_ERR_ARG (the
  * result of the previous call then stays as it was): carry_bytes >=
  * FQG_GZ_MEMBER_TEXT, a store or stream that does not exist, more bytes asked of fqg_deflate_output than gz_bytes +
- * tail_bytes. */
+ * tail_bytes.
+ *
+ * fqg_bgzf_deflate / fqg_text_bgzf_deflate are the same calls with BGZF's framing (SAM/BAM specification 4.1): every
+ * member is a BGZF block - the eighteen header bytes 1f 8b 08 04 00000000 00 ff 06 00 'B' 'C' 02 00 BSIZE (BSIZE: the
+ * block's bytes - 1), the SAME deflate block as the gzip member of that text, CRC-32 and ISIZE; a block of n text bytes
+ * has at most n + 31 bytes, so a full one fits BSIZE.  With final != 0 the 28-byte end-of-file block follows the last
+ * block; it is counted in gz_bytes and not in n_members, and an empty text with final is that block alone.  Here
+ * `carry` may have any length (a BAM header in front of the records can be many blocks long).  Result, tail and
+ * fqg_deflate_output as above; the bytes depend on the text and FQG_GZ_MEMBER_TEXT alone.
+ *
+ * fqg_deflate_output_begin starts the copy fqg_deflate_output makes and returns; host_dst should be pinned memory
+ * (fqg_host_alloc) for the copy to be asynchronous.  fqg_deflate_output_wait returns when it has landed; the next
+ * deflate call waits for it by itself (it writes the same device buffer). */
 #define FQG_GZ_MEMBER_TEXT 65280u
 #define FQG_TEXT_RECORDS 0   /* what fqg_barcodes_transform / fqg_records_filter / _gather / _split produced last */
 #define FQG_TEXT_BAM2FASTQ 1 /* what fqg_bam2fastq produced last */
+#define FQG_TEXT_BAM_TAGS 2  /* what fqg_bam_add_tags produced last (stream 0: the records; reading it leaves it as it is); \
+                                no store, FQG_ERR_ARG, on a context that has not called fqg_bam_add_tags yet */
 typedef struct {
   uint64_t text_bytes, n_members, gz_bytes, tail_bytes;
 } fqg_deflate_result;
@@ -672,7 +686,13 @@ int fqg_deflate(fqg_ctx *ctx, const void *carry, uint64_t carry_bytes, const voi
                 fqg_deflate_result *out);
 int fqg_text_deflate(fqg_ctx *ctx, int store, int stream, const void *carry, uint64_t carry_bytes, int final,
                      fqg_deflate_result *out);
+int fqg_bgzf_deflate(fqg_ctx *ctx, const void *carry, uint64_t carry_bytes, const void *src, uint64_t nbytes, int mem, int final,
+                     fqg_deflate_result *out);
+int fqg_text_bgzf_deflate(fqg_ctx *ctx, int store, int stream, const void *carry, uint64_t carry_bytes, int final,
+                          fqg_deflate_result *out);
 int fqg_deflate_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
+int fqg_deflate_output_begin(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
+int fqg_deflate_output_wait(fqg_ctx *ctx);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,16 @@
-"""The device deflate compressor (fqg_deflate, FQGPU_GZIP_GPU=1) on one box: python tools/gzip_gpu_quick.py [million reads]
+"""The device deflate compressor (fqg_deflate, FQGPU_GZIP_GPU=1) on one box: python tools/gzip_gpu_quick.py [million reads [bin]]
 
   kernels   GB/s of text through fqg_deflate's kernels (fqg_profile_*), the text device-resident: synthetic 150-base reads
             of fqg_synth_fastq, and the inflated FASTQ fixtures under tests/golden/data
   sizes     gzip bytes / text bytes of the same texts: the device members, zlib level 1 and the reference's level 4 on
             the same cuts, and FQGPU_GZIP_FAST's members on its own cuts (1 MiB)
   programs  wall time of bin/fastq_split_interleaved and bin/fastq_trim_poly_at on the synthetic reads (interleaved, a
-            plain file) in three modes: default, FQGPU_GZIP_FAST=1, FQGPU_GZIP_GPU=1; and the size of what they wrote
+            plain file) in three modes: default, FQGPU_GZIP_FAST=1, FQGPU_GZIP_GPU=1; and the size of what they wrote;
+            bin/fastq_pre_barcodes with both out-files on the two mate files, in the record-block loop and in the serial
+            loop (FQGPU_SERIAL_LOOP=1); bin/bam_add_tags on a BAM made from a quarter of the same reads (default and
+            FQGPU_GZIP_GPU=1: FQGPU_GZIP_FAST does not apply to BGZF), with the kernel time of fqg_bgzf_deflate on its
+            stream.  `bin`: the folder of the programs (default: this tree's), to run another build of them - the parent
+            commit's - through the same legs in the same session
 
 One JSON document on stdout.  No speed or size is asserted here: the numbers go to profiles/."""
 import glob
@@ -21,6 +26,7 @@ import zlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import fastq_utils_amd as fq  # noqa: E402
@@ -28,6 +34,7 @@ import fastq_utils_amd as fq  # noqa: E402
 M = fq.abi.GZ_MEMBER_TEXT
 RUNS = 5
 reads = int(float(sys.argv[1]) * 1e6) if len(sys.argv) > 1 else 2_000_000
+BIN = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(REPO, "bin")
 
 
 def zlib_ratio(data, level, cut):
@@ -38,14 +45,14 @@ def zlib_ratio(data, level, cut):
     return total / max(1, len(data))
 
 
-def device_run(ctx, ptr, nbytes):
+def device_run(ctx, ptr, nbytes, bgzf=False):
     """(median kernel ms of the members kernel, of all deflate kernels, median wall ms, gzip bytes)"""
     kern, every, wall, size = [], [], [], 0
     for rep in range(RUNS + 1):
         ctx.profile(True)
         ctx.profile_reset()
         t0 = time.perf_counter()
-        r = ctx.deflate(ptr, nbytes=nbytes, want_output=False)
+        r = (ctx.bgzf_deflate if bgzf else ctx.deflate)(ptr, nbytes=nbytes, want_output=False)
         ctx.synchronize()
         t1 = time.perf_counter()
         prof = ctx.profile_read()
@@ -69,7 +76,44 @@ def fast_ratio(path):
     return int(st["out"]) / max(1, int(st["in"]))
 
 
-out = {"member_text": M, "runs": RUNS, "texts": {}, "programs": {}}
+def bam_of(text, n, R):
+    """an unaligned BAM stream of the first n synthetic records (R bytes each, 150 bases): the names as
+    fastq_pre_barcodes writes them (STAGS_CELL=.._UMI=.._SAMPLE=.._ETAGS_<name>), the reads' bases and qualities"""
+    L = 150
+    a = np.frombuffer(text, dtype=np.uint8, count=n * R).reshape(n, R)
+    rng = np.random.default_rng(1)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    name = a[:, 1:R - (2 * L + 5)].copy()
+    name[name == 32] = 95
+    parts = [np.broadcast_to(np.frombuffer(b"STAGS_CELL=", dtype=np.uint8), (n, 11)), acgt[rng.integers(0, 4, (n, 16))],
+             np.broadcast_to(np.frombuffer(b"_UMI=", dtype=np.uint8), (n, 5)), acgt[rng.integers(0, 4, (n, 10))],
+             np.broadcast_to(np.frombuffer(b"_SAMPLE=", dtype=np.uint8), (n, 8)), acgt[rng.integers(0, 4, (n, 8))],
+             np.broadcast_to(np.frombuffer(b"_ETAGS_", dtype=np.uint8), (n, 7)), name, np.zeros((n, 1), dtype=np.uint8)]
+    qname = np.concatenate(parts, axis=1)
+    code = np.full(256, 15, dtype=np.uint8)
+    for ch, v in zip(b"ACGT", (1, 2, 4, 8)):
+        code[ch] = v
+    nib = code[a[:, R - (2 * L + 4):R - (L + 4)]]
+    seq = (nib[:, 0::2] << 4) | nib[:, 1::2]
+    qual = a[:, R - (L + 1):R - 1] - 33
+    body = 32 + qname.shape[1] + 4 + L // 2 + L
+    core = np.zeros((n, 36), dtype=np.uint8)
+    core[:, 0:4] = np.frombuffer(np.uint32(body).tobytes(), dtype=np.uint8)
+    core[:, 4:8] = 255                                                 # refID -1
+    core[:, 8:12] = 255                                                # pos -1
+    core[:, 12] = qname.shape[1]                                       # l_read_name, mapq 0
+    core[:, 14:16] = np.frombuffer(np.uint16(4680).tobytes(), dtype=np.uint8)  # bin
+    core[:, 16] = 1                                                    # one CIGAR operation
+    core[:, 18] = 4                                                    # flag: unmapped
+    core[:, 20:24] = np.frombuffer(np.uint32(L).tobytes(), dtype=np.uint8)
+    core[:, 24:32] = 255                                               # mate refID, mate pos -1
+    cigar = np.broadcast_to(np.frombuffer(np.uint32(L << 4).tobytes(), dtype=np.uint8), (n, 4))
+    recs = np.concatenate([core, qname, cigar, seq, qual], axis=1)
+    head = b"@HD\tVN:1.0\tSO:unsorted\n"
+    return b"BAM\x01" + len(head).to_bytes(4, "little") + head + (0).to_bytes(4, "little") + recs.tobytes()
+
+
+out = {"member_text": M, "runs": RUNS, "bin": os.path.relpath(BIN, REPO), "texts": {}, "programs": {}}
 with fq.Context(0) as ctx, tempfile.TemporaryDirectory() as tmp:
     R = fq.abi.synth_record_bytes(150)
     texts = {}
@@ -118,24 +162,57 @@ with tempfile.TemporaryDirectory() as tmp:
         with open(src, "wb") as f:
             f.write(bytes(inter.cpu().numpy()))
         del m, inter
+        # the mates as two files, and an unaligned BAM of a quarter of the reads (the stream compressed by the device: any
+        # BGZF file does as input)
+        mates = [os.path.join(tmp, "r%d.fastq" % k) for k in (1, 2)]
+        with open(src, "rb") as f:
+            both = np.frombuffer(f.read(), dtype=np.uint8).reshape(half // 2, 2, R)
+        for k in (0, 1):
+            with open(mates[k], "wb") as f:
+                f.write(both[:, k, :].tobytes())
+        n_bam = half // 4
+        stream = bam_of(both.tobytes(), n_bam, R)
+        del both
+        bam = os.path.join(tmp, "reads.bam")
+        with open(bam, "wb") as f:
+            f.write(ctx.bgzf_deflate(stream)["members"])
+        dev = torch.frombuffer(bytearray(stream), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        k_ms, all_ms, wall_ms, size = device_run(ctx, dev.data_ptr(), len(stream), bgzf=True)
+        out["texts"]["bam_stream_bgzf"] = {"bytes": len(stream), "blocks": -(-len(stream) // M), "k_deflate_members_ms": round(k_ms, 3),
+                                           "deflate_kernels_ms": round(all_ms, 3), "call_wall_ms": round(wall_ms, 3),
+                                           "kernel_GBps": round(len(stream) / all_ms / 1e6, 2), "ratio_device": round(size / len(stream), 4)}
+        bam_bytes = len(stream)
+        del dev, stream
     text_bytes = os.path.getsize(src)
-    for prog, args in (("fastq_split_interleaved", [src, os.path.join(tmp, "o")]),
-                       ("fastq_trim_poly_at", ["--file", src, "--outfile", os.path.join(tmp, "o.fastq.gz")])):
-        out["programs"][prog] = {"input_bytes": text_bytes}
-        for mode, env in modes.items():
+    barcodes = ["--read1", mates[0], "--read2", mates[1], "--umi_read", "read1", "--umi_offset", "0", "--umi_size", "8", "--read1_offset", "8",
+                "--phred_encoding", "33", "--outfile1", os.path.join(tmp, "o1.fastq.gz"), "--outfile2", os.path.join(tmp, "o2.fastq.gz")]
+    serial = {"FQGPU_SERIAL_LOOP": "1"}
+    host_only = {m: v for m, v in modes.items() if "FAST" not in m}
+    for leg, prog, args, extra, leg_modes, in_bytes in (
+            ("fastq_split_interleaved", "fastq_split_interleaved", [src, os.path.join(tmp, "o")], {}, modes, text_bytes),
+            ("fastq_trim_poly_at", "fastq_trim_poly_at", ["--file", src, "--outfile", os.path.join(tmp, "o.fastq.gz")], {}, modes, text_bytes),
+            ("fastq_pre_barcodes (block loop)", "fastq_pre_barcodes", barcodes, {}, modes, text_bytes),
+            ("fastq_pre_barcodes (serial loop)", "fastq_pre_barcodes", barcodes, serial, modes, text_bytes),
+            ("bam_add_tags", "bam_add_tags", ["--inbam", bam, "--outbam", os.path.join(tmp, "o.bam.gz")], {}, host_only, bam_bytes)):
+        out["programs"][leg] = {"input_bytes": in_bytes}
+        for mode, env in leg_modes.items():
             e = dict(os.environ)
-            for k in ("FQGPU_GZIP_GPU", "FQGPU_GZIP_FAST", "FQGPU_GZIP_LEVEL"):
+            for k in ("FQGPU_GZIP_GPU", "FQGPU_GZIP_FAST", "FQGPU_GZIP_LEVEL", "FQGPU_SERIAL_LOOP", "FQGPU_DEVICES"):
                 e.pop(k, None)
+            e.update(extra)
             e.update(env)
             wall = []
             for rep in range(3):
                 t0 = time.perf_counter()
-                p = subprocess.run([os.path.join(REPO, "bin", prog)] + args, env=e, capture_output=True)
+                p = subprocess.run([os.path.join(BIN, prog)] + args, env=e, capture_output=True)
                 wall.append(time.perf_counter() - t0)
                 assert p.returncode == 0, p.stderr[-400:]
             written = sum(os.path.getsize(p) for p in glob.glob(os.path.join(tmp, "o*.gz")))
-            out["programs"][prog][mode] = {"wall_s": [round(w, 3) for w in wall], "median_wall_s": round(statistics.median(wall), 3),
-                                           "gz_bytes": written, "ratio": round(written / text_bytes, 4)}
+            text = sum(len(gzip.open(p).read()) for p in glob.glob(os.path.join(tmp, "o*.gz")))
+            out["programs"][leg][mode] = {"wall_s": [round(w, 3) for w in wall], "median_wall_s": round(statistics.median(wall), 3),
+                                          "gz_bytes": written, "ratio": round(written / in_bytes, 4), "text_bytes": text,
+                                          "ratio_of_text": round(written / max(1, text), 4)}
             for p in glob.glob(os.path.join(tmp, "o*.gz")):
                 os.remove(p)
 print(json.dumps(out, indent=1))
