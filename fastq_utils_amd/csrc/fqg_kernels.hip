@@ -571,14 +571,29 @@ __device__ __forceinline__ uint32_t dpp0(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, true);
 }
 // inclusive scan over the 64 lanes in 7 DPP adds (no LDS traffic)
+// Every stage is ONE v_add_u32 that carries the DPP modifier.  (From update_dpp() and `+` the compiler makes a v_mov_b32_dpp
+// per stage and joins the adds of the first three stages into v_add3_u32, which cannot take one.)  A lane that row_mask /
+// bank_mask switch off, or whose source lane does not exist, keeps its value: the destination is also the plain operand,
+// and only the first stage - whose destination holds nothing yet - reads a missing lane as 0 (bound_ctrl).
+// The wait states are written out, the compiler does not look into the text: a DPP operand needs two behind the vector
+// instruction that wrote it and five behind a vector instruction that wrote EXEC.
 __device__ __forceinline__ uint32_t wave_scan_incl_dpp(uint32_t v) {
-  uint32_t x = v + dpp0<0x111, 0xf, 0xf>(v);
-  x += dpp0<0x112, 0xf, 0xf>(v);
-  x += dpp0<0x113, 0xf, 0xf>(v);
-  x += dpp0<0x114, 0xf, 0xe>(x);
-  x += dpp0<0x118, 0xf, 0xc>(x);
-  x += dpp0<0x142, 0xa, 0xf>(x);
-  x += dpp0<0x143, 0xc, 0xf>(x);
+  uint32_t x;
+  asm volatile(
+      "s_nop 4\n\t"
+      "v_add_u32_dpp %0, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_u32_dpp %0, %1, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_u32_dpp %0, %1, %0 row_shr:3 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xe\n\t"
+      "s_nop 1\n\t"
+      "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+      "s_nop 1\n\t"
+      "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+      : "=&v"(x)
+      : "v"(v));
   return x;
 }
 

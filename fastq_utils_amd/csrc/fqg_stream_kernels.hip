@@ -31,6 +31,7 @@
 // per-chunk ranges and of redone chunks) and the image flags that force the two-pass / exact path.
 #include "fqg_device.h"
 #include "fqg_type_spans.h"
+#include "fqg_mark_pack.h"
 
 namespace fqg {
 
@@ -192,7 +193,7 @@ __device__ __forceinline__ uint32_t stage_entry(uint32_t ent, uint32_t c1) {
 template <uint32_t ABL>
 __device__ __forceinline__ void stage_chunk(const uint8_t* __restrict__ img, uint64_t n, uint64_t cb, uint32_t chunk,
                                             const uint32_t (&nl)[kHalves], const uint32_t (&nl2)[kHalves],
-                                            const uint32_t (&ex)[kHalves], uint32_t tot,
+                                            const uint32_t (&ex)[kHalves], uint32_t tot, bool fits,
                                             uint16_t* __restrict__ slots, const uint8_t* __restrict__ copy,
                                             uint32_t tail, uint16_t* __restrict__ stage, bool interior) {
   const int lane = lane_id();
@@ -200,6 +201,19 @@ __device__ __forceinline__ void stage_chunk(const uint8_t* __restrict__ img, uin
   for (int k = 0; k < kHalves; ++k) {
     uint32_t m = nl[k], r = ex[k];
     const uint32_t at = (uint32_t)k * kHalfBytes + (uint32_t)lane * kLaneBytes;
+    if (fits) {
+      // every rank of the chunk has a slot (`fits` is uniform: total <= kStageCap): no test per newline.  The entry is the
+      // bit of nl2 on top of (at | j) - v_bfe_u32, v_or_b32 and one v_lshl_or_b32; `at` holds the slice and has its low five
+      // bits clear.  (as_computed: or the compiler shifts the bit by itself and joins the three with a v_or3_b32.)
+      while (m) {
+        const uint32_t j = (uint32_t)__builtin_ctz(m);
+        m &= m - 1;
+        slots[r] = (uint16_t)((__builtin_amdgcn_ubfe(nl2[k], j, 1u) << 14) | as_computed(at | j));
+        ++r;
+      }
+      continue;
+    }
+    // (a chunk with more newlines than slots: the image is abandoned to the two-pass path, kFlagStageOverflow)
     while (m) {
       const uint32_t j = (uint32_t)__builtin_ctz(m);
       m &= m - 1;
@@ -275,11 +289,8 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
 #pragma unroll
     for (int k = 0; k < kHalves; ++k) {
       hiacc = or3(or3(or3(or3(hiacc, v[k].a.x, v[k].a.y), v[k].a.z, v[k].a.w), v[k].b.x, v[k].b.y), v[k].b.z, v[k].b.w);
-      const uint32_t lo = pack_marks16(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc),
-                                       nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc));
-      const uint32_t hi = pack_marks16(nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc),
-                                       nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
-      nl[k] = lo | (hi << 16);
+      nl[k] = pack_marks32(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc), nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc),
+                           nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc), nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
     }
     const bool high = __ballot((hiacc & kH) != 0) != 0;
     const bool ctrl = __ballot((badacc & kH) != 0) != 0;
@@ -398,15 +409,13 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
 #pragma unroll
       for (int k = 0; k < kHalves; ++k) {
         const uint4 &a = v[k].a, &b = v[k].b;
-        const uint32_t inv = pack_marks16(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w)) |
-                             (pack_marks16(not_acgtn7(b.x), not_acgtn7(b.y), not_acgtn7(b.z), not_acgtn7(b.w)) << 16);
+        const uint32_t inv = pack_marks32(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w), not_acgtn7(b.x), not_acgtn7(b.y),
+                                          not_acgtn7(b.z), not_acgtn7(b.w));
         const uint32_t bad = (ABL & 8u) ? 0u : inv & M1[k];
         if (bad) queue_suspect(o, cs, wb + (uint64_t)k * kHalfBytes + (uint32_t)__builtin_ctz(bad));
-        const uint32_t okq =
-            pack_marks16(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
-                         in_range7a(a.w, lo_add, hihb, khv)) |
-            (pack_marks16(in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv), in_range7a(b.z, lo_add, hihb, khv),
-                          in_range7a(b.w, lo_add, hihb, khv)) << 16);
+        const uint32_t okq = pack_marks32(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
+                                          in_range7a(a.w, lo_add, hihb, khv), in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv),
+                                          in_range7a(b.z, lo_add, hihb, khv), in_range7a(b.w, lo_add, hihb, khv));
         const uint32_t qm = (ABL & 16u) ? 0u : M3[k];
         if (__ballot((qm & ~okq) != 0)) {  // rare: exact range of this slice's quality bytes
           any_viol = true;
@@ -471,7 +480,7 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
   }
 
   if (!(ABL & 2u)) {
-    stage_chunk<ABL>(img, n, cb, chunk, nl, nl2, ex, tot, s_slots[wv], copy, tail, o.stage, interior);
+    stage_chunk<ABL>(img, n, cb, chunk, nl, nl2, ex, tot, total <= (uint32_t)kStageCap, s_slots[wv], copy, tail, o.stage, interior);
   }
   if constexpr (NAMES == 2) {
     // ---- header lines that begin in this chunk -> 16-byte digests: canonical name + hash, four lanes per header ----
