@@ -9,18 +9,18 @@
 #include <getopt.h>
 #include <unistd.h>
 
-#include <algorithm>
 #include <chrono>
 #include <deque>
-#include <set>
 #include <functional>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "fq_blocks.h"
-#include "fq_input.h"
+#include "fq_common.h"
 #include "fq_multi.h"
 #include "fq_ordered.h"
+#include "fq_out_pool.h"
 #include "fq_parallel.h"
 
 // SURVEY 5 "metrics", as bin/fastq_info has it: FQGPU_JSON_METRICS=<file> writes the machine-readable twin of the
@@ -40,33 +40,7 @@ static void pb_json_metrics(long processed, long discarded, size_t devices) {
   fclose(jf);
 }
 
-using namespace fqhost;
-
 namespace {
-
-fqg_ctx* g_ctx = nullptr;
-[[noreturn]] void die_lib(const char* what, int rc) {
-  FQ_PRINT_ERROR("GPU library failure in %s (%d): %s", what, rc, g_ctx ? fqg_last_error(g_ctx) : "no context");
-  fqhost::leave(kExitSys);
-}
-#define LIB(call)                        \
-  do {                                   \
-    int rc__ = (call);                   \
-    if (rc__ != 0) die_lib(#call, rc__); \
-  } while (0)
-#define FQ_PRINT_INFO(...)        \
-  do {                            \
-    fprintf(stderr, "INFO:");     \
-    fprintf(stderr, __VA_ARGS__); \
-    fprintf(stderr, "\n");        \
-  } while (0)
-
-size_t piece_bytes() {
-  const char* e = getenv("FQGPU_CHUNK_MB");
-  size_t mb = e ? strtoull(e, nullptr, 10) : 512;
-  if (mb < 1) mb = 1;
-  return mb << 20;
-}
 
 enum { READ1 = 1, READ2 = 2, INDEX1 = 3, INDEX2 = 4, INDEX3 = 5 };
 
@@ -115,45 +89,6 @@ void print_usage() {  // src/fastq_pre_barcodes.c:311-346
   fprintf(stderr, "%s\n", msg);
 }
 
-// one input: pieces, frames, and where the next iteration reads
-struct Source {
-  const char* path = nullptr;
-  Input* in = nullptr;
-  fqg_frame* frame = nullptr;
-  fqg_file_state st{};
-  bool probed = false;
-  std::string format_line;
-  uint64_t avail = 0;       // complete records in the current frame
-  long use = 0;             // local index of the record the next iteration uses (may exceed avail)
-  uint64_t records_before = 0;  // records in earlier frames
-  bool final_piece = false;
-  int tail_lines = 0;
-  bool open_end = false;    // the file's last line has no '\n' and closes its last complete record: gzgets reads it up
-                            // to the end of the file, and the file is at its end for gzeof from then on
-  bool exhausted = false;   // no more data will come
-  bool carry_pending = false;
-  size_t carry_at = 0;      // bytes of the current piece covered by complete records
-};
-
-// state of the first record + the line fastq_get_readname prints on its first call for the file
-bool probe_bytes(const char* data, size_t size, fqg_file_state* st, std::string* format_line) {
-  st->is_pe = 1;
-  if (fqg_probe_first_record(data, size, 1, st) != 0) return false;
-  if (st->readname_format == FQG_NAME_CASAVA18) *format_line = "CASAVA=1.8\n";
-  else if (st->readname_format == FQG_NAME_INTEGER) {
-    // INTEGERNAME and NOP share a value; the text differs (src/fastq.c:465-474)
-    const char* nl = static_cast<const char*>(memchr(data, '\n', size));
-    std::string h(data + 1, nl ? (size_t)(nl - data) : size - 1);
-    const std::string name = h.c_str();
-    size_t i = 0;
-    while (i < name.size() && name[i] >= '0' && name[i] <= '9') ++i;
-    const std::string rest = name.substr(i);
-    const bool all_digits = i > 0 && (rest.empty() || rest == "\n" || rest == "\r");
-    *format_line = all_digits ? "Read name provided as an integer\n" : "Read name provided with no suffix\n";
-  }
-  return true;
-}
-
 // The reference reads a line beyond its gzgets buffers in pieces (src/fastq.c:249-253) and goes on out of step, every
 // piece a line of its own.  Everything in front of this piece of input went the reference's way; the program runs itself
 // again, as a child and on one device, on input that is cut where gzgets cuts it (fq_respawn.h, fq_reframe.h: inflated
@@ -171,10 +106,183 @@ std::function<void()> g_before_respawn;  // (the one-device loop: text still on 
   fqhost::leave(kExitSys);
 }
 
-void probe(Source& s) {
-  if (s.probed || s.in->size() == 0) return;
-  s.probed = probe_bytes(s.in->data(), s.in->size(), &s.st, &s.format_line);
+// ---- what the two loops share: how a piece of input is framed, what a batch says and counts once
+// fqg_barcodes_transform has returned, how its text comes back and is written, and how the run ends -----------------
+
+// A piece of one input that starts at a record boundary, framed.  A header line that starts with a NUL byte is "no
+// entry" for the reference (src/fastq.c:250): the input ends HERE, cleanly, whatever follows, and the records in front of
+// it are framed once more, alone.  Another line of a record that starts with NUL is an empty string: the file is
+// truncated THERE (src/fastq.c:254; tail_lines > 0), whatever follows.
+struct Framed {
+  fqg_validate_result r{};
+  bool ends_here = false, cut_short = false;
+  bool final = false;     // no record of the input lies behind this piece
+  int tail_lines = 0;
+  bool open_end = false;  // the file's last line has no '\n' and closes its last complete record: gzgets reads it up
+                          // to the end of the file, and the file is at its end for gzeof from then on
+};
+// 0, or the status of the library call *what that failed.  A line beyond the gzgets limits comes back as
+// f->r.code == FQG_E_LINE_TOO_LONG with nothing else decided; the frame is the caller's to retain.
+int frame_piece(fqg_ctx* c, const char* data, size_t size, bool final, const fqg_file_state* st, uint32_t flags, Framed* f,
+                const char** what) {
+  *f = Framed{};
+  *what = "fqg_validate";
+  fqg_validate_result& r = f->r;
+  int rc = fqg_validate(c, nullptr, data, size, FQG_MEM_HOST, final ? 1 : 0, st, FQG_VALIDATE_FRAME_ONLY | flags, &r);
+  if (rc || r.code == FQG_E_LINE_TOO_LONG) return rc;
+  f->ends_here = r.stopped != 0;
+  if (f->ends_here && (rc = fqg_validate(c, nullptr, data, r.consumed, FQG_MEM_HOST, 1, st, FQG_VALIDATE_FRAME_ONLY | flags, &r))) return rc;
+  f->cut_short = !f->ends_here && r.code == FQG_E_TRUNCATED && !final;
+  f->final = final || f->ends_here || f->cut_short;
+  f->tail_lines = f->ends_here ? 0 : r.tail_lines;
+  f->open_end = final && !f->ends_here && r.tail_lines == 0 && r.n_records > 0 && size > 0 && data[size - 1] != '\n';
+  return 0;
 }
+
+// how an input stood when its loop ended
+struct InputEnd {
+  bool drained = false;     // nothing of it is left for another iteration, and nothing more will come
+  bool at_end = false;      // the next read would begin exactly behind its last complete record ...
+  bool one_beyond = false;  // ... or one record further (the serial loop's second --interleaved reference)
+  bool open_end = false;    // Framed::open_end of its last piece
+  int tail_lines = 0;       // lines of an incomplete record behind the last complete one
+  uint64_t records = 0;     // complete records of the file up to there
+};
+
+// the header line of a FQG_E_WRONG_HEADER finding, and its line number by the file's own counter (src/fastq.c:448-451)
+struct WrongHeader {
+  unsigned long line;
+  std::string text;
+};
+
+struct Batches {
+  const char* const* file = nullptr;
+  const fqg_barcode_params* P = nullptr;
+  GzipMembers* outgz = nullptr;
+  int num_input_files = 0;
+  uint64_t scale = 1;  // 2 with --interleaved input: an iteration takes two reads of the file, the ticker counts reads
+  Probe pr[6];         // state of every input's first record + the line fastq_get_readname prints on its first call
+  unsigned long processed = 0, discarded = 0;
+  bool first = true;
+
+  // Before the batch's text goes out: the format lines of the first fastq_get_readname call per file, in file order
+  // (src/fastq.c:459-485) - up to the file whose first header is wrong -, and the warnings.
+  void announce(const fqg_barcode_result& r) {
+    if (first && num_input_files > 1)
+      for (int x = READ1; x <= INDEX3; ++x)
+        if (file[x]) {
+          if (r.code == FQG_E_WRONG_HEADER && r.iteration == 0 && r.file == x) break;
+          print_probe(pr[x]);
+        }
+    first = false;
+    for (uint64_t w = 0; w < r.n_short; ++w) fputs("Warning: Read too short - barcode not found\n", stderr);
+  }
+  // Behind it: the counters, the ticker and - after `flush` has brought out what the loop still holds - the finding
+  // that ends the run.
+  void count(const fqg_barcode_result& r, const std::function<void()>& flush, const std::function<WrongHeader()>& wrong_header) {
+    const unsigned long before = processed;
+    processed += r.n_done;
+    discarded += r.n_discarded;
+    ticker(before + 1, processed, 100000, scale);
+    if (r.code == FQG_OK) return;
+    flush();
+    if (r.code == FQG_E_WRONG_HEADER) {
+      const WrongHeader h = wrong_header();
+      fail_wrong_header(file[r.file], h.line, h.text);
+    }
+    FQ_PRINT_ERROR("Readnames do not match across files (read #%ld)", (long)(processed + 1));
+    fqhost::leave(kExitFormat);
+  }
+  // The loop is over.  An incomplete record where the next read would have happened is a truncated file
+  // (src/fastq.c:254-257); a clean end of any input just ends the loop.  The first input, in file order, that has nothing
+  // left decides - unless the loop's own condition ends it first (fastq_files_eof, src/fastq_pre_barcodes.c:288-297,
+  // :594): an input whose last line has no '\n' is at its end for gzeof once that line has been read, and no input is
+  // read again.
+  [[noreturn]] void finish(const InputEnd* end, size_t devices) {
+    bool loop_condition_ends_it = false;
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (file[x] && end[x].drained && end[x].at_end && end[x].open_end) loop_condition_ends_it = true;
+    for (int x = READ1; x <= INDEX3 && !loop_condition_ends_it; ++x)
+      if (file[x] && end[x].drained) {
+        if (end[x].tail_lines > 0 && (end[x].at_end || end[x].one_beyond)) fail_truncated(file[x], (unsigned long)(4 * end[x].records));
+        break;
+      }
+    FQ_PRINT_INFO("Reads processed: %ld", (long)processed);
+    FQ_PRINT_INFO("Reads discarded: %ld", (long)discarded);
+    if (!P->out_sam)
+      for (int x = READ1; x <= READ2; ++x)
+        if (P->emit[x] && !outgz[x].close()) {
+          FQ_PRINT_ERROR("unable to close file descriptor");
+          fqhost::leave(kExitSys);
+        }
+    fflush(stdout);
+    pb_json_metrics((long)processed, (long)discarded, devices);
+    fqhost::leave(0);
+  }
+};
+
+// One output's text of one batch on its way from the GPU to its file: `size` bytes in a buffer of the pool - the
+// text, or (FQGPU_GZIP_GPU=1, loops on one context) gz_bytes of gzip members and behind them the text that filled none.
+struct OutText {
+  char* buf = nullptr;
+  size_t cap = 0, size = 0, gz_bytes = 0;
+  bool members = false;
+};
+
+// The fetch step for output `which` of the transform that has just run on `c`: in device mode the text is compressed
+// where it lies, `carry` (the tail of the batch before, docs/host_gzip.md section 3) in front; a buffer of the pool;
+// the copy into it - `beside`: on the library's copy stream, beside what the caller does next, until fetch_wait; else
+// made when this returns (fqg_*_output is a copy on the context's own stream, not _begin + _wait).
+// 0, or the status of the call *what that failed.
+int fetch_begin(fqg_ctx* c, OutPool& pool, int which, size_t text_bytes, bool device_mode, const std::string& carry, bool beside,
+                OutText* o, const char** what) {
+  *o = OutText{};
+  o->members = device_mode;
+  o->size = text_bytes;
+  if (o->members) {
+    fqg_deflate_result dr;
+    *what = "fqg_text_deflate";
+    if (const int rc = fqg_text_deflate(c, FQG_TEXT_RECORDS, which, carry.data(), carry.size(), 0, &dr)) return rc;
+    o->gz_bytes = dr.gz_bytes;
+    o->size = dr.gz_bytes + dr.tail_bytes;
+  }
+  *what = "no pinned memory for the output text";
+  if (!(o->buf = pool.take(o->size, &o->cap))) return FQG_ERR_NOMEM;
+  if (o->members) {
+    *what = beside ? "fqg_deflate_output_begin" : "fqg_deflate_output";
+    return beside ? fqg_deflate_output_begin(c, o->buf, o->size) : fqg_deflate_output(c, o->buf, o->size);
+  }
+  *what = beside ? "fqg_barcodes_output_begin" : "fqg_barcodes_output";
+  return beside ? fqg_barcodes_output_begin(c, which, o->buf, o->size) : fqg_barcodes_output(c, which, o->buf, o->size);
+}
+// ... and its end: the copy has landed, and the tail that came with it is the carry of the next batch
+int fetch_wait(fqg_ctx* c, const OutText& o, std::string* carry) {
+  const int rc = o.members ? fqg_deflate_output_wait(c) : fqg_barcodes_output_wait(c);
+  if (!rc && o.members) carry->assign(o.buf + o.gz_bytes, o.size - o.gz_bytes);
+  return rc;
+}
+// the write step (0: the SAM text to stdout; device mode: the members, and the tail for close())
+bool write_out(GzipMembers* gz, int which, const OutText& o) {
+  if (which == 0) return fwrite(o.buf, 1, o.size, stdout) == o.size;
+  return o.members ? gz[which].write_members(o.buf, o.gz_bytes, o.buf + o.gz_bytes, o.size - o.gz_bytes) : gz[which].write(o.buf, o.size);
+}
+size_t outputs_per_batch(const fqg_barcode_params& P) {
+  return P.out_sam ? 1 : std::max<size_t>((size_t)((P.emit[1] ? 1 : 0) + (P.emit[2] ? 1 : 0)), 1);
+}
+
+// ---- the serial loop's input: pieces, frames, and where the next iteration reads ------------------------------------
+struct Source {
+  Input* in = nullptr;
+  Probe* pr = nullptr;  // (Batches::pr)
+  fqg_frame* frame = nullptr;
+  uint64_t avail = 0;           // complete records in the current frame
+  long use = 0;                 // local index of the record the next iteration uses (may exceed avail)
+  uint64_t records_before = 0;  // records in earlier frames
+  Framed f;                     // the current piece
+  bool exhausted = false;       // no more data will come
+  bool carry_pending = false;
+  size_t carry_at = 0;          // bytes of the current piece covered by complete records
+};
 
 // frame the next piece of `s`; false when the input is used up
 bool refill(Source& s) {
@@ -194,418 +302,273 @@ bool refill(Source& s) {
     s.exhausted = true;
     return false;
   }
-  probe(s);
-  fqg_validate_result r;
-  LIB(fqg_validate(g_ctx, nullptr, s.in->data(), s.in->size(), FQG_MEM_HOST, s.in->final() ? 1 : 0, &s.st,
-                   FQG_VALIDATE_FRAME_ONLY | s.in->vflags(), &r));
-  if (r.code == FQG_E_LINE_TOO_LONG) refuse_long_line(s.in->path().c_str(), s.records_before + r.record);
-  bool ends_here = r.stopped != 0;  // a header line that starts with a NUL byte: "no entry" (src/fastq.c:250), the input ends
-  if (ends_here)  // the records in front of it, framed alone
-    LIB(fqg_validate(g_ctx, nullptr, s.in->data(), r.consumed, FQG_MEM_HOST, 1, &s.st, FQG_VALIDATE_FRAME_ONLY | s.in->vflags(), &r));
-  // a record with a sequence / second header / quality line that starts with NUL: an empty string to the reference - the
-  // file is truncated THERE (src/fastq.c:254; tail_lines > 0), whatever follows
-  const bool cut_short = !ends_here && r.code == FQG_E_TRUNCATED && !s.in->final();
-  s.final_piece = s.in->final() || ends_here || cut_short;
-  s.tail_lines = r.tail_lines;
-  s.open_end = s.final_piece && !ends_here && r.tail_lines == 0 && r.n_records > 0 && s.in->size() > 0 && s.in->data()[s.in->size() - 1] != '\n';
-  s.avail = r.n_records;
-  if (r.n_records) LIB(fqg_frame_retain(g_ctx, &s.frame));
-  if (!s.in->final() && !ends_here && !cut_short) {
+  probe_piece(*s.pr, s.in->data(), s.in->size(), 1);
+  const char* what;
+  if (const int rc = frame_piece(g_ctx, s.in->data(), s.in->size(), s.in->final(), &s.pr->st, s.in->vflags(), &s.f, &what)) die_lib(what, rc);
+  if (s.f.r.code == FQG_E_LINE_TOO_LONG) refuse_long_line(s.in->path().c_str(), s.records_before + s.f.r.record);
+  s.avail = s.f.r.n_records;
+  if (s.avail) LIB(fqg_frame_retain(g_ctx, &s.frame));
+  if (!s.f.final) {
     s.carry_pending = true;
-    s.carry_at = r.consumed;
+    s.carry_at = s.f.r.consumed;
   } else s.exhausted = true;
-  return r.n_records > 0 || !s.exhausted;
+  return s.avail > 0 || !s.exhausted;
 }
 
-// ---- several GPUs (FQGPU_DEVICES=0,1,..): every input is cut into blocks of the same B records (fq_blocks.h), block j
-// of all inputs is one unit, whichever device is free takes the next unit, and this thread takes the results in unit
-// order - what the serial loop prints and writes, in its order.  Not for --interleaved input (a discarded read leaves
-// the reference's file pointers out of step from there on, src/fastq_pre_barcodes.c:653 vs :722: a serial dependence).
-struct BlockRun {
-  const char* const* file;
-  const fqg_barcode_params* P;
-  GzipMembers* outgz;
-  int out_sam, num_input_files;
+// What a batch of the serial loop prints goes to a writer thread (in order: one thread, one queue): gzip'ing and writing
+// batch k - the reference's whole cost in FASTQ mode - runs beside reading, framing and transforming batch k + 1.  Two
+// batches may wait; drain() before anything else may be said or the program leaves.
+struct OutJob {
+  int which = 0;
+  OutText t;
 };
-
-[[noreturn]] void run_blocks(const BlockRun& A, const std::vector<int>& devs) {
-  const size_t nd = devs.size();
-  const std::vector<fqg_ctx*> ctx = fqhost::open_more_contexts(g_ctx, devs);  // (ctx[0]: g_ctx, opened on devs[0])
-  RecordBlocks* cut[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  fqg_file_state st0[6];
-  memset(st0, 0, sizeof(st0));
-  std::string format_line[6];
-  double record_bytes = 64;
-  for (int x = READ1; x <= INDEX3; ++x)
-    if (A.file[x]) {
-      cut[x] = new RecordBlocks(g_ctx, A.file[x], (int)nd + 2);
-      if (cut[x]->peek_size()) probe_bytes(cut[x]->peek(), cut[x]->peek_size(), &st0[x], &format_line[x]);
-      else st0[x].is_pe = 1;
-      const double rb = cut[x]->peek_lines() >= 4 ? 4.0 * (double)cut[x]->peek_size() / (double)cut[x]->peek_lines()
-                                                  : (double)std::max<size_t>(cut[x]->peek_size(), 64);
-      record_bytes = std::max(record_bytes, rb);
-    }
-  const size_t piece = getenv("FQGPU_CHUNK_MB") ? piece_bytes() : (size_t)128 << 20;
-  uint64_t B = std::max<uint64_t>(1, (uint64_t)((double)piece / record_bytes));
-  if (const char* e = getenv("FQGPU_BLOCK_RECORDS")) B = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: tiny blocks)
-  for (int x = READ1; x <= INDEX3; ++x)
-    if (cut[x]) cut[x]->start(B);
-
-  struct Unit {
-    uint64_t seq = 0;
-    int rc = 0;
-    std::string err;
-    fqg_barcode_result r{};
-    uint64_t n = 0;                               // iterations the unit had to offer
-    uint64_t records[6] = {0, 0, 0, 0, 0, 0};     // complete records of every input's block
-    int tail_lines[6] = {0, 0, 0, 0, 0, 0};
-    bool final[6] = {false, false, false, false, false, false};
-    bool open_end[6] = {false, false, false, false, false, false};  // see Source::open_end
-    bool ends = false;                            // an input ends inside this unit although its block is not the last
-    int long_line_file = 0;                       // an input of this unit has a line beyond the gzgets limits ...
-    uint64_t long_line_record = 0;                // ... in this record of the file
-    char* out[3] = {nullptr, nullptr, nullptr};   // the text of every output: pinned buffers that go round (OutPool)
-    size_t out_cap[3] = {0, 0, 0};
-    // FQGPU_GZIP_GPU=1 on one context: out[which] holds gzip members (gz_bytes) and behind them the text that did not
-    // fill one (tail_bytes), not out_bytes of text
-    bool members[3] = {false, false, false};
-    size_t gz_bytes[3] = {0, 0, 0}, tail_bytes[3] = {0, 0, 0};
-    std::string wrong_header;                     // the text of the header line of a FQG_E_WRONG_HEADER finding
-    Block b[6];                                   // the context's thread's: given back before the unit is handed over
-  };
-  // The text a unit brings back from the GPU: pinned buffers that go round between the contexts' threads and the thread
-  // that writes.  Into fresh pageable memory the copy ran at 7.5 GB/s per context (page faults, a bounce buffer) and the
-  // copies of the next blocks TO the GPU waited behind it: 28 s for the 200 M pairs of the bench where the serial loop,
-  // whose text has always travelled in pinned buffers, takes 6.7.  As many buffers as the units that may be under way
-  // have outputs (`window` below); take() makes them as they are first asked for.
-  struct OutPool {
-    fqg_ctx* ctx;
-    size_t limit, n_made = 0;
-    std::vector<std::pair<char*, size_t>> free_;
-    std::set<char*> pageable;  // buffers that are not pinned (the pinned allocation failed)
-    std::mutex mu;
-    std::condition_variable cv;
-    bool quit = false;
-    char* take(size_t bytes, size_t* cap) {
-      std::unique_lock<std::mutex> lk(mu);
+struct AsyncOut {
+  GzipMembers* gz;
+  OutPool* pool;  // (where a buffer goes once it is written)
+  std::deque<OutJob> q;
+  std::mutex mu;
+  std::condition_variable cv;
+  bool quit = false, failed = false, busy = false;
+  std::thread th;
+  double t_write = 0;
+  void start() {
+    th = std::thread([this] {
       for (;;) {
-        size_t best = free_.size();  // a free one that is large enough: the smallest such
-        for (size_t i = 0; i < free_.size(); ++i)
-          if (free_[i].second >= bytes && (best == free_.size() || free_[i].second < free_[best].second)) best = i;
-        if (best != free_.size()) {
-          char* p = free_[best].first;
-          *cap = free_[best].second;
-          free_.erase(free_.begin() + (long)best);
-          return p;
+        OutJob j;
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return quit || !q.empty(); });
+          if (q.empty()) return;
+          j = std::move(q.front());
+          q.pop_front();
+          busy = true;
         }
-        if (n_made < limit) {
-          ++n_made;
-          lk.unlock();
-          const size_t want = bytes + bytes / 8 + 4096;
-          char* p = static_cast<char*>(fqg_host_alloc(ctx, want));
-          bool plain = false;
-          if (!p) {  // (no pinned memory to be had: pageable memory does it, slower)
-            p = static_cast<char*>(malloc(want));
-            plain = p != nullptr;
-          }
-          *cap = p ? want : 0;
-          if (!p || plain) {
-            lk.lock();
-            if (!p) --n_made;
-            else pageable.insert(p);
-          }
-          return p;
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = write_out(gz, j.which, j.t);
+        pool->give(j.t.buf, j.t.cap);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+          if (!ok) failed = true;
+          busy = false;
         }
-        if (!free_.empty()) {  // every buffer made, none of the free ones large enough: one of them makes room
-          char* small = free_.back().first;
-          free_.pop_back();
-          --n_made;
-          const bool plain = pageable.erase(small) != 0;
-          lk.unlock();
-          if (plain) free(small);
-          else fqg_host_free(ctx, small);
-          lk.lock();
-          continue;
-        }
-        if (quit) return nullptr;
-        cv.wait(lk);
+        cv.notify_all();
       }
-    }
-    void give(char* p, size_t cap) {
-      if (!p) return;
-      std::lock_guard<std::mutex> lk(mu);
-      free_.emplace_back(p, cap);
-      cv.notify_all();
-    }
-    void stop() {
+    });
+  }
+  void push(const OutJob& j) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return q.size() < 2; });
+    q.push_back(j);
+    lk.unlock();
+    cv.notify_all();
+  }
+  bool drain() {  // everything handed over is written; false: a write failed
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return q.empty() && !busy; });
+    return !failed;
+  }
+  void stop() {
+    {
       std::lock_guard<std::mutex> lk(mu);
       quit = true;
-      cv.notify_all();
     }
-  };
+    cv.notify_all();
+    if (th.joinable()) th.join();
+  }
+};
+
+// ---- the loop over record blocks: every input is cut into blocks of the same B records (fq_blocks.h), block j of all
+// inputs is one unit, whichever context is free takes the next unit (FQGPU_DEVICES=0,1,..: several GPUs), and the main
+// thread takes the results in unit order - what the serial loop prints and writes, in its order.  Not for --interleaved
+// input (a discarded read leaves the reference's file pointers out of step from there on,
+// src/fastq_pre_barcodes.c:653 vs :722: a serial dependence).
+struct Unit {
+  uint64_t seq = 0;
+  int rc = 0;
+  std::string err;
+  fqg_barcode_result r{};
+  uint64_t n = 0;                 // iterations the unit had to offer
+  Framed f[6];                    // every input's block
+  bool ends = false;              // an input ends inside this unit although its block is not the last
+  int long_line_file = 0;         // an input of this unit has a line beyond the gzgets limits ...
+  uint64_t long_line_record = 0;  // ... in this record of the file
+  OutText out[3];                 // the text of every output
+  std::string wrong_header;       // the text of the header line of a FQG_E_WRONG_HEADER finding
+  Block b[6];                     // the context's thread's: given back before the unit is handed over
+};
+
+struct BlockLoop {
+  Batches& A;
+  const std::vector<fqg_ctx*> ctx;  // (ctx[0]: g_ctx)
+  RecordBlocks* cut[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint64_t B = 1;
   // units under way or waiting for the writer: one per context and one more; none is begun beyond that (a context that
   // ran ahead would hold every buffer with units the writer cannot take yet, and the unit it waits for would find none)
-  const uint64_t window = nd + 1;
-  const size_t outs_per_unit = A.out_sam ? 1 : (size_t)((A.P->emit[1] ? 1 : 0) + (A.P->emit[2] ? 1 : 0));
-  OutPool out_pool{g_ctx, (size_t)window * std::max<size_t>(outs_per_unit, 1)};
+  const uint64_t window;
+  OutPool out_pool;  // as many buffers as the units that may be under way have outputs
+  // The carry chain of the device compressor, one per output file: the context's thread's alone.  With ONE context every
+  // unit passes through that thread in unit order (fq_ordered.h), so the tail of unit k is the carry of unit k + 1; the
+  // thread that writes never calls into the context while units are under way.
+  std::string gz_carry[3];
   const bool timing = getenv("FQGPU_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   struct UnitTimes {  // FQGPU_TIMING: one context's seconds
     double frame = 0, transform = 0, out = 0;
   };
-  std::vector<UnitTimes> T(nd);
-  // The carry chain of the device compressor (docs/host_gzip.md section 3), one per output file: the context's thread's
-  // alone.  With ONE context every unit passes through that thread in unit order (fq_ordered.h), so the tail of unit k is
-  // the carry of unit k + 1; the thread that writes never calls into the context while units are under way.
-  std::string gz_carry[3];
-  using UnitRun = OrderedRun<Unit>;
-  // (fq_ordered.h: the units to whichever context is free, the results to this thread in unit order)
-  UnitRun run(
-      nd, window,
-      [&](uint64_t seq, Unit& u, bool& last) {
-        for (int x = READ1; x <= INDEX3; ++x)  // (false only after an abort: a unit that holds the end of an input is the last one handed out)
-          if (cut[x] && !cut[x]->next(&u.b[x])) return false;
-        u.seq = seq;
-        for (int x = READ1; x <= INDEX3; ++x)
-          if (cut[x] && u.b[x].final) last = true;
-        return true;
-      },
-      [&](size_t di, Unit& u) {
-        fqg_ctx* c = ctx[di];
-        Block* const b = u.b;
-        const double t1 = timing ? now() : 0;
-        const fqg_frame* frames[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        fqg_frame* held[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        fqg_file_state states[6];
-        memcpy(states, st0, sizeof(states));
-        uint64_t first[6] = {0, 0, 0, 0, 0, 0};
-        auto lib_fail = [&](const char* what, int rc) {
-          u.rc = rc;
-          u.err = std::string(what) + ": " + fqg_last_error(c);
-        };
-        u.n = ~0ull;
-        for (int x = READ1; x <= INDEX3 && !u.rc; ++x)
-          if (cut[x]) {
-            fqg_validate_result r;
-            const int rc = fqg_validate(c, nullptr, b[x].data, b[x].size, FQG_MEM_HOST, b[x].final ? 1 : 0, &states[x],
-                                        FQG_VALIDATE_FRAME_ONLY, &r);
-            if (rc) {
-              lib_fail("fqg_validate", rc);
-              break;
-            }
-            if (r.code == FQG_E_LINE_TOO_LONG) {  // (the thread that takes the results starts the program over: refuse_long_line)
-              u.long_line_file = x;
-              u.long_line_record = u.seq * B + r.record;
-              u.rc = FQG_ERR_ARG;
-              break;
-            }
-            // a header line that starts with a NUL byte is "no entry" for the reference (src/fastq.c:250): this input ends
-            // HERE, cleanly, whatever follows - the unit is the last one the consumer looks at
-            const bool ends_here = r.stopped != 0;
-            // ... and another line of a record that starts with NUL is an empty string: the file is truncated there
-            // (src/fastq.c:254; tail_lines > 0) - the last unit as well
-            const bool cut_short = !ends_here && r.code == FQG_E_TRUNCATED && !b[x].final;
-            if (cut_short) u.ends = true;
-            if (ends_here) {
-              // frame the records in front of it once more, alone: what follows the NUL is not this file's any more
-              u.ends = true;
-              const int rc2 = fqg_validate(c, nullptr, b[x].data, r.consumed, FQG_MEM_HOST, 1, &states[x], FQG_VALIDATE_FRAME_ONLY, &r);
-              if (rc2) {
-                lib_fail("fqg_validate", rc2);
-                break;
-              }
-            }
-            if (!b[x].final && !ends_here && !cut_short && (r.n_records != B || r.consumed != b[x].size)) {
-              u.rc = FQG_ERR_STATE;
-              u.err = std::string("a block of ") + A.file[x] + " cut at a record boundary was not consumed whole";
-              break;
-            }
-            u.records[x] = r.n_records;
-            u.tail_lines[x] = ends_here ? 0 : r.tail_lines;
-            u.final[x] = b[x].final || ends_here || cut_short;
-            u.open_end[x] = b[x].final && !ends_here && r.tail_lines == 0 && r.n_records > 0 && b[x].size > 0 && b[x].data[b[x].size - 1] != '\n';
-            u.n = std::min<uint64_t>(u.n, r.n_records);
-            if (r.n_records) {
-              const int rc2 = fqg_frame_retain(c, &held[x]);
-              if (rc2) {
-                lib_fail("fqg_frame_retain", rc2);
-                break;
-              }
-              frames[x] = held[x];
-            }
-          }
-        const double t2 = timing ? now() : 0;
-        T[di].frame += t2 - t1;
-        double t3 = t2;
-        if (!u.rc && u.n > 0) {
-          fqg_barcode_params Pb = *A.P;
-          const int rc = fqg_barcodes_transform(c, frames, states, first, &Pb, u.n, u.seq * B, &u.r);
-          if (rc) lib_fail("fqg_barcodes_transform", rc);
-          t3 = timing ? now() : 0;
-          T[di].transform += t3 - t2;
-          for (int which = 0; which < 3 && !u.rc; ++which)
-            if (u.r.out_bytes[which]) {
-              size_t bytes = u.r.out_bytes[which];
-              u.members[which] = which > 0 && A.outgz[which].on_device();  // (handed over for one context only: main)
-              if (u.members[which]) {
-                fqg_deflate_result dr;
-                const int rc2 = fqg_text_deflate(c, FQG_TEXT_RECORDS, which, gz_carry[which].data(), gz_carry[which].size(), 0, &dr);
-                if (rc2) {
-                  lib_fail("fqg_text_deflate", rc2);
-                  break;
-                }
-                u.gz_bytes[which] = dr.gz_bytes;
-                u.tail_bytes[which] = dr.tail_bytes;
-                bytes = dr.gz_bytes + dr.tail_bytes;
-              }
-              u.out[which] = out_pool.take(bytes, &u.out_cap[which]);
-              if (!u.out[which]) {
-                u.rc = FQG_ERR_NOMEM;
-                u.err = "no pinned memory for the output text";
-                break;
-              }
-              if (u.members[which]) {
-                const int rc2 = fqg_deflate_output(c, u.out[which], bytes);
-                if (rc2) lib_fail("fqg_deflate_output", rc2);
-                else gz_carry[which].assign(u.out[which] + u.gz_bytes[which], u.tail_bytes[which]);
-              } else {
-                const int rc2 = fqg_barcodes_output(c, which, u.out[which], u.r.out_bytes[which]);
-                if (rc2) lib_fail("fqg_barcodes_output", rc2);
-              }
-            }
-          if (!u.rc && u.r.code == FQG_E_WRONG_HEADER) {
-            const Block& bb = b[u.r.file];
-            const char *p = bb.data, *end = bb.data + bb.size;
-            for (uint64_t line = 0; p < end && line < 4 * u.r.n_done; ++line) {
-              const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
-              p = nl ? nl + 1 : end;
-            }
-            const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-            u.wrong_header.assign(p, nl ? nl + 1 : end);
-          }
-        } else if (!u.rc) u.n = 0;
-        const double t4 = timing ? now() : 0;
-        T[di].out += t4 - t3;
-        for (int x = READ1; x <= INDEX3; ++x)
-          if (cut[x]) {
-            if (held[x]) fqg_frame_release(held[x]);
-            cut[x]->release(b[x]);
-          }
-      },
-      [&] {  // (a context may be waiting for an output buffer or for blocks, a cutter for a slot that stays held)
-        out_pool.stop();
-        for (int x = READ1; x <= INDEX3; ++x)
-          if (cut[x]) cut[x]->abort();
-      },
-      [&](size_t di, const UnitRun::Waits& w) {
-        if (timing) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu units; waiting for blocks %.3f s, copy + framing %.3f s, transform %.3f s, output D2H %.3f s, handing over %.3f s\n",
-                            di, (unsigned long long)w.items, w.fetch, T[di].frame, T[di].transform, T[di].out, w.hand_over);
-      });
+  std::vector<UnitTimes> T;
+  static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-  unsigned long processed = 0, discarded = 0;
-  bool first_batch = true;
-  Unit last;
-  bool have_last = false;
-  double t_main_wait = 0;
-  const double t_loop = now();
-  for (;;) {
-    Unit u;
-    const double tw = timing ? now() : 0;
-    const bool more = run.next(u);
-    if (timing) t_main_wait += now() - tw;
-    if (!more) break;
-    if (u.rc) {
-      run.stop();
-      if (u.long_line_file) refuse_long_line(A.file[u.long_line_file], u.long_line_record);
-      FQ_PRINT_ERROR("GPU library failure in %s (%d)", u.err.c_str(), u.rc);
-      fqhost::leave(kExitSys);
-    }
-    if (u.n > 0) {
-      const fqg_barcode_result& r = u.r;
-      if (first_batch && A.num_input_files > 1) {
-        // format lines of the first fastq_get_readname call per file, in file order (src/fastq.c:459-485)
-        for (int x = READ1; x <= INDEX3; ++x)
-          if (A.file[x]) {
-            if (r.code == FQG_E_WRONG_HEADER && r.iteration == 0 && r.file == x) break;
-            fputs(format_line[x].c_str(), stderr);
-            if (st0[x].space == FQG_SPACE_COLOUR) fputs("Color space\n", stderr);
-          }
-      }
-      first_batch = false;
-      for (uint64_t w = 0; w < r.n_short; ++w) fputs("Warning: Read too short - barcode not found\n", stderr);
-      if (r.out_bytes[0]) fwrite(u.out[0], 1, r.out_bytes[0], stdout);
-      // (device mode: the members, and the unit's tail for close() - the tail of the LAST unit taken here, whatever the
-      // context's thread went on to compress behind a unit that ends the run)
-      for (int which = 1; which < 3; ++which)
-        if (r.out_bytes[which] &&
-            !(u.members[which] ? A.outgz[which].write_members(u.out[which], u.gz_bytes[which], u.out[which] + u.gz_bytes[which], u.tail_bytes[which])
-                               : A.outgz[which].write(u.out[which], r.out_bytes[which]))) {
-          run.stop();
-          FQ_PRINT_ERROR("%s.\n", A.outgz[which].error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
-          fqhost::leave(kExitSys);
-        }
-      const unsigned long before = processed;
-      processed += r.n_done;
-      discarded += r.n_discarded;
-      for (unsigned long c = (before / 100000 + 1) * 100000; c <= processed; c += 100000) {
-        fprintf(stderr, "\b\b\b\b\b\b\b\b\b\b\b\b\b\b\b%lu", c);
-        fflush(stderr);
-      }
-      if (r.code != FQG_OK) {
-        run.stop();
-        if (r.code == FQG_E_WRONG_HEADER) {  // src/fastq.c:448-451, with the file's own line counter
-          const uint64_t reads_of_file = u.seq * B + r.n_done + 1;
-          FQ_PRINT_ERROR("Error in file %s: line %lu: wrong header %s", A.file[r.file], (unsigned long)(4 * reads_of_file),
-                         u.wrong_header.c_str());
-          fqhost::leave(kExitFormat);
-        }
-        FQ_PRINT_ERROR("Readnames do not match across files (read #%ld)", (long)(processed + 1));
-        fqhost::leave(kExitFormat);
-      }
-    }
-    for (int which = 0; which < 3; ++which) {
-      out_pool.give(u.out[which], u.out_cap[which]);
-      u.out[which] = nullptr;
-    }
-    run.done();
-    const bool ends = u.ends;
-    last = std::move(u);
-    have_last = true;
-    if (ends) break;  // (later units, if any were handed out, are dropped)
-  }
-  run.stop();
-  if (timing) fprintf(fqhost::diag(), "fqgpu timing: the thread that writes: %.3f s in the loop, %.3f s of them waiting for the next unit\n", now() - t_loop, t_main_wait);
-  // an incomplete record where the next read would have happened is a truncated file (src/fastq.c:254-257); a clean
-  // end of any input just ends the loop.  The first input, in file order, that has nothing left decides - unless the
-  // loop's own condition ends it first (fastq_files_eof, src/fastq_pre_barcodes.c:288-297, :594): an input whose last
-  // line has no '\n' is at its end for gzeof once that line has been read, and no input is read again.
-  bool loop_condition_ends_it = false;
-  if (have_last)
-    for (int x = READ1; x <= INDEX3; ++x)
-      if (A.file[x] && last.final[x] && last.open_end[x] && last.records[x] == last.n) loop_condition_ends_it = true;
-  if (have_last && !loop_condition_ends_it)
+  BlockLoop(Batches& a, const std::vector<int>& devs)
+      : A(a), ctx(fqhost::open_more_contexts(g_ctx, devs)), window(devs.size() + 1),
+        out_pool(FQ_PINNED_ALLOC(g_ctx), (size_t)window * outputs_per_batch(*a.P)), T(devs.size()) {
+    double record_bytes = 64;
     for (int x = READ1; x <= INDEX3; ++x)
       if (A.file[x]) {
-        if (!(last.final[x] && last.records[x] == last.n)) continue;
-        if (last.tail_lines[x] > 0) {
-          FQ_PRINT_ERROR("Error in file %s: line %lu: file truncated", A.file[x],
-                         (unsigned long)(4 * (last.seq * B + last.records[x])));
-          fqhost::leave(1);
-        }
-        break;
+        cut[x] = new RecordBlocks(g_ctx, A.file[x], (int)devs.size() + 2);
+        probe_piece(A.pr[x], cut[x]->peek(), cut[x]->peek_size(), 1);
+        const double rb = cut[x]->peek_lines() >= 4 ? 4.0 * (double)cut[x]->peek_size() / (double)cut[x]->peek_lines()
+                                                    : (double)std::max<size_t>(cut[x]->peek_size(), 64);
+        record_bytes = std::max(record_bytes, rb);
       }
-  FQ_PRINT_INFO("Reads processed: %ld", (long)processed);
-  FQ_PRINT_INFO("Reads discarded: %ld", (long)discarded);
-  if (!A.out_sam)
-    for (int x = READ1; x <= READ2; ++x)
-      if (A.P->emit[x] && !A.outgz[x].close()) {
-        FQ_PRINT_ERROR("unable to close file descriptor");
+    B = std::max<uint64_t>(1, (uint64_t)((double)piece_bytes(128) / record_bytes));
+    if (const char* e = getenv("FQGPU_BLOCK_RECORDS")) B = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: tiny blocks)
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (cut[x]) cut[x]->start(B);
+  }
+
+  // block `seq` of every input (false only after an abort: a unit that holds the end of an input is the last one handed out)
+  bool next_unit(uint64_t seq, Unit& u, bool& last) {
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (cut[x] && !cut[x]->next(&u.b[x])) return false;
+    u.seq = seq;
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (cut[x] && u.b[x].final) last = true;
+    return true;
+  }
+  static void lib_fail(fqg_ctx* c, Unit& u, const char* what, int rc) {
+    u.rc = rc;
+    u.err = std::string(what) + ": " + fqg_last_error(c);
+  }
+  // frame the unit's blocks; held[x]: the retained frame of input x
+  void frame_unit(fqg_ctx* c, Unit& u, const fqg_file_state* states, fqg_frame** held) {
+    u.n = ~0ull;
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (cut[x]) {
+        const Block& b = u.b[x];
+        Framed& f = u.f[x];
+        const char* what;
+        if (const int rc = frame_piece(c, b.data, b.size, b.final, &states[x], 0, &f, &what)) return lib_fail(c, u, what, rc);
+        if (f.r.code == FQG_E_LINE_TOO_LONG) {  // (the thread that takes the results starts the program over: refuse_long_line)
+          u.long_line_file = x;
+          u.long_line_record = u.seq * B + f.r.record;
+          u.rc = FQG_ERR_ARG;
+          return;
+        }
+        if (f.ends_here || f.cut_short) u.ends = true;  // the last unit the consumer looks at
+        if (!f.final && (f.r.n_records != B || f.r.consumed != b.size)) {
+          u.rc = FQG_ERR_STATE;
+          u.err = std::string("a block of ") + A.file[x] + " cut at a record boundary was not consumed whole";
+          return;
+        }
+        u.n = std::min<uint64_t>(u.n, f.r.n_records);
+        if (f.r.n_records)
+          if (const int rc = fqg_frame_retain(c, &held[x])) return lib_fail(c, u, "fqg_frame_retain", rc);
+      }
+  }
+  // transform the unit and fetch its text (and the header text of a wrong-header finding: the blocks are given back)
+  void transform_unit(size_t di, fqg_ctx* c, Unit& u, const fqg_file_state* states, fqg_frame* const* held) {
+    const double t2 = timing ? now() : 0;
+    const uint64_t first[6] = {0, 0, 0, 0, 0, 0};
+    fqg_barcode_params Pb = *A.P;
+    if (const int rc = fqg_barcodes_transform(c, held, states, first, &Pb, u.n, u.seq * B, &u.r)) lib_fail(c, u, "fqg_barcodes_transform", rc);
+    const double t3 = timing ? now() : 0;
+    T[di].transform += t3 - t2;
+    for (int which = 0; which < 3 && !u.rc; ++which)
+      if (u.r.out_bytes[which]) {
+        const char* what;
+        // (a device was handed over to the output files for one context only: main)
+        if (const int rc = fetch_begin(c, out_pool, which, u.r.out_bytes[which], which > 0 && A.outgz[which].on_device(), gz_carry[which],
+                                       false, &u.out[which], &what))
+          lib_fail(c, u, what, rc);
+        else if (const int rc2 = fetch_wait(c, u.out[which], &gz_carry[which])) lib_fail(c, u, "fqg_*_output_wait", rc2);
+      }
+    if (!u.rc && u.r.code == FQG_E_WRONG_HEADER) u.wrong_header = locate_record(u.b[u.r.file].data, u.b[u.r.file].size, u.r.n_done).l[0];
+    T[di].out += (timing ? now() : 0) - t3;
+  }
+  void work(size_t di, Unit& u) {
+    fqg_ctx* c = ctx[di];
+    const double t1 = timing ? now() : 0;
+    fqg_frame* held[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    fqg_file_state states[6];
+    for (int x = 0; x < 6; ++x) states[x] = A.pr[x].st;
+    frame_unit(c, u, states, held);
+    T[di].frame += (timing ? now() : 0) - t1;
+    if (!u.rc && u.n > 0) transform_unit(di, c, u, states, held);
+    else if (!u.rc) u.n = 0;
+    for (int x = READ1; x <= INDEX3; ++x)
+      if (cut[x]) {
+        if (held[x]) fqg_frame_release(held[x]);
+        cut[x]->release(u.b[x]);
+      }
+  }
+
+  [[noreturn]] void run(size_t devices) {
+    using UnitRun = OrderedRun<Unit>;
+    // (fq_ordered.h: the units to whichever context is free, the results to this thread in unit order)
+    UnitRun run(
+        ctx.size(), window, [&](uint64_t seq, Unit& u, bool& last) { return next_unit(seq, u, last); },
+        [&](size_t di, Unit& u) { work(di, u); },
+        [&] {  // (a context may be waiting for an output buffer or for blocks, a cutter for a slot that stays held)
+          out_pool.stop();
+          for (int x = READ1; x <= INDEX3; ++x)
+            if (cut[x]) cut[x]->abort();
+        },
+        [&](size_t di, const UnitRun::Waits& w) {
+          if (timing) fprintf(fqhost::diag(), "fqgpu timing: context %zu: %llu units; waiting for blocks %.3f s, copy + framing %.3f s, transform %.3f s, output D2H %.3f s, handing over %.3f s\n",
+                              di, (unsigned long long)w.items, w.fetch, T[di].frame, T[di].transform, T[di].out, w.hand_over);
+        });
+    InputEnd end[6];
+    double t_main_wait = 0;
+    const double t_loop = now();
+    for (;;) {
+      Unit u;
+      const double tw = timing ? now() : 0;
+      const bool more = run.next(u);
+      if (timing) t_main_wait += now() - tw;
+      if (!more) break;
+      if (u.rc) {
+        run.stop();
+        if (u.long_line_file) refuse_long_line(A.file[u.long_line_file], u.long_line_record);
+        FQ_PRINT_ERROR("GPU library failure in %s (%d)", u.err.c_str(), u.rc);
         fqhost::leave(kExitSys);
       }
-  fflush(stdout);
-  pb_json_metrics((long)processed, (long)discarded, std::set<int>(devs.begin(), devs.end()).size());
-  fqhost::leave(0);
-}
+      if (u.n > 0) {
+        A.announce(u.r);
+        for (int which = 0; which < 3; ++which)
+          if (u.r.out_bytes[which] && !write_out(A.outgz, which, u.out[which]) && which > 0) {
+            run.stop();
+            FQ_PRINT_ERROR("%s.\n", A.outgz[which].error().c_str());  // GZ_WRITE's gzerror() text, src/fastq.c:211-235
+            fqhost::leave(kExitSys);
+          }
+        A.count(u.r, [&] { run.stop(); }, [&] { return WrongHeader{(unsigned long)(4 * (u.seq * B + u.r.n_done + 1)), u.wrong_header}; });
+      }
+      for (OutText& o : u.out) out_pool.give(o.buf, o.cap);
+      run.done();
+      for (int x = READ1; x <= INDEX3; ++x) {  // (of the last unit taken: later ones, if any were handed out, are dropped)
+        const Framed& f = u.f[x];
+        end[x].drained = f.final && f.r.n_records == u.n;
+        end[x].at_end = true;
+        end[x].open_end = f.open_end;
+        end[x].tail_lines = f.tail_lines;
+        end[x].records = u.seq * B + f.r.n_records;
+      }
+      if (u.ends) break;
+    }
+    run.stop();
+    if (timing) fprintf(fqhost::diag(), "fqgpu timing: the thread that writes: %.3f s in the loop, %.3f s of them waiting for the next unit\n", now() - t_loop, t_main_wait);
+    A.finish(end, devices);
+  }
+};
 
 }  // namespace
 
@@ -752,19 +715,20 @@ int main(int argc, char** argv) {
   }
   P.out_sam = out_sam;
   P.tenx = tenx;
+  GzipMembers outgz[3];  // gzip level 4 like the reference's "w4", one member per 4 MiB block, all cores
+  Batches A;
+  A.file = file, A.P = &P, A.outgz = outgz, A.num_input_files = num_input_files, A.scale = has_interleaved ? 2 : 1;
   Source src[6];
   for (int x = READ1; x <= INDEX3; ++x)
     if (file[x]) {
       P.present[x] = 1;
-      src[x].path = file[x];
-      if (!multi) src[x].in = new Input(g_ctx, file[x], piece_bytes());
+      src[x].pr = &A.pr[x];
+      if (!multi) src[x].in = new Input(g_ctx, file[x], piece_bytes(512));
     }
   if (has_interleaved && (!file[P.interleaved[0]] || !file[P.interleaved[1]])) {
     FQ_PRINT_ERROR("--interleaved refers to an input that was not given");
     fqhost::leave(kExitParams);
   }
-  GzipMembers outgz[3];  // gzip level 4 like the reference's "w4", one member per 4 MiB block, all cores
-  bool out_open[3] = {false, false, false};
   if (!out_sam) {
     for (int x = READ1; x <= READ2; ++x)
       if (outfile[x]) {
@@ -778,7 +742,6 @@ int main(int argc, char** argv) {
           FQ_PRINT_ERROR("Unable to open %s", outfile[x]);
           fqhost::leave(kExitParams);
         }
-        out_open[x] = true;
         // FQGPU_GZIP_GPU=1: the device compressor, in the loops that run on ONE context.  Over several contexts unit k
         // could cut its members only once the text lengths of units 0 .. k - 1 are known (docs/host_gzip.md section 3):
         // no device is handed over there and the host compressor runs
@@ -791,107 +754,15 @@ int main(int argc, char** argv) {
     printf("\n");
   }
 
-  if (multi) {
-    BlockRun A{file, &P, outgz, out_sam, num_input_files};
-    run_blocks(A, devices);
-  }
-  unsigned long processed = 0, discarded = 0;
-  bool first_batch = true;
-  // What a batch prints goes to a writer thread (in order: one thread, one queue): gzip'ing and writing batch k - the
-  // reference's whole cost in FASTQ mode - runs beside reading, framing and transforming batch k + 1.  Two batches may
-  // wait; drain() before anything else may be said or the program leaves.
-  // (the text travels in pinned buffers that go round: the copy from the GPU into fresh pageable memory - page faults, a
-  // bounce buffer - took four times as long as everything else the program does)
-  struct OutJob {
-    int which = 0;
-    char* text = nullptr;
-    size_t size = 0, cap = 0;
-    bool members = false;  // FQGPU_GZIP_GPU=1: `gz` bytes of gzip members, then size - gz bytes of text that filled none
-    size_t gz = 0;
-  };
-  struct AsyncOut {
-    GzipMembers* gz;
-    std::deque<OutJob> q;
-    std::vector<OutJob> spare;  // buffers that have been written out
-    std::mutex mu;
-    std::condition_variable cv;
-    bool quit = false, failed = false, busy = false;
-    std::thread th;
-    double t_write = 0;
-    void start() {
-      th = std::thread([this] {
-        for (;;) {
-          OutJob j;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return quit || !q.empty(); });
-            if (q.empty()) return;
-            j = std::move(q.front());
-            q.pop_front();
-            busy = true;
-          }
-          const auto t0 = std::chrono::steady_clock::now();
-          bool ok = true;
-          if (j.which == 0) ok = fwrite(j.text, 1, j.size, stdout) == j.size;
-          else if (j.members) ok = gz[j.which].write_members(j.text, j.gz, j.text + j.gz, j.size - j.gz);
-          else ok = gz[j.which].write(j.text, j.size);
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (!ok) failed = true;
-            busy = false;
-            spare.push_back(j);
-          }
-          cv.notify_all();
-        }
-      });
-    }
-    // a pinned buffer of at least `bytes` for the next batch's text (a spare one when it is large enough)
-    OutJob buffer(fqg_ctx* ctx, size_t bytes) {
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        for (size_t i = 0; i < spare.size(); ++i)
-          if (spare[i].cap >= bytes) {
-            OutJob j = spare[i];
-            spare.erase(spare.begin() + (long)i);
-            return j;
-          }
-        if (!spare.empty()) {  // too small: replace it
-          fqhost::slot_release(ctx, spare.back().text);
-          spare.pop_back();
-        }
-      }
-      OutJob j;
-      j.cap = bytes + bytes / 8 + (1u << 20);
-      j.text = fqhost::slot_alloc(ctx, j.cap);
-      if (!j.text) {
-        FQ_PRINT_ERROR("unable to allocate %zu bytes of pinned memory", j.cap);
-        fqhost::leave(kExitSys);
-      }
-      return j;
-    }
-    void push(const OutJob& j) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return q.size() < 2; });
-      q.push_back(j);
-      lk.unlock();
-      cv.notify_all();
-    }
-    bool drain() {  // everything handed over is written; false: a write failed
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return q.empty() && !busy; });
-      return !failed;
-    }
-    void stop() {
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        quit = true;
-      }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-  } outq;
+  if (multi) BlockLoop(A, devices).run(std::set<int>(devices.begin(), devices.end()).size());
+
+  // ---- the serial loop: --interleaved input, a run started over on re-framed input, FQGPU_SERIAL_LOOP=1 ----
+  // (the text travels in pinned buffers that go round: per output one on its way from the GPU, two that wait for the
+  // writer and the one it writes)
+  OutPool out_pool(FQ_PINNED_ALLOC(g_ctx), 4 * outputs_per_batch(P));
+  AsyncOut outq;
   outq.gz = outgz;
+  outq.pool = &out_pool;
   outq.start();
   auto drain_or_die = [&] {
     if (!outq.drain()) {
@@ -912,23 +783,21 @@ int main(int argc, char** argv) {
   std::vector<OutJob> in_flight;  // output of the last transform, on its way to the host
   std::string gz_carry[3];        // device mode: the text the last batch left over, per output file (the carry chain)
   auto land_output = [&] {
-    if (in_flight.empty()) return;
-    const double t_d = now();
-    LIB(fqg_barcodes_output_wait(g_ctx));
-    LIB(fqg_deflate_output_wait(g_ctx));
-    const double t_e = now();
     for (const OutJob& job : in_flight) {
-      if (job.members) gz_carry[job.which].assign(job.text + job.gz, job.size - job.gz);  // (the tail came with the copy)
+      const double t_d = now();
+      if (const int rc = fetch_wait(g_ctx, job.t, &gz_carry[job.which])) die_lib("fqg_*_output_wait", rc);
+      const double t_e = now();
       outq.push(job);
+      t_fetch += t_e - t_d;
+      t_hand += now() - t_e;
     }
     in_flight.clear();
-    t_fetch += t_e - t_d;
-    t_hand += now() - t_e;
   };
-  g_before_respawn = [&] {
+  auto flush = [&] {
     land_output();
     drain_or_die();
   };
+  g_before_respawn = flush;
   for (;;) {
     // every input needs a frame that holds the record its next iteration uses
     const double t_a = now();
@@ -966,84 +835,40 @@ int main(int argc, char** argv) {
     for (int x = READ1; x <= INDEX3; ++x)
       if (file[x]) {
         frames[x] = src[x].frame;
-        states[x] = src[x].st;
+        states[x] = A.pr[x].st;
         // the library adds +1 for the second interleaved reference itself
         first[x] = (uint64_t)src[x].use - ((has_interleaved && x == P.interleaved[1]) ? 1 : 0);
       }
     fqg_barcode_result r;
     land_output();  // (the transform writes the device buffers the previous batch's text is copied from)
     const double t_b = now();
-    LIB(fqg_barcodes_transform(g_ctx, frames, states, first, &Pb, n, processed, &r));
+    LIB(fqg_barcodes_transform(g_ctx, frames, states, first, &Pb, n, A.processed, &r));
     const double t_c = now();
     t_refill += t_b - t_a;
     t_transform += t_c - t_b;
-    if (first_batch && num_input_files > 1) {
-      drain_or_die();  // (nothing is in flight yet: the first batch)
-      // format lines of the first fastq_get_readname call per file, in file order (src/fastq.c:459-485)
-      for (int x = READ1; x <= INDEX3; ++x)
-        if (file[x]) {
-          if (r.code == FQG_E_WRONG_HEADER && r.iteration == 0 && r.file == x) break;
-          fputs(src[x].format_line.c_str(), stderr);
-          if (src[x].st.space == FQG_SPACE_COLOUR) fputs("Color space\n", stderr);
-        }
-    }
-    first_batch = false;
-    for (uint64_t w = 0; w < r.n_short; ++w) fputs("Warning: Read too short - barcode not found\n", stderr);
+    A.announce(r);
     // The text comes back on a stream of its own, beside the upload and framing of the NEXT pieces of input (the link
     // carries both directions at once: tools/kbench/duplex.hip); it is handed to the writer (stdout / gzip) when the
-    // next batch is about to be transformed - land_output(), at the top of the loop - or the loop ends.
+    // next batch is about to be transformed - land_output(), at the top of the loop - or the loop ends.  (Device mode:
+    // the carry is the tail that landed with the previous batch: land_output() has run before this batch's transform.)
     for (int which = 0; which < 3; ++which)
       if (r.out_bytes[which]) {
         const double t_d = now();
-        // device mode: the members and the tail come back instead of the text; the writer gets members to write.  (The
-        // carry is the tail that landed with the previous batch: land_output() has run before this batch's transform.)
-        const bool members = which > 0 && outgz[which].on_device();
-        fqg_deflate_result dr;
-        memset(&dr, 0, sizeof(dr));
-        if (members) LIB(fqg_text_deflate(g_ctx, FQG_TEXT_RECORDS, which, gz_carry[which].data(), gz_carry[which].size(), 0, &dr));
-        OutJob job = outq.buffer(g_ctx, members ? dr.gz_bytes + dr.tail_bytes : r.out_bytes[which]);
+        OutJob job;
         job.which = which;
-        job.size = members ? dr.gz_bytes + dr.tail_bytes : r.out_bytes[which];
-        job.members = members;
-        job.gz = dr.gz_bytes;
-        if (members) LIB(fqg_deflate_output_begin(g_ctx, job.text, job.size));
-        else LIB(fqg_barcodes_output_begin(g_ctx, which, job.text, job.size));
+        const char* what;
+        if (const int rc = fetch_begin(g_ctx, out_pool, which, r.out_bytes[which], which > 0 && outgz[which].on_device(), gz_carry[which], true,
+                                       &job.t, &what))
+          die_lib(what, rc);
         in_flight.push_back(job);
         t_fetch += now() - t_d;
       }
-    const unsigned long before = processed;
-    processed += r.n_done;
-    discarded += r.n_discarded;
-    for (unsigned long c = (before / 100000 + 1) * 100000; c <= processed; c += 100000) {
-      fprintf(stderr, "\b\b\b\b\b\b\b\b\b\b\b\b\b\b\b%lu", c * (has_interleaved ? 2 : 1));
-      fflush(stderr);
-    }
-    if (r.code != FQG_OK) {
-      land_output();
-      drain_or_die();
-      if (r.code == FQG_E_WRONG_HEADER) {
-        // src/fastq.c:448-451, with the file's own line counter
-        Source& s = src[r.file];
-        const uint64_t rec = s.records_before + (uint64_t)s.use + r.n_done * step_of(r.file);
-        const char* b = s.in->data();
-        // the header text: first line of that record in the current piece
-        const char* p = b;
-        const char* end = b + s.in->size();
-        const uint64_t local = (uint64_t)s.use + r.n_done * step_of(r.file);
-        for (uint64_t line = 0; p < end && line < 4 * local; ++line) {
-          const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
-          p = nl ? nl + 1 : end;
-        }
-        const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-        const std::string hdr(p, nl ? nl + 1 : end);
-        const uint64_t reads_of_file = rec + 1;  // records this file has handed out so far
-        FQ_PRINT_ERROR("Error in file %s: line %lu: wrong header %s", s.path, (unsigned long)(4 * reads_of_file),
-                       hdr.c_str());
-        fqhost::leave(kExitFormat);
-      }
-      FQ_PRINT_ERROR("Readnames do not match across files (read #%ld)", (long)(processed + 1));
-      fqhost::leave(kExitFormat);
-    }
+    // (the header text of a wrong header: first line of that record in the file's current piece)
+    A.count(r, flush, [&] {
+      const Source& s = src[r.file];
+      const uint64_t local = (uint64_t)s.use + r.n_done * step_of(r.file);
+      return WrongHeader{(unsigned long)(4 * (s.records_before + local + 1)), locate_record(s.in->data(), s.in->size(), local).l[0]};
+    });
     const bool ended_on_discard = has_interleaved && r.n_done < n;
     for (int x = READ1; x <= INDEX3; ++x)
       if (file[x]) {
@@ -1051,44 +876,21 @@ int main(int argc, char** argv) {
         if (ended_on_discard && x == P.interleaved[0]) src[x].use -= 1;  // no re-synchronising read after a discard
       }
   }
-  land_output();
-  drain_or_die();
+  flush();
   outq.stop();
   if (timing)
     fprintf(fqhost::diag(), "\nfqgpu timing: reading + framing %.3f s, transform %.3f s, output D2H %.3f s, waiting for the writer %.3f s; "
                     "the writer (gzip / stdout) worked %.3f s beside them\n", t_refill, t_transform, t_fetch, t_hand, outq.t_write);
-  // an incomplete record where the next read would have happened is a truncated file
-  // (src/fastq.c:254-257); a clean end of any input just ends the loop - and so does the loop's own condition
-  // (fastq_files_eof, src/fastq_pre_barcodes.c:288-297, :594), before any input is read again: an input whose last line
-  // has no '\n' is at its end for gzeof once that line has been read
-  bool loop_condition_ends_it = false;
+  InputEnd end[6];
   for (int x = READ1; x <= INDEX3; ++x)
     if (file[x]) {
       const Source& s = src[x];
-      if (s.exhausted && s.open_end && (!s.frame || s.use == (long)s.avail)) loop_condition_ends_it = true;
+      end[x].drained = s.exhausted && (!s.frame || s.use >= (long)s.avail);
+      end[x].at_end = !s.frame || s.use == (long)s.avail;
+      end[x].one_beyond = has_interleaved && x == P.interleaved[1] && s.use == (long)s.avail + 1;
+      end[x].open_end = s.f.open_end;
+      end[x].tail_lines = s.f.tail_lines;
+      end[x].records = s.records_before + s.avail;
     }
-  for (int x = READ1; x <= INDEX3 && !loop_condition_ends_it; ++x)
-    if (file[x]) {
-      Source& s = src[x];
-      const bool drained = s.exhausted && (!s.frame || s.use >= (long)s.avail);
-      if (!drained) continue;
-      if (s.tail_lines > 0 && (!s.frame || s.use == (long)s.avail ||
-                               (has_interleaved && x == P.interleaved[1] && s.use == (long)s.avail + 1))) {
-        FQ_PRINT_ERROR("Error in file %s: line %lu: file truncated", s.path,
-                       (unsigned long)(4 * (s.records_before + s.avail)));
-        fqhost::leave(1);
-      }
-      break;
-    }
-  FQ_PRINT_INFO("Reads processed: %ld", (long)processed);
-  FQ_PRINT_INFO("Reads discarded: %ld", (long)discarded);
-  if (!out_sam)
-    for (int x = READ1; x <= READ2; ++x)
-      if (out_open[x] && !outgz[x].close()) {
-        FQ_PRINT_ERROR("unable to close file descriptor");
-        fqhost::leave(kExitSys);
-      }
-  fflush(stdout);
-  pb_json_metrics((long)processed, (long)discarded, 1);
-  fqhost::leave(0);
+  A.finish(end, 1);
 }

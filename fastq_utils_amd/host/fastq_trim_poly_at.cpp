@@ -10,13 +10,6 @@
 
 using namespace fqhost;
 
-#define FQ_PRINT_INFO(...)        \
-  do {                            \
-    fprintf(stderr, "INFO:");     \
-    fprintf(stderr, __VA_ARGS__); \
-    fprintf(stderr, "\n");        \
-  } while (0)
-
 static void print_usage() {  // src/fastq_trim_poly_at.c:121-133
   const char msg[] =
       "\n"

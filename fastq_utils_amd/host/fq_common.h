@@ -1,6 +1,7 @@
 // fq_common.h - what the drop-in programs that read FASTQ through the name index share: the library handle, the
 // wording of the reference's messages (src/fastq.c), the once-per-file probes and the indexing loop
-// (fastq_index_readnames, src/fastq.c:396-439) as bulk calls.  Included by fastq_info.cpp and fastq_filterpair.cpp.
+// (fastq_index_readnames, src/fastq.c:396-439) as bulk calls.  Included by fastq_info.cpp, fastq_filterpair.cpp,
+// fastq_split_interleaved.cpp and fastq_pre_barcodes.cpp.
 #pragma once
 #include <regex.h>
 
@@ -26,9 +27,9 @@ fqg_ctx* g_ctx = nullptr;
     if (rc__ != 0) die_lib(#call, rc__); \
   } while (0)
 
-size_t piece_bytes() {
+size_t piece_bytes(size_t default_mb = 128) {
   const char* e = getenv("FQGPU_CHUNK_MB");
-  size_t mb = e ? strtoull(e, nullptr, 10) : 128;  // (3 pinned slots of this size: fq_input.h; pinning them is part of the start-up)
+  size_t mb = e ? strtoull(e, nullptr, 10) : default_mb;  // (3 pinned slots of this size: fq_input.h; pinning them is part of the start-up)
   if (mb < 1) mb = 1;
   return mb << 20;
 }

@@ -39,6 +39,12 @@ namespace fqhost {
     fprintf(stderr, __VA_ARGS__); \
     fprintf(stderr, "\n");        \
   } while (0)
+#define FQ_PRINT_INFO(...)        \
+  do {                            \
+    fprintf(stderr, "INFO:");     \
+    fprintf(stderr, __VA_ARGS__); \
+    fprintf(stderr, "\n");        \
+  } while (0)
 constexpr int kExitParams = 1, kExitSys = 2, kExitFormat = 3;
 
 // How the programs leave: with everything they said flushed, and WITHOUT exit()'s hooks.  The HIP runtime tears itself

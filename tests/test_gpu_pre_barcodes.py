@@ -67,6 +67,17 @@ def test_golden_invocations(i):
     golden_check(GOLDEN[i], PLAIN_RUNS.get((i, None)))
 
 
+# FQGPU_SERIAL_LOOP=1: the loop that --interleaved input and a run started over on re-framed input go through, here on
+# every kind of input - the messages and stopping rules of the two loops are the same code and must give the same text
+SERIAL = (("FQGPU_SERIAL_LOOP", "1"),)
+SERIAL_RUNS = SideBySide(golden_run, [(i, SERIAL) for i in range(len(GOLDEN))])
+
+
+@pytest.mark.parametrize("i", range(len(GOLDEN)), ids=GOLDEN_IDS)
+def test_golden_invocations_serial_loop(i):
+    golden_check(GOLDEN[i], SERIAL_RUNS.get((i, SERIAL)))
+
+
 def make_10x(rng, n, umi_q_low=0.05, short=0.01):
     """R1 = 16 bp cell + 10 bp UMI, R2 = 40..150 bp cDNA; same names before the blank."""
     bases = np.frombuffer(b"ACGTN", dtype=np.uint8)
@@ -335,8 +346,8 @@ def test_several_devices_file_sets(name):
 
 @pytest.mark.parametrize("extra", [["--sam", "--outfile1", "-"], ["--sam", "--10x", "--outfile1", "-"], ["--outfile1", "o.fastq.gz"]],
                          ids=["sam", "sam10x", "fastq"])
-@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}, {"FQGPU_DEVICES": "0,0", "FQGPU_BLOCK_RECORDS": "7"}],
-                         ids=["default", "tiny_tiles", "devices"])
+@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}, {"FQGPU_DEVICES": "0,0", "FQGPU_BLOCK_RECORDS": "7"},
+                                 {"FQGPU_SERIAL_LOOP": "1"}], ids=["default", "tiny_tiles", "devices", "serial_loop"])
 def test_quality_line_shorter_than_the_barcode_range(extra, env):
     """a record of the barcode file whose quality line ends before offset + size (a damaged file: '+' twice, a quality
     line cut short): the reference copies the quality characters with strncpy from a buffer that still holds the bytes of
@@ -405,7 +416,7 @@ def _casava_names(n):
     return out
 
 
-@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}], ids=["default", "tiny_tiles"])
+@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}, {"FQGPU_SERIAL_LOOP": "1"}], ids=["default", "tiny_tiles", "serial_loop"])
 @pytest.mark.parametrize("extra", [["--sam", "--outfile1", "-"], ["--outfile1", "o.fastq.gz"]], ids=["sam", "fastq"])
 def test_names_that_agree_in_every_shape(extra, env):
     rng = np.random.default_rng(77)
@@ -440,7 +451,7 @@ MISMATCHES = {
 }
 
 
-@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}], ids=["default", "tiny_tiles"])
+@pytest.mark.parametrize("env", [None, {"FQGPU_BC_LDS": "4096"}, {"FQGPU_SERIAL_LOOP": "1"}], ids=["default", "tiny_tiles", "serial_loop"])
 @pytest.mark.parametrize("shape", sorted(MISMATCHES))
 def test_names_that_do_not_agree(shape, env):
     """the first iteration whose names differ stops the program, discards in front of it are counted, what was printed
@@ -472,7 +483,8 @@ def test_names_that_do_not_agree(shape, env):
         assert strip_progress(err) == strip_progress(want["stderr"])
 
 
-@pytest.mark.parametrize("env", [None, {"FQGPU_DEVICES": "0,0", "FQGPU_BLOCK_RECORDS": "3"}], ids=["default", "devices"])
+@pytest.mark.parametrize("env", [None, {"FQGPU_DEVICES": "0,0", "FQGPU_BLOCK_RECORDS": "3"}, {"FQGPU_SERIAL_LOOP": "1"}],
+                         ids=["default", "devices", "serial_loop"])
 @pytest.mark.parametrize("open_end", [True, False], ids=["no_last_newline", "last_newline"])
 @pytest.mark.parametrize("which", ["r1", "r2"])
 def test_loop_condition_ends_the_loop_before_a_truncated_record_is_read(which, open_end, env):

@@ -1,7 +1,7 @@
 """ASan / UBSan (and TSan for the reader thread) builds of the CPU-side C / C++ of this repository (SURVEY section 5,
 sanitizer row): the oracle restatements (oracle/fq_oracle.c, rl_oracle.c), the container code of libfastq_gpu.so that
 needs no GPU (compat/range_list_compat.cpp), the host-side (de)compression (host/fq_parallel.h) and the host stager
-(host/fq_source.h, fq_input.h, fq_multi.h, fq_blocks.h, fq_ordered.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
+(host/fq_source.h, fq_input.h, fq_multi.h, fq_blocks.h, fq_ordered.h, fq_out_pool.h).  Each is compiled with a small driver under tests/cxx/ and must run clean."""
 import gzip
 import os
 import subprocess
@@ -329,3 +329,18 @@ def test_ordered_worker_pool_runs_clean(tmpdir, san):
     subprocess.run(["g++", "-std=c++17", "-pthread", "-Wall", "-Wextra"] + flags + ["-o", exe, os.path.join(CXX, "ordered_run_check.cpp")], check=True)
     p = subprocess.run([exe], env=dict(ENV, TSAN_OPTIONS="halt_on_error=1"), capture_output=True, timeout=120)
     assert p.returncode == 0 and p.stdout.startswith(b"ok 48"), (p.stdout, p.stderr.decode()[-1500:])
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_output_buffer_pool_runs_clean(tmpdir, san):
+    """fq_out_pool.h (the pinned buffers a batch's text comes back in, under both loops of fastq_pre_barcodes): never more
+    than `limit` buffers alive; take waits for give, and stop() sends a waiting take home with nothing; a free buffer
+    that is too small is replaced, not counted beside its successor; the smallest buffer that fits is taken; without
+    pinned memory a pageable buffer does it and goes back through free(); without any memory take brings nothing and
+    uses up no slot (the allocators may return NULL here, as they do in the programs).  Every case ends by itself."""
+    flags = ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-g", "-O1"]
+    exe = str(tmpdir / ("outpool_" + san.split(",")[0]))
+    subprocess.run(["g++", "-std=c++17", "-pthread", "-Wall", "-Wextra"] + flags + ["-o", exe, os.path.join(CXX, "out_pool_check.cpp")], check=True)
+    env = dict(ENV, ASAN_OPTIONS=ENV["ASAN_OPTIONS"] + ":allocator_may_return_null=1", TSAN_OPTIONS="halt_on_error=1:allocator_may_return_null=1")
+    p = subprocess.run([exe], env=env, capture_output=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.startswith(b"ok 12"), (p.stdout, p.stderr.decode()[-1500:])
