@@ -125,9 +125,11 @@ struct CallState {
   unsigned int pad_;
   unsigned long long trunc_record;    // frame-only images: min record whose 2nd, 3rd or 4th line starts with NUL
   // the streaming pass in parts (k_stream_pass1_lines): newlines up to and including part p; the steps the line workers
-  // inside the pass-1 launches have done
+  // inside the pass-1 launches have done: steps [0, lines_done_steps), without a gap; lines_done[p]: what the workers of
+  // part p left for those of part p + 1 (fqg_part_steps.h: the end of their steps, or kPartDeclined)
   unsigned long long part_newlines[4];
   unsigned long long lines_done_steps;
+  unsigned long long lines_done[4];
 };
 
 // Device counterpart of FASTQ_FILE's counters (src/fastq.h:116-122).

@@ -32,6 +32,7 @@
 #include "fqg_device.h"
 #include "fqg_type_spans.h"
 #include "fqg_mark_pack.h"
+#include "fqg_part_steps.h"
 
 namespace fqg {
 
@@ -1301,7 +1302,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
 // start first and keep one slot per CU -, the others are pass-1 workgroups of chunks [chunk_first, n_chunks).  The line
 // workers take what they need from DEVICE memory: the newline count behind the parts scanned so far (CallState::
 // part_newlines, k_scan_b) gives their steps - every step whose ranks are all staged - and the flags that send an image
-// to the two-pass path (NUL, CR, high bytes, a chunk with too many newlines) make them do nothing.  Their statistics go
+// to the two-pass path (NUL, CR, high bytes, a chunk with too many newlines) make them do nothing.  A part whose newline
+// density the kernel without a search is not made for is left to the launches behind the parts, and so is every part
+// after it: the steps the workers have done are [0, CallState::lines_done_steps), without a gap (fqg_part_steps.h).
+// Their statistics go
 // to accumulators the caller merges once the whole image has passed (k_acc_merge): a later part can still raise a flag.
 // ------------------------------------------------------------------------------------------
 template <int NAMES>
@@ -1319,16 +1323,26 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   }
   // ---- a line worker: the steps of part `part`, from what the scans have left in the call state ----
   if (__hip_atomic_load(&cs->flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (kFlagNul | kFlagCr | kFlagHigh | kFlagStageOverflow)) return;
-  const unsigned long long R = cs->part_newlines[part], R0 = part ? cs->part_newlines[part - 1] : 0ull;
-  const double per_chunk = (double)R / (double)(chunk_first ? chunk_first : 1u);
-  if (per_chunk > 60.0 || per_chunk < 32.0) return;  // (the host decides the same way for the whole image: frame_stream)
+  // (the host decides the same way for the whole image - stream_lines -, and begins at lines_done_steps: the workers of a
+  // part run only directly behind the steps that are done, fqg_part_steps.h.  lines_done[part - 1] is of the launch before
+  // this one, lines_done[part] for the next: nobody reads it in this launch)
+  static_assert(kPartStepRanks == (uint64_t)(4 * kWave * kLinesPer), "a step of the line kernels");
+  // (what is read here is the same in every lane, and every lane is active: saying so keeps it in scalar registers - as
+  // vector values the three counts cost two more vector registers than the 72 of seven wavefronts per SIMD, 12 bytes of
+  // scratch per lane in a kernel whose other workgroups are pass 1)
+  const unsigned long long R = readlane64(cs->part_newlines[part], 0), R0 = part ? readlane64(cs->part_newlines[part - 1], 0) : 0ull;
+  const PartSteps ps = part_steps(R0, R, chunk_first, part ? readlane64(cs->lines_done[part - 1], 0) : 0ull);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    cs->lines_done[part] = ps.done;
+    if (ps.run) cs->lines_done_steps = ps.step_hi;
+  }
+  if (!ps.run) return;
   A.n_newlines = R;
   A.n_lines = R;
   A.limit = R & ~3ull;
   A.cr.n_chunks = chunk_first;
-  A.step_lo = R0 / (uint64_t)(4 * kWave * kLinesPer);
-  A.step_hi = R / (uint64_t)(4 * kWave * kLinesPer);  // full steps only: every rank of theirs has a staged entry
-  if (blockIdx.x == 0 && threadIdx.x == 0) cs->lines_done_steps = A.step_hi;
+  A.step_lo = ps.step_lo;
+  A.step_hi = ps.step_hi;  // full steps only: every rank of theirs has a staged entry
   if (A.step_hi <= A.step_lo) return;
   stream_lines_fast_body(A, todo, blockIdx.x, line_workers, lds.lf);
 }

@@ -4,6 +4,7 @@ the all-to-all is done by hand, every owner runs its fingerprint set, candidates
 the name bytes.  The finding must be the one the oracle's serial loop makes on the whole file.  The
 same protocol through fastq_utils_amd.dist.global_first_duplicate on a 1-rank RCCL group."""
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -94,9 +95,10 @@ def oracle_first_duplicate(img):
 @pytest.mark.parametrize("style", ["casava", "slash", "int", "nosuffix"])
 @pytest.mark.parametrize("n_shards", [1, 2, 5, 8])
 def test_virtual_ranks_find_what_the_serial_loop_finds(ctx, style, n_shards):
-    rng = np.random.default_rng(hash((style, n_shards)) & 0xFFFF)
+    seed = zlib.crc32(repr((style, n_shards)).encode()) & 0xFFFF  # (the same image in every run: not hash())
+    rng = np.random.default_rng(seed)
     img = fuzz.make_fastq(rng, 4000, 20, 60, style)
-    assert virtual_first_duplicate(ctx, img, n_shards) is None and oracle_first_duplicate(img) is None
+    assert virtual_first_duplicate(ctx, img, n_shards) is None and oracle_first_duplicate(img) is None, f"seed={seed}"
     recs = records_of(img)
     # plant repeats: far apart (other shard), near (same shard), and two competing ones
     for plan in ([(3900, 17)], [(1201, 1200)], [(3000, 10), (2500, 2400), (3999, 0)]):
@@ -107,8 +109,8 @@ def test_virtual_ranks_find_what_the_serial_loop_finds(ctx, style, n_shards):
         bad = b"".join(rr)
         want = oracle_first_duplicate(bad)
         got = virtual_first_duplicate(ctx, bad, n_shards)
-        assert want == min(d for d, _ in plan)
-        assert got is not None and got[0] == want
+        assert want == min(d for d, _ in plan), f"seed={seed} plan={plan}"
+        assert got is not None and got[0] == want, f"seed={seed} plan={plan} got={got} want={want}"
 
 
 def test_protocol_through_a_one_rank_rccl_group(ctx):
