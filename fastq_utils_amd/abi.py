@@ -43,6 +43,7 @@ EXPORTS = [
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
     "fqg_bam2fastq", "fqg_bam2fastq_output", "fqg_deflate", "fqg_text_deflate", "fqg_deflate_output",
     "fqg_bgzf_deflate", "fqg_text_bgzf_deflate", "fqg_deflate_output_begin", "fqg_deflate_output_wait",
+    "fqg_bgzf_inflate", "fqg_inflate_output", "fqg_inflate_device",
     "fqg_umi_count", "fqg_umi_features", "fqg_umi_record_features", "fqg_umi_replayed_features", "fqg_umi_umis",
     "fqg_umi_cells", "fqg_umi_entries", "fqg_umi_emit",
     "fqg_fp_owner", "fqg_names_fingerprints", "fqg_names_fingerprints_acct", "fqg_names_fingerprints_named", "fqg_frame_name_records", "fqg_frame_names_equal", "fqg_device_alloc", "fqg_device_free",
@@ -62,6 +63,14 @@ class LibraryMissing(RuntimeError):
 class DeflateResult(C.Structure):
     _fields_ = [("text_bytes", C.c_uint64), ("n_members", C.c_uint64), ("gz_bytes", C.c_uint64),
                 ("tail_bytes", C.c_uint64)]
+
+
+class InflateResult(C.Structure):
+    _fields_ = [("raw_bytes", C.c_uint64), ("n_blocks", C.c_uint64), ("out_bytes", C.c_uint64), ("bad_block", C.c_uint64),
+                ("crc_block", C.c_uint64), ("code", C.c_int32), ("reserved", C.c_int32)]
+
+
+NO_BLOCK = 2 ** 64 - 1  # bad_block / crc_block: none
 
 
 class FileState(C.Structure):
@@ -326,6 +335,10 @@ def load():
     L.fqg_text_bgzf_deflate.argtypes = L.fqg_text_deflate.argtypes
     L.fqg_deflate_output_begin.argtypes = [vp, vp, u64]
     L.fqg_deflate_output_wait.argtypes = [vp]
+    L.fqg_bgzf_inflate.argtypes = [vp, vp, u64, C.POINTER(InflateResult)]
+    L.fqg_inflate_output.argtypes = [vp, u64, vp, u64]
+    L.fqg_inflate_device.argtypes = [vp]
+    L.fqg_inflate_device.restype = vp
     L.fqg_umi_emit.argtypes = [vp, C.POINTER(C.c_uint32), u64, C.c_uint32, C.POINTER(UmiResult)]
     L.fqg_umi_features.argtypes = [vp, vp, u64]
     L.fqg_umi_cells.argtypes = [vp, C.POINTER(u64), u64]
@@ -1067,6 +1080,26 @@ class Context:
 
     def deflate_output_wait(self):
         self._check(load().fqg_deflate_output_wait(self.h))
+
+    def bgzf_inflate(self, raw, want_output=True):
+        """fqg_bgzf_inflate: a whole BGZF file (bytes) inflated on the device.  Returns the result fields and, with
+        want_output and no refused block, `data`: the inflated stream (inflate_output fetches a part of it,
+        inflate_device is where it lies)."""
+        buf = C.create_string_buffer(bytes(raw), max(1, len(raw)))
+        r = InflateResult()
+        self._check(load().fqg_bgzf_inflate(self.h, buf, len(raw), C.byref(r)))
+        out = {k: int(getattr(r, k)) for k, _ in InflateResult._fields_ if k != "reserved"}
+        if want_output and out["bad_block"] == NO_BLOCK:
+            out["data"] = self.inflate_output(0, out["out_bytes"])
+        return out
+
+    def inflate_output(self, first, nbytes):
+        dst = C.create_string_buffer(max(1, nbytes))
+        self._check(load().fqg_inflate_output(self.h, first, dst, nbytes))
+        return dst.raw[:nbytes]
+
+    def inflate_device(self):
+        return load().fqg_inflate_device(self.h) or 0
 
     def _deflate_result(self, r, want_output):
         out = {k: int(getattr(r, k)) for k, _ in DeflateResult._fields_}

@@ -31,6 +31,7 @@
 #include "fqg_bamtags_kernels.hip"
 #include "fqg_bam2fastq_kernels.hip"
 #include "fqg_deflate_kernels.hip"
+#include "fqg_inflate_kernels.hip"
 
 using namespace fqg;
 
@@ -172,6 +173,11 @@ struct fqg_ctx {
   OutText gz_text;
   DevBuf gz_in, gz_carry, gz_slots, gz_sizes, gz_off, gz_sums, gz_toks, gz_tab;
   bool gz_tab_ready = false;
+  // fqg_bgzf_inflate: the inflated stream of the last call in a buffer no other call moves (the BAM calls read it where it
+  // lies), and the call's scratch - the file, one row per block, their status words, the two first-block cells
+  DevBuf inf_out, inf_raw, inf_rows, inf_status, inf_first;
+  uint64_t inf_bytes = 0;
+  bool inf_valid = false;
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
 
@@ -477,7 +483,8 @@ void fqg_close(fqg_ctx* c) {
   release(c->bc_tile_big);
   for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call,
                     &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf, &c->gz_text.buf, &c->gz_in, &c->gz_carry,
-                    &c->gz_slots, &c->gz_sizes, &c->gz_off, &c->gz_sums, &c->gz_toks, &c->gz_tab})
+                    &c->gz_slots, &c->gz_sizes, &c->gz_off, &c->gz_sums, &c->gz_toks, &c->gz_tab, &c->inf_out, &c->inf_raw,
+                    &c->inf_rows, &c->inf_status, &c->inf_first})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
@@ -541,8 +548,10 @@ int fqg_release_scratch(fqg_ctx* c) {
   for (DevBuf* b : {&c->image, &c->tile_counts, &c->tile_local, &c->span_sums, &c->line_end, &c->records, &c->suspect, &c->list,
                     &c->stage, &c->cinfo, &c->queue, &c->redo, &c->lines_slow, &c->build_keys[0], &c->build_keys[1],
                     &c->build_cursor, &c->build_spill, &c->name_recs, &c->name_hcount, &c->name_redo, &c->name_redo_chunks,
-                    &c->bc_status, &c->bc_tile_big})
+                    &c->bc_status, &c->bc_tile_big, &c->inf_out, &c->inf_raw, &c->inf_rows, &c->inf_status, &c->inf_first})
     release(*b);
+  c->inf_valid = false;  // (fqg_inflate_device: valid until here)
+  c->inf_bytes = 0;
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
     release(c->bc_off[i]);
@@ -2792,5 +2801,6 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 #include "fqg_bam2fastq_abi.inc"
 #include "fqg_split_abi.inc"
 #include "fqg_deflate_abi.inc"
+#include "fqg_inflate_abi.inc"
 
 }  // extern "C"

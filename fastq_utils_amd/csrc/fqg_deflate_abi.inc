@@ -34,6 +34,20 @@ void gz_make_tables(GzTables& T) {
   }
 }
 
+// the tables on the device, uploaded once per context (fqg_bgzf_inflate reads the same ones)
+int gz_upload_tables(fqg_ctx* c) {
+  if (c->gz_tab_ready) return 0;
+  static const GzTables tables = [] {
+    GzTables T;
+    gz_make_tables(T);
+    return T;
+  }();
+  NEED(ensure(c, c->gz_tab, sizeof(GzTables)));
+  HIP_TRY(c, hipMemcpyAsync(c->gz_tab.p, &tables, sizeof(GzTables), hipMemcpyHostToDevice, c->stream));
+  c->gz_tab_ready = true;
+  return 0;
+}
+
 // the workgroups of k_deflate_members that are resident at once (members are dealt round-robin)
 unsigned gz_resident_groups(fqg_ctx* c) {
   int per_cu = 0;
@@ -54,16 +68,7 @@ int gz_run(fqg_ctx* c, uint32_t frame, const void* carry, uint64_t carry_bytes, 
   const uint64_t n_members = n_full + ((final && (rest || (!n_full && !bgzf))) ? 1 : 0);
   const uint64_t eof_bytes = bgzf && final ? sizeof(kBgzfEof) : 0;
   const uint64_t tail = final ? 0 : rest, member_text = text_bytes - tail;
-  if (!c->gz_tab_ready) {
-    static const GzTables tables = [] {
-      GzTables T;
-      gz_make_tables(T);
-      return T;
-    }();
-    NEED(ensure(c, c->gz_tab, sizeof(GzTables)));
-    HIP_TRY(c, hipMemcpyAsync(c->gz_tab.p, &tables, sizeof(GzTables), hipMemcpyHostToDevice, c->stream));
-    c->gz_tab_ready = true;
-  }
+  NEED(gz_upload_tables(c));
   if (carry_bytes) {
     NEED(ensure(c, c->gz_carry, carry_bytes + 64));  // (a member inside the carry is staged in whole 16-byte words)
     HIP_TRY(c, hipMemcpyAsync(c->gz_carry.p, carry, carry_bytes, hipMemcpyHostToDevice, c->stream));

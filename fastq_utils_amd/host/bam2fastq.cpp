@@ -106,7 +106,7 @@ int main(int argc, char* argv[]) {
     leave(2);
   }
   BamInput bam;
-  bam.inflate(in, bam_file);
+  bam.inflate(in, bam_file, g_ctx);
   bam.index(bam_file);  // (a record cut short ends the loop, :249)
   const std::vector<uint8_t>& stream = bam.stream;
   const std::vector<uint64_t>& offsets = bam.offsets;
@@ -135,7 +135,8 @@ int main(int argc, char* argv[]) {
     prm.tenx = tenx != 0;
     prm.first_alignment = done;
     fqg_b2f_result res;
-    rc = fqg_bam2fastq(g_ctx, stream.data() + p0, p1 - p0, FQG_MEM_HOST, local.data(), last - done, &prm, &res);
+    rc = fqg_bam2fastq(g_ctx, bam.device ? bam.device + p0 : stream.data() + p0, p1 - p0, bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST,
+                       local.data(), last - done, &prm, &res);
     if (rc != 0) {
       PRINT_ERROR("GPU library failure in fqg_bam2fastq (%d): %s", rc, fqg_last_error(g_ctx));
       leave(2);

@@ -129,7 +129,7 @@ int main(int argc, char* argv[]) {
     leave(2);
   }
   BamInput bam;
-  bam.inflate(in, inbam_file);
+  bam.inflate(in, inbam_file, g_ctx);
   bam.index(inbam_file);
   const std::vector<uint8_t>& stream = bam.stream;
   const std::vector<uint64_t>& offsets = bam.offsets;
@@ -199,7 +199,8 @@ int main(int argc, char* argv[]) {
   prm.names = names.data();
   prm.names_bytes = names.size();
   fqg_bam_tags_result res;
-  rc = fqg_bam_add_tags(g_ctx, stream.data(), used, FQG_MEM_HOST, offsets.data(), n_rec, &prm, &res);
+  rc = fqg_bam_add_tags(g_ctx, bam.device ? bam.device : stream.data(), used, bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(),
+                        n_rec, &prm, &res);
   if (rc != 0) {
     PRINT_ERROR("GPU library failure in fqg_bam_add_tags (%d): %s", rc, fqg_last_error(g_ctx));
     leave(2);

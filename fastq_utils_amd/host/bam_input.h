@@ -2,6 +2,7 @@
 // they leave, how they report, and the input side - the whole file read, its BGZF members inflated back to back
 // (SAM/BAM specification, section 4.1), the alignment records found by their block_size fields.
 #pragma once
+#include <string.h>
 #include <unistd.h>
 
 #include "../../include/fqg.h"
@@ -42,14 +43,48 @@ inline bool index_records(const uint8_t* stream, size_t nbytes, std::vector<uint
 
 // The input of a program in two steps (bam_umi_count says "Processing" and creates its files between them); each
 // prints its message and leaves with status 2 when it fails.
+//
+// FQGPU_INFLATE_GPU=1 (and a context): the BGZF blocks are inflated on the device (fqg_bgzf_inflate, docs/host_gzip.md
+// section 4).  The stream comes back once for the host's walk over the records and stays on the device, where the bulk
+// calls read it (`device`: FQG_MEM_DEVICE, nothing is uploaded a second time).  A file the library's header walk refuses,
+// or a block that does not inflate, is the message and the status of the host path: the two walks have the same rules,
+// and the device's verdict on a block is zlib's.  A wrong CRC-32 is not looked at, as the host path (raw inflate) does
+// not look at it.  FQGPU_INFLATE_DEBUG=1 says on stderr which inflate ran.
 struct BamInput {
   std::vector<uint8_t> stream;    // the inflated file
   std::vector<uint64_t> offsets;  // of its alignment records
   uint64_t n_rec = 0, used = 0;   // how many; the end of the last complete one
+  const uint8_t* device = nullptr;  // the inflated file on the device; null: it is in `stream` alone
 
-  void inflate(FILE* in, const char* name) {
+  void inflate(FILE* in, const char* name, fqg_ctx* ctx = nullptr) {
     std::vector<uint8_t> raw;
-    if (!read_all(in, raw) || !fqhost::bgzf_inflate_parallel(raw, stream)) {
+    bool ok = read_all(in, raw);
+    const char* e = getenv("FQGPU_INFLATE_GPU");
+    const bool on_device = ctx && e && !strcmp(e, "1");
+    unsigned long long n_blocks = 0;
+    if (ok && on_device) {
+      fqg_inflate_result r;
+      int rc = fqg_bgzf_inflate(ctx, raw.data(), raw.size(), &r);
+      if (rc == 0 && r.bad_block == UINT64_MAX) {
+        stream.resize(r.out_bytes);
+        rc = fqg_inflate_output(ctx, 0, stream.data(), r.out_bytes);
+        device = static_cast<const uint8_t*>(fqg_inflate_device(ctx));
+        n_blocks = r.n_blocks;
+      } else if (rc == 0 || rc == FQG_ERR_ARG) ok = false;
+      if (ok && rc != 0) {
+        PRINT_ERROR("GPU library failure in fqg_bgzf_inflate (%d): %s", rc, fqg_last_error(ctx));
+        leave(2);
+      }
+    } else if (ok) {
+      size_t n = 0;
+      ok = fqhost::bgzf_inflate_parallel(raw, stream, &n);
+      n_blocks = n;
+    }
+    if (getenv("FQGPU_INFLATE_DEBUG")) {
+      if (ok) fprintf(stderr, "[inflate] %s: %llu blocks\n", on_device ? "device" : "host", n_blocks);
+      else fprintf(stderr, "[inflate] %s: refused\n", on_device ? "device" : "host");
+    }
+    if (!ok) {
       PRINT_ERROR("%s is not a readable BGZF / BAM file", name);
       leave(2);
     }

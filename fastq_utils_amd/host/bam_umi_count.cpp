@@ -189,8 +189,19 @@ int main(int argc, char* argv[]) {
     PRINT_ERROR("no usable MI355X device (fqg_open: %d); this program has no CPU path", rc);
     leave(2);
   }
+  // (FQGPU_INFLATE_GPU: a run over several contexts keeps the host inflate - the other contexts take their ranges of
+  // the stream from host memory, as fastq_pre_barcodes over several contexts keeps the host compressor)
+  std::vector<int> devs;
+  if (const char* e = getenv("FQGPU_DEVICES"))
+    for (const char* p = e; *p;) {
+      char* q = nullptr;
+      const long v = strtol(p, &q, 10);
+      if (q == p) break;
+      devs.push_back((int)v);
+      p = *q == ',' ? q + 1 : q;
+    }
   BamInput bam;
-  bam.inflate(in, bam_file);
+  bam.inflate(in, bam_file, devs.size() > 1 ? nullptr : g_ctx);
   fprintf(stderr, "Processing %s\n", bam_file);
 
   const char kHdr[] = "%%MatrixMarket matrix coordinate real general\n";  // the reference prints both percent signs
@@ -246,15 +257,6 @@ int main(int argc, char* argv[]) {
   // before: its words are the reference's.
   fqhost::UmiMultiResult multi;
   {
-    std::vector<int> devs;
-    if (const char* e = getenv("FQGPU_DEVICES"))
-      for (const char* p = e; *p;) {
-        char* q = nullptr;
-        const long v = strtol(p, &q, 10);
-        if (q == p) break;
-        devs.push_back((int)v);
-        p = *q == ',' ? q + 1 : q;
-      }
     if (devs.size() > 1 && bam_sorted_by_cell && n_rec) {
       std::vector<fqg_ctx*> ctxs{g_ctx};
       for (size_t i = 1; i < devs.size(); ++i) {
@@ -289,7 +291,8 @@ int main(int argc, char* argv[]) {
     res.rl_changed = multi.rl_changed;
     res.rl_undefined = multi.rl_undefined;
   } else
-    LIB(fqg_umi_count(g_ctx, stream.data(), stream.size(), FQG_MEM_HOST, offsets.data(), n_rec, &prm, &res));
+    LIB(fqg_umi_count(g_ctx, bam.device ? bam.device : stream.data(), stream.size(), bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(), n_rec,
+                      &prm, &res));
   if (res.rl_unresolved) {  // never silently different from the reference
     fprintf(stderr, "\nERROR: bam_umi_count: a UMI set could not be replayed within this build's limits\n");
     leave(2);
@@ -307,7 +310,8 @@ int main(int argc, char* argv[]) {
   auto cells_in_front = [&] {
     fqg_umi_result part;
     if (!bam_sorted_by_cell || res.record == 0 ||
-        fqg_umi_count(g_ctx, stream.data(), stream.size(), FQG_MEM_HOST, offsets.data(), res.record, &prm, &part) != 0 ||
+        fqg_umi_count(g_ctx, bam.device ? bam.device : stream.data(), stream.size(), bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(),
+                      res.record, &prm, &part) != 0 ||
         part.code != FQG_OK || part.rl_unresolved || part.n_cells < 2)
       return;
     const uint64_t written = part.n_cells - 1;

@@ -322,7 +322,7 @@ class GzipMembers {
 };
 
 // the whole file, BGZF members inflated back to back (SAM/BAM specification, section 4.1)
-inline bool bgzf_inflate_parallel(const std::vector<uint8_t>& raw, std::vector<uint8_t>& out) {
+inline bool bgzf_inflate_parallel(const std::vector<uint8_t>& raw, std::vector<uint8_t>& out, size_t* n_blocks = nullptr) {
   struct Block {
     size_t at, size, xlen, out_at, isize;
   };
@@ -349,6 +349,7 @@ inline bool bgzf_inflate_parallel(const std::vector<uint8_t>& raw, std::vector<u
     p += bsize;
   }
   out.resize(total);
+  if (n_blocks) *n_blocks = blocks.size();
   std::atomic<bool> ok{true};
   // blocks are at most 64 KiB: hand them out in runs
   const size_t run = 64, n_runs = (blocks.size() + run - 1) / run;

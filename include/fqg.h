@@ -694,6 +694,37 @@ int fqg_deflate_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
 int fqg_deflate_output_begin(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
 int fqg_deflate_output_wait(fqg_ctx *ctx);
 
+/* ---- BGZF blocks inflated on the device ------------------------------------------------------------------
+ * fqg_bgzf_inflate takes a whole BGZF file (SAM/BAM specification 4.1) in host memory.  The block headers are walked on
+ * the host: 1f 8b 08 with FLG & 4, XLEN, the BC subfield of length 2 anywhere among the subfields, BSIZE + 1 inside the
+ * file and at least 12 + XLEN + 8; fewer than 18 bytes behind the last block are ignored (raw_bytes says where the blocks
+ * end).  A file this walk refuses, or a block whose ISIZE is above 65536, is FQG_ERR_ARG with a text in fqg_last_error, and
+ * the stream of the previous call stays as it was.  Every block's raw deflate stream is then inflated on the device to the
+ * place the ISIZEs in front of it give it.  A block is good iff its stream reaches the end-of-block of its final deflate
+ * block having written exactly ISIZE bytes - the verdict of zlib's inflate(), raw, Z_FINISH, with ISIZE bytes of room;
+ * payload bytes behind that point are not looked at, and a block with ISIZE 0 (the end-of-file block) is not looked at
+ * at all.  A block that is not good is a finding, not an error: the call returns 0, bad_block is the first such block and
+ * code says why (FQG_E_INFLATE_*); the bytes of the stream at and behind that block's place are then undefined.  The
+ * CRC-32 of every good block is compared with the stored one and the first difference REPORTED in crc_block - the bytes
+ * are delivered all the same: a caller that refuses such a file does so itself.
+ *
+ * The stream stays on the device in a buffer no other call moves or writes: fqg_inflate_device is its address (16-byte
+ * aligned; null before the first call), valid until the next fqg_bgzf_inflate, fqg_release_scratch or fqg_close, and may
+ * be handed - with an offset - to fqg_bam2fastq, fqg_bam_add_tags and fqg_umi_count as FQG_MEM_DEVICE.
+ * fqg_inflate_output copies [first, first + nbytes) of it to the host; a range that passes out_bytes is FQG_ERR_ARG. */
+typedef struct {
+  uint64_t raw_bytes;   /* bytes of `raw` that belong to blocks */
+  uint64_t n_blocks;    /* including empty ones */
+  uint64_t out_bytes;   /* sum of ISIZE */
+  uint64_t bad_block;   /* first block that does not inflate, or UINT64_MAX */
+  uint64_t crc_block;   /* first good block whose CRC-32 differs from the stored one, or UINT64_MAX */
+  int32_t code;         /* FQG_OK, or FQG_E_INFLATE_* naming why bad_block was refused */
+  int32_t reserved;
+} fqg_inflate_result;
+int fqg_bgzf_inflate(fqg_ctx *ctx, const void *raw, uint64_t nbytes, fqg_inflate_result *out);
+int fqg_inflate_output(fqg_ctx *ctx, uint64_t first, void *host_dst, uint64_t nbytes);
+const void *fqg_inflate_device(const fqg_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,7 +81,21 @@ enum fqg_code {
   FQG_E_B2F_TOO_LONG = 30,
   /* bam_aux_get / bam_aux2Z / bam1_qname read on behind the record when a field, a Z value without NUL or the read
    * name does not end inside it.  Refused. */
-  FQG_E_B2F_AUX = 31
+  FQG_E_B2F_AUX = 31,
+  /* Not reference outcomes.  fqg_bgzf_inflate: why the raw deflate stream of a BGZF block does not inflate to its ISIZE
+   * bytes - the cases in which zlib's inflate(), raw, Z_FINISH, ISIZE bytes of room, does not return Z_STREAM_END
+   * (fastq_utils_amd/csrc/fqg_inflate_core.h).  BTYPE: block type 3.  STORED: LEN != ~NLEN.  HEADER: a dynamic block's
+   * header (HLIT > 286, HDIST > 30, an over-subscribed or incomplete code, a repeat with nothing before it or past the end,
+   * no end-of-block code).  CODE: a bit pattern no symbol owns, length symbol 286 / 287, distance symbol 30 / 31.
+   * DISTANCE: further back than the block has written.  SIZE: more than ISIZE bytes, or fewer at the end.  INPUT: the
+   * payload ends before the final block does. */
+  FQG_E_INFLATE_BTYPE = 32,
+  FQG_E_INFLATE_STORED = 33,
+  FQG_E_INFLATE_HEADER = 34,
+  FQG_E_INFLATE_CODE = 35,
+  FQG_E_INFLATE_DISTANCE = 36,
+  FQG_E_INFLATE_SIZE = 37,
+  FQG_E_INFLATE_INPUT = 38
 };
 
 /* read-name formats, src/fastq.h:25-28 (INTEGERNAME and NOP share the value 2) */
