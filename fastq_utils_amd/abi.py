@@ -36,7 +36,7 @@ EXPORTS = [
     "fqg_index_destroy", "fqg_index_insert_unique", "fqg_index_match_delete", "fqg_index_probe_delete",
     "fqg_index_alive", "fqg_index_n_frames", "fqg_index_frame", "fqg_index_names_captured", "fqg_index_expect_lookups", "fqg_records_gather",
     "fqg_records_gather_output", "fqg_records_split", "fqg_records_split_output", "fqg_records_split_info", "fqg_names_compare",
-    "fqg_barcodes_transform", "fqg_barcodes_output", "fqg_barcodes_output_begin", "fqg_barcodes_output_wait", "fqg_records_filter", "fqg_records_filter_output",
+    "fqg_bam_header", "fqg_barcodes_transform", "fqg_barcodes_output", "fqg_barcodes_output_begin", "fqg_barcodes_output_wait", "fqg_records_filter", "fqg_records_filter_output",
     "fqg_whitelist_create", "fqg_whitelist_destroy", "fqg_barcodes_whitelist",
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
@@ -278,6 +278,8 @@ def load():
     L.fqg_barcodes_transform.argtypes = [vp, C.POINTER(vp), C.POINTER(FileState), C.POINTER(u64),
                                          C.POINTER(BarcodeParams), u64, u64, C.POINTER(BarcodeResult)]
     L.fqg_barcodes_output.argtypes = [vp, C.c_int, vp, u64]
+    L.fqg_bam_header.argtypes = [C.c_int, C.POINTER(C.c_char_p), vp, u64]
+    L.fqg_bam_header.restype = u64
     L.fqg_census_create.argtypes = [vp, C.POINTER(vp)]
     L.fqg_census_destroy.argtypes = [vp]
     L.fqg_census_destroy.restype = None
@@ -349,6 +351,19 @@ def load():
 
 class FqgError(RuntimeError):
     pass
+
+
+OUT_SAM, OUT_BAM = 1, 2   # fqg_barcode_params.out_sam (FQG_OUT_SAM, FQG_OUT_BAM)
+E_BAM_RECORD = 39         # fqg_codes.h FQG_E_BAM_RECORD
+
+
+def bam_header(argv) -> bytes:
+    """fqg_bam_header: the BAM header of `fastq_pre_barcodes --bam` run as argv (argv[0] = the program)"""
+    arr = (C.c_char_p * len(argv))(*[a.encode("latin-1") if isinstance(a, str) else a for a in argv])
+    n = load().fqg_bam_header(len(argv), arr, None, 0)
+    buf = C.create_string_buffer(n)
+    load().fqg_bam_header(len(argv), arr, buf, n)
+    return buf.raw[:n]
 
 
 def probe_first_record(image: bytes, is_pe: bool) -> FileState:
@@ -687,11 +702,14 @@ class Context:
         return Frame(self)
 
     def barcodes_transform(self, frames, states, n_iterations, umi=None, cell=None, sample=None, phred=33,
-                           min_qual=0, sam=True, tenx=False, first_read_number=0):
+                           min_qual=0, sam=True, tenx=False, first_read_number=0, slices=None):
         """fastq_pre_barcodes' main loop on retained frames.  frames / states: {READ1..INDEX3: Frame / FileState};
-        umi / cell / sample: (file reference, offset, size) or None.  Output stays on the device
-        (barcodes_output copies it)."""
+        umi / cell / sample: (file reference, offset, size) or None; sam: False FASTQ text, True / OUT_SAM SAM lines,
+        OUT_BAM the alignment records libbam makes of those lines; slices: {READ1 / READ2: (offset, size)} as
+        --read1_offset / --read1_size.  Output stays on the device (barcodes_output copies it)."""
         p, fr, stt, first = self._barcode_args(frames, states, umi, cell, sample, phred, min_qual, sam, tenx)
+        for x, (off, size) in (slices or {}).items():
+            p.read_offset[x], p.read_size[x] = off, size
         r = BarcodeResult()
         self._check(load().fqg_barcodes_transform(self.h, fr, stt, first, C.byref(p), n_iterations, first_read_number,
                                                   C.byref(r)))

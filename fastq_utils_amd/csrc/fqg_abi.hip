@@ -2154,6 +2154,7 @@ static int bc_make_params(fqg_ctx* c, const fqg_frame* const frames[6], const fq
   for (int x = 1; x <= 2; ++x)
     if (((bp->out_sam && x == 1) || (!bp->out_sam && bp->emit[x])) && !P.f[x].present)
       return fail(c, FQG_ERR_ARG, "fqg_barcodes_transform: output requested for an absent input");
+  if (bp->out_sam < 0 || bp->out_sam > FQG_OUT_BAM) return fail(c, FQG_ERR_ARG, "fqg_barcodes_transform: out_sam is 0, 1 or 2");
   const int64_t sizes[3] = {bp->umi_size, bp->cell_size, bp->sample_size};
   for (int i = 0; i < 3; ++i)
     if (sizes[i] < 0 || sizes[i] >= 50) return fail(c, FQG_ERR_ARG, "barcode sizes must be 0..49 (MAX_BARCODE_LENGTH)");
@@ -2212,12 +2213,17 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
   if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
   {
     ProfScope ps(c, "k_bc_plan");
-#define FQG_PLAN_TILE(MASK)                                                                                       \
+#define FQG_PLAN_TILE(MASK)                                                                            \
+  do {                                                                                                 \
+    if (P.out_sam == FQG_OUT_BAM) FQG_PLAN_TILE_(MASK, true);                                          \
+    else FQG_PLAN_TILE_(MASK, false);                                                                  \
+  } while (0)
+#define FQG_PLAN_TILE_(MASK, BAM)                                                                                     \
   do {                                                                                                            \
     const unsigned plan_lds = tc.plan_cap;                                                                        \
     const uint64_t plan_tiles = (n_tiles + tc.plan_m - 1) / tc.plan_m;                                            \
-    const unsigned grid = (unsigned)std::min<uint64_t>(plan_tiles, resident_waves(c, (const void*)k_bc_plan_tile<MASK>, plan_lds)); \
-    hipLaunchKernelGGL(k_bc_plan_tile<MASK>, dim3(grid), dim3(kWave), plan_lds, c->stream, P, tc, n_iter,          \
+    const unsigned grid = (unsigned)std::min<uint64_t>(plan_tiles, resident_waves(c, (const void*)k_bc_plan_tile<MASK, BAM>, plan_lds)); \
+    hipLaunchKernelGGL((k_bc_plan_tile<MASK, BAM>), dim3(grid), dim3(kWave), plan_lds, c->stream, P, tc, n_iter,          \
                        (uint8_t*)c->bc_status.p, (uint32_t*)c->bc_len[0].p, (uint32_t*)c->bc_len[1].p,            \
                        (uint32_t*)c->bc_len[2].p, (uint8_t*)c->bc_tile_big.p, c->d_bcall);                         \
   } while (0)
@@ -2229,6 +2235,7 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
       default: FQG_PLAN_TILE(0); break;
     }
 #undef FQG_PLAN_TILE
+#undef FQG_PLAN_TILE_
   }
   HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2285,8 +2292,9 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
     case 0x0E: FQG_EMIT_TILE(SAM, 0x0E); break;   \
     default: FQG_EMIT_TILE(SAM, 0); break;        \
   }
-    if (P.out_sam) FQG_EMIT_TILE_MASKS(true)
-    else FQG_EMIT_TILE_MASKS(false)
+    if (P.out_sam == FQG_OUT_BAM) FQG_EMIT_TILE_MASKS(kEmitBam)
+    else if (P.out_sam) FQG_EMIT_TILE_MASKS(kEmitSam)
+    else FQG_EMIT_TILE_MASKS(kEmitFastq)
 #undef FQG_EMIT_TILE_MASKS
 #undef FQG_EMIT_TILE
     if (getenv("FQGPU_BC_DEBUG"))
@@ -2295,20 +2303,27 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
     if (n_big) {
       const unsigned grid_e =
           (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_done + 3) / 4, (uint64_t)c->cu_count * 8));
-      hipLaunchKernelGGL(k_bc_emit_direct, dim3(grid_e), dim3(kBlock), 0, c->stream, P, tc, n_done,
-                         (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo[0], eo[1], eo[2], c->d_bcall);
+      if (P.out_sam == FQG_OUT_BAM)
+        hipLaunchKernelGGL(k_bc_emit_direct<true>, dim3(grid_e), dim3(kBlock), 0, c->stream, P, tc, n_done,
+                           (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo[0], eo[1], eo[2], c->d_bcall);
+      else
+        hipLaunchKernelGGL(k_bc_emit_direct<false>, dim3(grid_e), dim3(kBlock), 0, c->stream, P, tc, n_done,
+                           (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo[0], eo[1], eo[2], c->d_bcall);
     }
   }
   HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  if (c->h_bcall->first_finding != ~0ull) {
+  // (a refused BAM record is found by the plan, which looks at all n_iter iterations: one behind where interleaved input
+  // re-synchronises is none)
+  if (c->h_bcall->first_finding != ~0ull && (c->h_bcall->first_finding >> 8) < n_done) {
     // Names that do not agree (or a header without '@') at iteration k: the reference stops there, before it looks at
     // the iteration's barcodes.  What the batch yields is what lies in front of k: the text up to k's place in every
     // output, the discards among the first k iterations.
     const uint64_t k = c->h_bcall->first_finding >> 8;
     out->iteration = k;
     out->code = (int32_t)((c->h_bcall->first_finding & 0xFF) >> 3);
+    if (out->code == (int32_t)kBcFindBam) out->code = FQG_E_BAM_RECORD;
     out->file = (int32_t)(c->h_bcall->first_finding & 7);
     out->n_done = k;
     out->n_discarded = out->n_short = 0;

@@ -2,7 +2,8 @@
 // (reference src/fastq_pre_barcodes.c:594-727): lock-step records of up to five files, read
 // names must agree, UMI / cell / sample substrings are cut out (with an optional minimum base
 // quality), the header gets the STAGS_..._ETAGS_ prefix, reads are optionally sliced, and the
-// result is emitted as FASTQ text (one or two outputs) or as SAM lines.
+// result is emitted as FASTQ text (one or two outputs), as SAM lines, or as the BAM alignment records that samtools
+// 0.1.19 makes of those lines (fastq_pre_barcodes --bam: the file `... --sam | samtools view -b -` writes).
 //
 // Three launches per batch of iterations; plan and emit work on TILES of T consecutive iterations,
 // one wavefront per tile, whose records (contiguous in every input image) are first copied into LDS
@@ -11,7 +12,7 @@
 //                   every output - from the line index and the bytes of the barcode-carrying files alone
 //   scan            64-bit exclusive prefix of the byte counts -> where each iteration writes
 //   k_bc_emit_tile  the name checks (on the headers of every file, which it stages anyway), then one lane per
-//                   output line (SAM) or record (FASTQ): the lane writes its text into the tile's LDS output
+//                   output line (SAM), alignment record (BAM) or record (FASTQ): the lane writes its text into the tile's LDS output
 //                   area, which then goes to the output image with 16-byte stores; three tiles under way
 // T is chosen by the host from the mean record sizes so that a tile fits its LDS areas; a tile that
 // does not fit (long reads) is flagged by the plan and handled by the slower direct paths (records read
@@ -50,7 +51,7 @@ struct BcParams {
   int32_t n_inputs;
   int32_t umi_read, cell_read, sample_read;
   int32_t phred, min_qual;
-  int32_t out_sam, tenx;
+  int32_t out_sam, tenx;  // out_sam: 0 FASTQ, FQG_OUT_SAM, FQG_OUT_BAM
   int32_t has_nul;  // some input's image holds NUL bytes: every tile takes the record-by-record kernels (bc_clip_nul)
   int32_t ablate;  // measurement only (FQGPU_BC_ABL, SAM emit): 1 = no line is written, 2 = no flush, 4 = no name check, 8 = no landing of the spans
   int32_t emit[3];
@@ -453,11 +454,49 @@ __device__ __forceinline__ unsigned bc_sam_flag(bool se, bool mate1) {
   return se ? 4u : (mate1 ? 77u : 141u);  // BAM_FUNMAP | FMUNMAP | FPAIRED | FREAD1/2
 }
 
+// ---- the SAM line as an alignment record (out_sam == FQG_OUT_BAM) ----
+// What libbam 0.1.19 (sam_read1, bam_import.c:237-467; bam_write1) makes of the line above: the fields are cut at every
+// isspace() byte but the blank (kseq.h KS_SEP_TAB), the read number is the name, "*" / "0" become -1, the bases go
+// through bam_nt16_table at four bits each, the qualities are byte - 33 (a QUAL of exactly "*": 0xff), and every
+// xx:Z:value becomes xx, 'Z', value, NUL.  The second mate's " CR:Z:" (a blank, no tab) stays in the value of the field
+// in front of it.
+// A finding that is not the reference's: the line is one that libbam aborts on or reads foreign memory for.  Internal
+// value (5 bits in BcCall::first_finding, behind the name findings of the same iteration); the library reports
+// FQG_E_BAM_RECORD.
+constexpr uint32_t kBcFindBam = 31;
+__device__ __forceinline__ uint32_t bc_bam_record_len(unsigned long number, bool mate1, const SamGeom& g, const BcTags& t) {
+  uint32_t n = 36 + dec_digits(number) + 1 + ((g.seq_n + 1) >> 1) + g.seq_n + 4 + g.name_n + 4 + g.qual_n;
+  if (t.n[0]) n += 8 + t.n[0] + t.qn[0];
+  if (t.n[1]) n += (mate1 ? 8u : 10u) + t.n[1] + t.qn[1];
+  if (t.n[2]) n += 8 + t.n[2] + t.qn[2];
+  return n;
+}
+// what the line's GEOMETRY says against it: an empty SEQ or QUAL (an empty QUAL is an empty op:Z: as well), SEQ and QUAL
+// of different lengths (a QUAL of one character may be "*": the emit kernel looks), an empty aux value
+__device__ __forceinline__ bool bc_bam_refused(bool mate1, const SamGeom& g, const BcTags& t) {
+  bool bad = g.seq_n == 0 || g.qual_n == 0 || g.name_n == 0 || (g.qual_n != g.seq_n && g.qual_n != 1);
+  bad |= t.n[0] && !t.qn[0] && (mate1 || !t.n[1]);  // (the second mate's QX / UY value ends in " CR:Z:...")
+  bad |= (t.n[1] && !t.qn[1]) || (t.n[2] && !t.qn[2]);
+  return bad;
+}
+// the record of one mate of an iteration: its bytes; *finding becomes (code << 3 | mate) when it has none yet
+__device__ __forceinline__ uint32_t bc_bam_mate_len(const BcParams& P, uint64_t k, bool mate1, const BcLine (&ln)[4],
+                                                    const BcTags& t, uint32_t* finding) {
+  const int x = mate1 ? 1 : 2;
+  const SamGeom g = bc_sam_geom(bc_slices(P, x), P.read_off[x], P.read_size[x], mate1, ln);
+  if (!*finding && bc_bam_refused(mate1, g, t)) *finding = (kBcFindBam << 3) | (uint32_t)x;
+  return bc_bam_record_len(P.first_read_number + k + 1, mate1, g, t);
+}
+
 // byte counts of the outputs of a kept iteration
+template <bool BAM>
 __device__ __forceinline__ void bc_out_lens(const BcParams& P, uint64_t k, const BcLine (&L)[kBcFiles][4], const BcTags& t,
-                                            uint32_t* a, uint32_t* b, uint32_t* c) {
+                                            uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* finding) {
   *a = *b = *c = 0;
-  if (P.out_sam) {
+  if (BAM) {
+    *a = bc_bam_mate_len(P, k, true, L[1], t, finding);
+    if (P.f[2].present) *a += bc_bam_mate_len(P, k, false, L[2], t, finding);
+  } else if (P.out_sam) {
     const bool se = !P.f[2].present;
     *a = bc_sam_line_len(P.first_read_number + k + 1, bc_sam_flag(se, true),
                          bc_sam_geom(bc_slices(P, 1), P.read_off[1], P.read_size[1], true, L[1]), t);
@@ -491,11 +530,24 @@ __device__ __forceinline__ uint8_t bc_decide_with(const BcParams& P, LinesOf lin
     }
   return kBcKeep;
 }
-template <int MASK, class LinesOf>
+template <int MASK, bool BAM, class LinesOf>
 __device__ __forceinline__ void bc_out_lens_with(const BcParams& P, uint64_t k, LinesOf lines_of, const BcTags& t, uint32_t* a,
-                                                 uint32_t* b, uint32_t* c) {
+                                                 uint32_t* b, uint32_t* c, uint32_t* finding) {
   *a = *b = *c = 0;
   const bool se = !bc_has<MASK>(P, 2);
+  if (BAM) {
+    {
+      BcLine ln[4];
+      lines_of(1, ln);
+      *a = bc_bam_mate_len(P, k, true, ln, t, finding);
+    }
+    if (!se) {
+      BcLine ln[4];
+      lines_of(2, ln);
+      *a += bc_bam_mate_len(P, k, false, ln, t, finding);
+    }
+    return;
+  }
   if (P.out_sam || P.emit[1]) {
     BcLine ln[4];
     lines_of(1, ln);
@@ -699,6 +751,14 @@ __device__ __forceinline__ void bc_lines_all(const BcParams& P, uint64_t k, BcLi
     if (bc_has<MASK>(P, x)) bc_lines(P.f[x], k, L[x]);
 }
 
+// a finding of an iteration (the names: the emit kernels; a refused BAM record: the plan too): the smallest (iteration << 8 | code << 3 | file) wins
+__device__ __forceinline__ void bc_report_finding(BcCall* __restrict__ call, bool active, uint64_t k, uint32_t finding) {
+  if (!__ballot(active && finding != 0)) return;  // (the usual case: one ballot)
+  const unsigned long long none = ~0ull;
+  const unsigned long long fnd = wave_min64(active && finding ? (unsigned long long)((k << 8) | finding) : none);
+  if ((threadIdx.x & 63) == 0 && fnd < __atomic_load_n(&call->first_finding, __ATOMIC_RELAXED)) atomicMin(&call->first_finding, fnd);
+}
+
 // One wavefront per PLAN tile = plan_m consecutive tiles of the emit kernel, one lane per iteration.  The plan decides
 // what the iteration's output is made of - keep / discard (get_barcode's bounds and minimum quality) and the byte count
 // of every output - from the line index and the bytes of the barcode-carrying files alone (bc_staged<PLAN>): its LDS
@@ -720,7 +780,9 @@ struct PlanShape {
   static constexpr bool ahead = MASK != 0 && MASK != 0x0A;
   static constexpr int waves = MASK == 0 ? 4 : (MASK == 0x0A ? 5 : 1);
 };
-template <int MASK>
+// BAM: the byte counts are those of alignment records (out_sam == FQG_OUT_BAM), and a record that is refused is a
+// finding - a kernel of its own, so that the kernels of the other two outputs stay what they were.
+template <int MASK, bool BAM = false>
 __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(BcParams P, BcTile tc, uint64_t n_iter, uint8_t* __restrict__ status,
                                                         uint32_t* __restrict__ len0, uint32_t* __restrict__ len1,
                                                         uint32_t* __restrict__ len2, uint8_t* __restrict__ tile_big,
@@ -754,7 +816,7 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
     else geo_of(tile, cur);
     // (an image with NUL bytes: lines are C strings, found by scanning them where they lie - bc_lines)
     BcTags t;
-    uint32_t a = 0, b = 0, c = 0;
+    uint32_t a = 0, b = 0, c = 0, refused = 0;  // refused: the iteration's line is none libbam takes (BAM records only)
     uint8_t st;
     if constexpr (MASK == 0) {
       // any set of files: a file's lines are made where they are looked at (bc_decide_with) - never all five at once
@@ -767,11 +829,11 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
       if (fit) {
         auto staged = [&](int x, BcLine(&ln)[4]) { bc_file_lines<true, MASK>(P, cur, sp, s_lds, x, ln); };
         st = bc_decide_with<true, MASK>(P, staged, &t);
-        if (st == kBcKeep) bc_out_lens_with<MASK>(P, k, staged, t, &a, &b, &c);
+        if (st == kBcKeep) bc_out_lens_with<MASK, BAM>(P, k, staged, t, &a, &b, &c, &refused);
       } else {  // long reads: from the images
         auto from_image = [&](int x, BcLine(&ln)[4]) { bc_lines(P.f[x], k, ln); };
         st = bc_decide_with<false, MASK>(P, from_image, &t);
-        if (st == kBcKeep) bc_out_lens_with<MASK>(P, k, from_image, t, &a, &b, &c);
+        if (st == kBcKeep) bc_out_lens_with<MASK, BAM>(P, k, from_image, t, &a, &b, &c, &refused);
       }
     } else {
       const bool fit = !P.has_nul && bc_stage_tile<true, MASK>(P, cur, (int)Tn - 1, lane, s_lds, plan_cap, L);
@@ -779,12 +841,12 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
       __builtin_amdgcn_wave_barrier();
       if (fit) {
         st = bc_decide_lines<true, MASK>(P, L, &t);
-        if (st == kBcKeep) bc_out_lens(P, k, L, t, &a, &b, &c);
+        if (st == kBcKeep) bc_out_lens<BAM>(P, k, L, t, &a, &b, &c, &refused);
       } else {  // long reads: from the images
         BcLine G[kBcFiles][4];
         bc_lines_all<MASK>(P, k, G);
         st = bc_decide_lines<false, MASK>(P, G, &t);
-        if (st == kBcKeep) bc_out_lens(P, k, G, t, &a, &b, &c);
+        if (st == kBcKeep) bc_out_lens<BAM>(P, k, G, t, &a, &b, &c, &refused);
       }
     }
     if (valid) {
@@ -797,6 +859,7 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
     } else {
       a = b = c = 0;
     }
+    if (BAM) bc_report_finding(call, valid, k, valid ? refused : 0u);
     const unsigned long long none = ~0ull;
     const bool dropped = valid && (st == kBcDiscardShort || st == kBcDiscardQual);
     n_dropped += dropped ? 1u : 0u;
@@ -827,14 +890,6 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
     if (n_dropped) atomicAdd(&call->discarded, (unsigned long long)n_dropped);
     if (n_short) atomicAdd(&call->short_warnings, (unsigned long long)n_short);
   }
-}
-
-// a name finding of the emit kernels: the smallest (iteration << 8 | code << 3 | file) wins
-__device__ __forceinline__ void bc_report_finding(BcCall* __restrict__ call, bool active, uint64_t k, uint32_t finding) {
-  if (!__ballot(active && finding != 0)) return;  // (the usual case: one ballot)
-  const unsigned long long none = ~0ull;
-  const unsigned long long fnd = wave_min64(active && finding ? (unsigned long long)((k << 8) | finding) : none);
-  if ((threadIdx.x & 63) == 0 && fnd < __atomic_load_n(&call->first_finding, __ATOMIC_RELAXED)) atomicMin(&call->first_finding, fnd);
 }
 
 // discarded iterations among the first n_done: one atomic per workgroup
@@ -1132,6 +1187,262 @@ __device__ __forceinline__ void bc_emit_sam_line(const BcParams& P, unsigned lon
   w.ch('\n');
 }
 
+// ---- the alignment record of a SAM line (bc_bam_record_len) ----
+// bam_nt16_table (bam_import.c:17-34) computed: '=' 0, A C M G R S V T W Y H K D B N (either case) 1..15 in that
+// order of values, '0'..'3' 1 2 4 8, everything else 15.  Two 64-bit constants hold the nibbles of 0x40..0x5f (the
+// letters by c & 31; the other columns of the table are 15), one those of 0x30..0x3f.
+__device__ __forceinline__ uint32_t bc_nt16(uint32_t c) {
+  //                               O N M L K J I H G F E D C B A @        _ ^ ] \ [ Z Y X W V U T S R Q P
+  constexpr uint64_t let_lo = 0xFF3FCFFB4FFD2E1Full, let_hi = 0xFFFFFFAF97F865FFull;
+  //                               ? > = < ; : 9 8 7 6 5 4 3 2 1 0
+  constexpr uint64_t dig = 0xFF0FFFFFFFFF8421ull;
+  // (32-bit halves, chosen by bit 3: a 64-bit select and shift per base cost the emit kernel registers it does not have)
+  const bool up = (c & 8u) != 0;
+  const uint32_t l0 = up ? (uint32_t)(let_lo >> 32) : (uint32_t)let_lo, l1 = up ? (uint32_t)(let_hi >> 32) : (uint32_t)let_hi;
+  const uint32_t d = up ? (uint32_t)(dig >> 32) : (uint32_t)dig;
+  const uint32_t half = (c & 0x40u) ? ((c & 0x10u) ? l1 : l0) : ((c & 0xF0u) == 0x30u ? d : ~0u);
+  return (c & 0x80u) ? 15u : (half >> (4u * (c & 7u))) & 15u;
+}
+// 0x80 in every byte of x that libbam would cut the line at (9..13: isspace() but the blank) or, HI, that is >= 0x80.
+// (In 32-bit halves: their constants are literals of the instructions; 64-bit ones are registers held across the
+// kernel's loop, which has none to spare.)
+template <bool HI>
+__device__ __forceinline__ uint32_t bc_bam_bad4(uint32_t x) {
+  const uint32_t lo7 = x & 0x7F7F7F7Fu;
+  const uint32_t ge9 = lo7 + 0x77777777u, ge14 = lo7 + 0x72727272u;  // bit 7: the low 7 bits are >= 9 / >= 14
+  const uint32_t sp = ge9 & ~ge14 & ~x & 0x80808080u;
+  return HI ? sp | (x & 0x80808080u) : sp;
+}
+template <bool HI>
+__device__ __forceinline__ uint32_t bc_bam_bad_bytes(uint64_t x) {
+  return bc_bam_bad4<HI>((uint32_t)x) | bc_bam_bad4<HI>((uint32_t)(x >> 32));
+}
+__device__ __forceinline__ uint64_t bc_low_bytes(uint64_t x, uint32_t n) {  // the low n bytes, n = 1..7
+  return x & ((1ull << (8u * n)) - 1ull);
+}
+// x - 33 in every byte (no borrow between bytes)
+__device__ __forceinline__ uint32_t bc_minus33_4(uint32_t x) {
+  return ((x | 0x80808080u) - 0x21212121u) ^ ((x ^ ~0x21212121u) & 0x80808080u);
+}
+__device__ __forceinline__ uint64_t bc_minus33(uint64_t x) {
+  return (uint64_t)bc_minus33_4((uint32_t)x) | ((uint64_t)bc_minus33_4((uint32_t)(x >> 32)) << 32);
+}
+// the bases of 8 bytes (the first r of them: the rest give zero nibbles) -> 4 bytes, high nibble first
+__device__ __forceinline__ uint32_t bc_pack8(uint64_t v, uint32_t r) {
+  uint32_t out = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; ++j) {
+    const uint32_t nib = j < r ? bc_nt16((uint32_t)(v >> (8 * j)) & 0xFFu) : 0u;
+    out |= nib << (8 * (j >> 1) + ((j & 1) ? 0 : 4));
+  }
+  return out;
+}
+
+// 0xffffffff made where it is stored: as a constant it is lifted out of the emit kernel's loop over the tiles into
+// registers of its own (three of them, and a fourth pair for the fill), which that loop does not have
+__device__ __forceinline__ uint32_t bc_minus_one() {
+  uint32_t v = 0xFFFFFFFFu;
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// One lane writes one record in LDS (k_bc_emit_tile).  bad: a byte that refuses the record was seen.
+struct BamLaneWriter : LaneWriter {
+  uint32_t bad = 0;
+  __device__ __forceinline__ void see(uint32_t marks) { bad |= marks; }
+  __device__ __forceinline__ void le32(uint32_t v) {
+    __builtin_memcpy(p, &v, 4);
+    p += 4;
+  }
+  // the low n (1..7) bytes of a at q
+  static __device__ __forceinline__ void put_low(uint8_t* q, uint64_t a, uint32_t n) {
+    uint32_t done = 0;
+    if (n & 4) {
+      const uint32_t w = (uint32_t)a;
+      __builtin_memcpy(q, &w, 4);
+      done = 4;
+    }
+    if (n & 2) {
+      const uint16_t w = (uint16_t)(a >> (8 * done));
+      __builtin_memcpy(q + done, &w, 2);
+      done += 2;
+    }
+    if (n & 1) q[done] = (uint8_t)(a >> (8 * done));
+  }
+  // LaneWriter::copy with the test for the bytes that refuse the record.  QUAL: p gets the bytes minus 33 (FILL: 0xff
+  // over n33 bytes instead), p + dist the bytes themselves (the op:Z: value)
+  template <bool NAME, bool QUAL>
+  __device__ __forceinline__ void checked(const uint8_t* s, uint32_t n, uint32_t dist = 0) {
+    auto st8 = [&](uint32_t at, uint64_t v) {
+      see(bc_bam_bad_bytes<false>(v));
+      if (NAME) v = at_for_blank(v);
+      if (QUAL) {
+        __builtin_memcpy(p + dist + at, &v, 8);
+        v = bc_minus33(v);
+      }
+      __builtin_memcpy(p + at, &v, 8);
+    };
+    if (n >= 8) {
+      uint32_t i = 0;
+      // (two reads in flight per LDS round trip, where LaneWriter::copy has four)
+      for (; i + 16 <= n; i += 16) {
+        const uint64_t a = ld8(s + i), b = ld8(s + i + 8);
+        st8(i, a);
+        st8(i + 8, b);
+      }
+      if (i + 8 <= n) {
+        st8(i, ld8(s + i));
+        i += 8;
+      }
+      if (i < n) st8(n - 8, ld8(s + n - 8));
+    } else if (n) {
+      uint64_t a = bc_low_bytes(ld8(s), n);  // the sources have 8 bytes of slack
+      see(bc_bam_bad_bytes<false>(a));
+      if (NAME) a = at_for_blank(a);
+      if (QUAL) {
+        put_low(p + dist, a, n);
+        a = bc_minus33(a);
+      }
+      put_low(p, a, n);
+    }
+    p += n;
+  }
+  __device__ __forceinline__ void bytes(const uint8_t* s, uint32_t n) { checked<false, false>(s, n); }
+  __device__ __forceinline__ void name(const uint8_t* s, uint32_t n) { checked<true, false>(s, n); }
+  // the quality values and, dist bytes on, the op:Z: value; fill: n_seq times 0xff instead of the values (QUAL is "*",
+  // or a refused record whose QUAL has another length than its SEQ).  What lies behind the values is written later.
+  __device__ __forceinline__ void quals(const uint8_t* s, uint32_t n, uint32_t n_seq, bool fill, uint32_t dist) {
+    if (!fill) {
+      checked<false, true>(s, n, dist);
+      return;
+    }
+    uint8_t* const q = p;
+    p += dist;
+    checked<false, false>(s, n);
+    p = q;
+    const uint64_t ff = ((uint64_t)bc_minus_one() << 32) | bc_minus_one();
+    for (uint32_t i = 0; i < n_seq; i += 8) __builtin_memcpy(p + i, &ff, 8);  // (up to 7 bytes into the aux fields: rewritten below)
+    p += n_seq;
+  }
+  // the bases at four bits each; the last word may run up to 3 bytes into the quality values, which are written next
+  __device__ __forceinline__ void bases(const uint8_t* s, uint32_t n) {
+    for (uint32_t i = 0; i < n; i += 8) {
+      const uint32_t r = n - i < 8u ? n - i : 8u;
+      uint64_t v = ld8(s + i);
+      if (r < 8) v = bc_low_bytes(v, r);
+      see(bc_bam_bad_bytes<true>(v));
+      const uint32_t w = bc_pack8(v, r);
+      __builtin_memcpy(p + (i >> 1), &w, 4);
+    }
+    p += (n + 1) >> 1;
+  }
+  __device__ __forceinline__ bool refused() const { return bad != 0; }
+};
+
+// The whole wavefront writes one record to the output image (k_bc_emit_direct), lane i byte i of every piece.
+struct BamWriter : Writer {
+  uint32_t bad = 0;  // per lane
+  static __device__ __forceinline__ uint32_t cuts(uint8_t c) { return c >= 9 && c <= 13 ? 1u : 0u; }
+  __device__ __forceinline__ void le32(uint32_t v) {
+    if (lane < 4) p[lane] = (uint8_t)(v >> (8 * lane));
+    p += 4;
+  }
+  __device__ __forceinline__ void bytes(const uint8_t* s, uint32_t n) {
+    for (uint32_t i = lane; i < n; i += kWave) {
+      bad |= cuts(s[i]);
+      p[i] = s[i];
+    }
+    p += n;
+  }
+  __device__ __forceinline__ void name(const uint8_t* s, uint32_t n) {
+    for (uint32_t i = lane; i < n; i += kWave) {
+      bad |= cuts(s[i]);
+      p[i] = s[i] == ' ' ? (uint8_t)'@' : s[i];
+    }
+    p += n;
+  }
+  __device__ __forceinline__ void quals(const uint8_t* s, uint32_t n, uint32_t n_seq, bool fill, uint32_t dist) {
+    for (uint32_t i = lane; i < n; i += kWave) {
+      bad |= cuts(s[i]);
+      p[dist + i] = s[i];
+    }
+    for (uint32_t i = lane; i < n_seq; i += kWave) p[i] = fill ? (uint8_t)0xff : (uint8_t)(s[i] - 33);
+    p += n_seq;
+  }
+  __device__ __forceinline__ void bases(const uint8_t* s, uint32_t n) {
+    const uint32_t nb = (n + 1) >> 1;
+    for (uint32_t i = lane; i < nb; i += kWave) {
+      const uint8_t a = s[2 * i], b = 2 * i + 1 < n ? s[2 * i + 1] : (uint8_t)0;
+      bad |= cuts(a) | cuts(b) | ((a | b) >> 7);
+      p[i] = (uint8_t)((bc_nt16(a) << 4) | (2 * i + 1 < n ? bc_nt16(b) : 0u));
+    }
+    p += nb;
+  }
+  __device__ __forceinline__ bool refused() const { return bad != 0; }
+};
+
+// one alignment record: the SAM line of bc_emit_sam_line as libbam reads it.  rec_bytes = bc_bam_record_len.
+template <class W>
+__device__ __forceinline__ void bc_emit_bam_record(const BcParams& P, unsigned long number, bool se, bool mate1,
+                                                   const BcLine (&ln)[4], const SamGeom& g, const BcTags& t, uint32_t rec_bytes,
+                                                   W& w) {
+  const uint32_t l_seq = g.seq_n;
+  const uint32_t none = bc_minus_one();
+  w.le32(rec_bytes - 4);                                  // block_size
+  w.le32(none);                                           // refID "*"
+  w.le32(none);                                           // pos "0" - 1
+  w.le32((4680u << 16) | (255u << 8) | (dec_digits(number) + 1));  // bin = reg2bin(-1, 0), mapq, l_read_name
+  w.le32(bc_sam_flag(se, mate1) << 16);                   // flag, no CIGAR
+  w.le32(l_seq);
+  w.le32(none);                                           // next_refID "*"
+  w.le32(none);                                           // next_pos "0" - 1
+  w.le32(g.shown);                                        // tlen: column 9
+  w.dec(number);
+  w.ch('\0');
+  const uint8_t* const seq = ln[1].p + g.cs.from;
+  const uint8_t* const qual = ln[3].p + g.cq.from;
+  // the characters that decide by themselves (one byte each; empty fields are the plan's finding, nothing is read of them)
+  const bool seq_star = l_seq == 1 && seq[0] == '*';  // libbam: no sequence at all - and then a QUAL that is not "*" aborts
+  const bool qual_star = g.qual_n == 1 && qual[0] == '*';
+  const bool glue = !mate1 && t.n[1];  // " CR:Z:<cell>" ends the value of the field in front of it
+  w.bases(seq, l_seq);
+  w.quals(qual, g.qual_n, l_seq, qual_star || g.qual_n != l_seq, l_seq + 3 + g.name_n + 1 + 3);
+  if (seq_star || (!qual_star && g.qual_n != l_seq)) w.bad |= 1;
+  BC_LIT(w, "onZ");
+  w.name(ln[0].p + 1, g.name_n);
+  w.ch('\0');
+  BC_LIT(w, "opZ");
+  w.skip(g.qual_n);
+  if (t.n[0]) {
+    w.ch('\0');
+    if (P.tenx) BC_LIT(w, "UBZ"); else BC_LIT(w, "RXZ");
+    w.bytes(t.s[0], t.n[0]);
+    w.ch('\0');
+    if (P.tenx) BC_LIT(w, "UYZ"); else BC_LIT(w, "QXZ");
+    w.bytes(t.q[0], t.qn[0]);
+  }
+  if (t.n[1]) {
+    if (glue) BC_LIT(w, " CR:Z:");
+    else {
+      w.ch('\0');
+      BC_LIT(w, "CRZ");
+    }
+    w.bytes(t.s[1], t.n[1]);
+    w.ch('\0');
+    BC_LIT(w, "CYZ");
+    w.bytes(t.q[1], t.qn[1]);
+  }
+  if (t.n[2]) {
+    w.ch('\0');
+    BC_LIT(w, "BCZ");
+    w.bytes(t.s[2], t.n[2]);
+    w.ch('\0');
+    BC_LIT(w, "QTZ");
+    w.bytes(t.q[2], t.qn[2]);
+  }
+  w.ch('\0');
+}
+
 struct EmitOut {
   const uint32_t* len;
   const unsigned long long* off;
@@ -1139,10 +1450,12 @@ struct EmitOut {
   uint8_t* out;
 };
 
-// One wavefront per tile.  SAM: one lane per line (two per iteration for paired reads); FASTQ: one
-// lane per record, one output after the other.
-template <bool SAM, int MASK>
-__global__ __launch_bounds__(kWave, 2) void k_bc_emit_tile(BcParams P, BcTile tc, uint64_t n_done,
+// One wavefront per tile.  SAM lines and BAM records: one lane per line / record (two per iteration for paired
+// reads); FASTQ: one lane per record, one output after the other.
+enum : int { kEmitFastq = 0, kEmitSam = FQG_OUT_SAM, kEmitBam = FQG_OUT_BAM };
+// (READ1 alone: the SAM kernel comes out at three wavefronts per SIMD unasked; its BAM twin is held to as many)
+template <int KIND, int MASK>
+__global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) void k_bc_emit_tile(BcParams P, BcTile tc, uint64_t n_done,
                                                         const uint8_t* __restrict__ status,
                                                         const uint8_t* __restrict__ tile_big, EmitOut o0, EmitOut o1,
                                                         EmitOut o2, BcCall* __restrict__ call) {
@@ -1150,6 +1463,7 @@ __global__ __launch_bounds__(kWave, 2) void k_bc_emit_tile(BcParams P, BcTile tc
   uint8_t* s_in = s_lds;
   uint8_t* s_out = s_lds + tc.in_cap;
   const int lane = (int)threadIdx.x;
+  constexpr bool SAM = KIND != kEmitFastq;  // (one lane per line: the layout of both)
   const bool se = !bc_has<MASK>(P, 2);
   const uint32_t lpi = SAM && !se ? 2u : 1u;  // lanes per iteration
   const uint32_t it_raw = lpi == 2 ? (uint32_t)lane >> 1 : (uint32_t)lane;
@@ -1241,7 +1555,10 @@ __global__ __launch_bounds__(kWave, 2) void k_bc_emit_tile(BcParams P, BcTile tc
                                     mate1, own);
       const unsigned long number = P.first_read_number + k + 1;
       // (single-end: the line's length is what the plan computed for the iteration; two mates share that number)
-      const uint32_t my_len = !keep ? 0u : (lpi == 1 ? cur.olen[0] : bc_sam_line_len(number, bc_sam_flag(se, mate1), g, t));
+      const uint32_t my_len = !keep ? 0u
+                              : (lpi == 1 ? cur.olen[0]
+                                          : (KIND == kEmitBam ? bc_bam_record_len(number, mate1, g, t)
+                                                              : bc_sam_line_len(number, bc_sam_flag(se, mate1), g, t)));
       const unsigned long long where = cur.off[0] + cur.sum[0];
       const unsigned long long tile_at = rfl64(where);
       const uint32_t before = __shfl_up(my_len, 1, 64);
@@ -1249,7 +1566,13 @@ __global__ __launch_bounds__(kWave, 2) void k_bc_emit_tile(BcParams P, BcTile tc
       const uint32_t total = wave_max32(start + my_len);
       uint8_t* dst = o0.out + tile_at;
       const uint32_t skew = (uint32_t)((uintptr_t)dst & 15u);
-      if (keep && !(P.ablate & 1)) {
+      if constexpr (KIND == kEmitBam) {
+        BamLaneWriter w;
+        w.p = s_out + skew + start;
+        if (keep) bc_emit_bam_record(P, number, se, mate1, own, g, t, my_len, w);
+        // a byte that refuses the record (what its geometry says against it: the plan)
+        bc_report_finding(call, keep, k, keep && w.refused() ? (kBcFindBam << 3) | (mate1 ? 1u : 2u) : 0u);
+      } else if (keep && !(P.ablate & 1)) {
         LaneWriter w{s_out + skew + start};
         bc_emit_sam_line(P, number, se, mate1, own, g, t, w);
       }
@@ -1285,6 +1608,7 @@ __global__ __launch_bounds__(kWave, 2) void k_bc_emit_tile(BcParams P, BcTile tc
 
 // iterations of the tiles that do not fit LDS (long reads): one wavefront per iteration, records read
 // from the images, text written straight to the output image
+template <bool BAM>
 __global__ __launch_bounds__(kBlock) void k_bc_emit_direct(BcParams P, BcTile tc, uint64_t n_done,
                                                            const uint8_t* __restrict__ status,
                                                            const uint8_t* __restrict__ tile_big, EmitOut o0, EmitOut o1,
@@ -1303,7 +1627,22 @@ __global__ __launch_bounds__(kBlock) void k_bc_emit_direct(BcParams P, BcTile tc
     if (status[k] != kBcKeep) continue;
     BcTags t;
     bc_tags_of_kept(P, L, &t);
-    if (P.out_sam) {
+    if constexpr (BAM) {
+      BamWriter w;
+      w.p = o0.out + o0.off[k] + o0.sum[k / kScan64Span];
+      w.lane = lane;
+      const unsigned long number = P.first_read_number + k + 1;
+      const SamGeom g1 = bc_sam_geom(bc_slices(P, 1), P.read_off[1], P.read_size[1], true, L[1]);
+      bc_emit_bam_record(P, number, se, true, L[1], g1, t, bc_bam_record_len(number, true, g1, t), w);
+      uint32_t finding = __ballot(w.refused()) ? (kBcFindBam << 3) | 1u : 0u;
+      if (!se) {
+        const SamGeom g2 = bc_sam_geom(bc_slices(P, 2), P.read_off[2], P.read_size[2], false, L[2]);
+        w.bad = 0;
+        bc_emit_bam_record(P, number, se, false, L[2], g2, t, bc_bam_record_len(number, false, g2, t), w);
+        if (!finding && __ballot(w.refused())) finding = (kBcFindBam << 3) | 2u;
+      }
+      if (finding && lane == 0) atomicMin(&call->first_finding, (unsigned long long)((k << 8) | finding));
+    } else if (P.out_sam) {
       Writer w{o0.out + o0.off[k] + o0.sum[k / kScan64Span], lane};
       bc_emit_sam_line(P, P.first_read_number + k + 1, se, true, L[1],
                        bc_sam_geom(bc_slices(P, 1), P.read_off[1], P.read_size[1], true, L[1]), t, w);

@@ -1,5 +1,6 @@
-// fqg_host.cpp - host-only parts of the C-ABI: the once-per-file probes.
+// fqg_host.cpp - host-only parts of the C-ABI: the once-per-file probes, the BAM header of fastq_pre_barcodes.
 #include <regex.h>
+#include <string.h>
 
 #include <string>
 
@@ -60,6 +61,22 @@ int fqg_probe_first_record(const void* host_image, uint64_t nbytes, int is_pe, f
   out->readname_format = fqg_probe_readname_format(hdr.c_str() + 1);
   out->space = fqg_probe_space(seq.c_str());
   return 0;
+}
+
+// What bam_header_write makes of the two lines fastq_pre_barcodes prints in front of its SAM text
+// (src/fastq_pre_barcodes.c:579-584; sam_header_read keeps them verbatim, there is no @SQ line)
+uint64_t fqg_bam_header(int argc, const char* const* argv, void* out, uint64_t cap) {
+  std::string text = "@HD\tVN:1.0 SO:unknown\n@PG\tID:1 PN:fastq_pre_barcodes CL:";
+  if (argc > 0 && argv) text += argv[0];
+  for (int i = 1; i < argc - 1; ++i) text += std::string(" ") + argv[i];  // (the reference drops the last word)
+  text += "\n";
+  std::string h("BAM\1", 4);
+  const uint32_t l_text = (uint32_t)text.size();
+  for (int k = 0; k < 4; ++k) h.push_back((char)(l_text >> (8 * k)));
+  h += text;
+  h.append(4, '\0');  // n_ref
+  if (out && cap >= h.size()) memcpy(out, h.data(), h.size());
+  return h.size();
 }
 
 }  // extern "C"

@@ -5,6 +5,9 @@
 //          bookkeeping across pieces, gzip / stdout writing of what the GPU produced
 //   GPU    framing of every input, read-name agreement, barcode extraction with the quality
 //          filter, header tagging, slicing, and the assembly of the output text (FASTQ or SAM)
+// --bam (not an option of the reference): what `fastq_pre_barcodes --sam ... | samtools view -b -` writes in the
+// reference's sh/fastq2bam, without the pipe - the GPU makes the alignment records samtools 0.1.19 makes of the SAM
+// lines, the program writes the BGZF file to stdout.
 // There is no CPU path for the per-read work.
 #include <getopt.h>
 #include <unistd.h>
@@ -85,6 +88,7 @@ void print_usage() {  // src/fastq_pre_barcodes.c:311-346
       "  --read2_offset integer   :\n"
       "  --read2_size integer     :\n"
       "  --10x     : use 10X UMI tags (UB and UY) instead of the default tags defined in the SAM specification\n";
+  // (--bam is not listed: the usage text is the reference's, byte for byte; README.md and DESIGN.md 4.5 describe it)
   fprintf(stderr, "usage: fastq_pre_barcodes --read1 fastq_file --outfile1 out_file [optional parameters]\n");
   fprintf(stderr, "%s\n", msg);
 }
@@ -155,6 +159,27 @@ struct WrongHeader {
   std::string text;
 };
 
+// --bam: the BGZF file on stdout.  Host mode: the records come back as they are and the host's threads compress them
+// (zlib's default level, as bam_add_tags does).  Device mode (FQGPU_GZIP_GPU=1, loops on one context): every batch's
+// records are compressed where they lie (fqg_text_bgzf_deflate) with the carry chain of the gzip files - the header is
+// the first carry -, and what is left when the loop ends becomes the last block.  Either way the blocks are cut at
+// multiples of 65280 bytes of the stream and the end-of-file block closes the file.
+struct BamOut {
+  bool on = false, device = false;
+  fqhost::BgzfStream host;
+  std::string* carry = nullptr;  // device mode: the loop's carry of output 0
+  bool close(fqg_ctx* c) {
+    if (!device) return host.close();
+    fqg_deflate_result dr;
+    if (fqg_bgzf_deflate(c, carry->data(), carry->size(), nullptr, 0, FQG_MEM_HOST, 1, &dr)) return false;
+    std::vector<char> last(dr.gz_bytes);
+    if (fqg_deflate_output(c, last.data(), last.size())) return false;
+    return fwrite(last.data(), 1, last.size(), stdout) == last.size();
+  }
+};
+BamOut g_bam;
+std::string g_bam_header;  // device mode: the first carry of output 0
+
 struct Batches {
   const char* const* file = nullptr;
   const fqg_barcode_params* P = nullptr;
@@ -190,6 +215,11 @@ struct Batches {
       const WrongHeader h = wrong_header();
       fail_wrong_header(file[r.file], h.line, h.text);
     }
+    if (r.code == FQG_E_BAM_RECORD) {  // (not a reference outcome: samtools view -b would abort on this line, or worse)
+      FQ_PRINT_ERROR("read #%ld: the SAM line of read%d cannot be written as a BAM record (empty or mismatched sequence / quality, "
+                     "an empty tag value, or a tab, a line break or a byte >= 0x80 where libbam cannot take one)", (long)(processed + 1), r.file);
+      fqhost::leave(2);
+    }
     FQ_PRINT_ERROR("Readnames do not match across files (read #%ld)", (long)(processed + 1));
     fqhost::leave(kExitFormat);
   }
@@ -215,6 +245,10 @@ struct Batches {
           FQ_PRINT_ERROR("unable to close file descriptor");
           fqhost::leave(kExitSys);
         }
+    if (g_bam.on && !g_bam.close(g_ctx)) {
+      FQ_PRINT_ERROR("unable to write the BAM file to stdout");
+      fqhost::leave(kExitSys);
+    }
     fflush(stdout);
     pb_json_metrics((long)processed, (long)discarded, devices);
     fqhost::leave(0);
@@ -241,8 +275,10 @@ int fetch_begin(fqg_ctx* c, OutPool& pool, int which, size_t text_bytes, bool de
   o->size = text_bytes;
   if (o->members) {
     fqg_deflate_result dr;
-    *what = "fqg_text_deflate";
-    if (const int rc = fqg_text_deflate(c, FQG_TEXT_RECORDS, which, carry.data(), carry.size(), 0, &dr)) return rc;
+    *what = which == 0 ? "fqg_text_bgzf_deflate" : "fqg_text_deflate";
+    if (const int rc = which == 0 ? fqg_text_bgzf_deflate(c, FQG_TEXT_RECORDS, 0, carry.data(), carry.size(), 0, &dr)  // (--bam)
+                                  : fqg_text_deflate(c, FQG_TEXT_RECORDS, which, carry.data(), carry.size(), 0, &dr))
+      return rc;
     o->gz_bytes = dr.gz_bytes;
     o->size = dr.gz_bytes + dr.tail_bytes;
   }
@@ -261,8 +297,10 @@ int fetch_wait(fqg_ctx* c, const OutText& o, std::string* carry) {
   if (!rc && o.members) carry->assign(o.buf + o.gz_bytes, o.size - o.gz_bytes);
   return rc;
 }
-// the write step (0: the SAM text to stdout; device mode: the members, and the tail for close())
+// the write step (0: the SAM text to stdout, or --bam: the records through the host compressor / the blocks the device
+// made of them; device mode: the members, and the tail for close())
 bool write_out(GzipMembers* gz, int which, const OutText& o) {
+  if (which == 0 && g_bam.on) return o.members ? fwrite(o.buf, 1, o.gz_bytes, stdout) == o.gz_bytes : g_bam.host.write(o.buf, o.size);
   if (which == 0) return fwrite(o.buf, 1, o.size, stdout) == o.size;
   return o.members ? gz[which].write_members(o.buf, o.gz_bytes, o.buf + o.gz_bytes, o.size - o.gz_bytes) : gz[which].write(o.buf, o.size);
 }
@@ -410,7 +448,7 @@ struct BlockLoop {
   // The carry chain of the device compressor, one per output file: the context's thread's alone.  With ONE context every
   // unit passes through that thread in unit order (fq_ordered.h), so the tail of unit k is the carry of unit k + 1; the
   // thread that writes never calls into the context while units are under way.
-  std::string gz_carry[3];
+  std::string gz_carry[3] = {g_bam_header, std::string(), std::string()};
   const bool timing = getenv("FQGPU_TIMING") != nullptr;
   struct UnitTimes {  // FQGPU_TIMING: one context's seconds
     double frame = 0, transform = 0, out = 0;
@@ -421,6 +459,7 @@ struct BlockLoop {
   BlockLoop(Batches& a, const std::vector<int>& devs)
       : A(a), ctx(fqhost::open_more_contexts(g_ctx, devs)), window(devs.size() + 1),
         out_pool(FQ_PINNED_ALLOC(g_ctx), (size_t)window * outputs_per_batch(*a.P)), T(devs.size()) {
+    g_bam.carry = &gz_carry[0];
     double record_bytes = 64;
     for (int x = READ1; x <= INDEX3; ++x)
       if (A.file[x]) {
@@ -487,7 +526,7 @@ struct BlockLoop {
       if (u.r.out_bytes[which]) {
         const char* what;
         // (a device was handed over to the output files for one context only: main)
-        if (const int rc = fetch_begin(c, out_pool, which, u.r.out_bytes[which], which > 0 && A.outgz[which].on_device(), gz_carry[which],
+        if (const int rc = fetch_begin(c, out_pool, which, u.r.out_bytes[which], which > 0 ? A.outgz[which].on_device() : g_bam.device, gz_carry[which],
                                        false, &u.out[which], &what))
           lib_fail(c, u, what, rc);
         else if (const int rc2 = fetch_wait(c, u.out[which], &gz_carry[which])) lib_fail(c, u, "fqg_*_output_wait", rc2);
@@ -593,6 +632,7 @@ int main(int argc, char** argv) {
                                          {"paired_end", no_argument, &paired, 1},
                                          {"single_end", no_argument, &paired, 0},
                                          {"sam", no_argument, &out_sam, 1},
+                                         {"bam", no_argument, &out_sam, FQG_OUT_BAM},
                                          {"fastq", no_argument, &out_sam, 0},
                                          {"help", no_argument, &help, 1},
                                          {"umi_read", required_argument, 0, 'a'},
@@ -747,6 +787,21 @@ int main(int argc, char** argv) {
         // no device is handed over there and the host compressor runs
         if (devices.size() <= 1) outgz[x].device(FQ_GZIP_DEVICE(g_ctx));
       }
+  } else if (out_sam == FQG_OUT_BAM) {
+    // the header libbam makes of the two lines below (fqg_bam_header: one place for the @PG rule).  Device mode: several
+    // contexts have no carry chain (above) and take the host compressor - and so must a run that such a run starts over
+    std::string head(fqg_bam_header(argc, argv, nullptr, 0), '\0');
+    fqg_bam_header(argc, argv, &head[0], head.size());
+    const char* gz_gpu = getenv("FQGPU_GZIP_GPU");
+    g_bam.on = true;
+    g_bam.device = gz_gpu && atoi(gz_gpu) != 0 && devices.size() <= 1;
+    if (!g_bam.device) setenv("FQGPU_GZIP_GPU", "0", 1);
+    g_bam.host.open(stdout, Z_DEFAULT_COMPRESSION);
+    if (g_bam.device) g_bam_header = head;
+    else if (!g_bam.host.write(head.data(), head.size())) {
+      FQ_PRINT_ERROR("unable to write the BAM file to stdout");
+      fqhost::leave(kExitSys);
+    }
   } else {
     printf("@HD\tVN:1.0 SO:unknown\n");
     printf("@PG\tID:1 PN:fastq_pre_barcodes CL:%s", argv[0]);
@@ -781,7 +836,8 @@ int main(int argc, char** argv) {
     if (file[x]) src[x].use = (has_interleaved && x == P.interleaved[1]) ? 1 : 0;
 
   std::vector<OutJob> in_flight;  // output of the last transform, on its way to the host
-  std::string gz_carry[3];        // device mode: the text the last batch left over, per output file (the carry chain)
+  std::string gz_carry[3] = {g_bam_header, std::string(), std::string()};  // device mode: the text the last batch left over, per output (the carry chain)
+  g_bam.carry = &gz_carry[0];
   auto land_output = [&] {
     for (const OutJob& job : in_flight) {
       const double t_d = now();
@@ -857,7 +913,7 @@ int main(int argc, char** argv) {
         OutJob job;
         job.which = which;
         const char* what;
-        if (const int rc = fetch_begin(g_ctx, out_pool, which, r.out_bytes[which], which > 0 && outgz[which].on_device(), gz_carry[which], true,
+        if (const int rc = fetch_begin(g_ctx, out_pool, which, r.out_bytes[which], which > 0 ? outgz[which].on_device() : g_bam.device, gz_carry[which], true,
                                        &job.t, &what))
           die_lib(what, rc);
         in_flight.push_back(job);

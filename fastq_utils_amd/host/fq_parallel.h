@@ -450,4 +450,44 @@ inline bool bgzf_deflate_parallel(const std::vector<std::pair<const uint8_t*, si
   return true;
 }
 
+// A BGZF file written piece by piece (fastq_pre_barcodes --bam: the header, then every batch's records): the blocks
+// are cut at multiples of 0xff00 bytes counted from the start of the STREAM, whatever the pieces are - what does not
+// fill a block waits for the next piece -, so the file's bytes are a function of the stream alone (a run that starts
+// over, fq_respawn.h, writes the same file again).  close(): the rest as a last block, then the end-of-file block.
+class BgzfStream {
+ public:
+  void open(FILE* f, int level) {
+    f_ = f;
+    level_ = level;
+  }
+  bool is_open() const { return f_ != nullptr; }
+  bool write(const void* data, size_t n) { return put(static_cast<const uint8_t*>(data), n, false); }
+  bool close() {
+    const bool ok = put(nullptr, 0, true);
+    f_ = nullptr;
+    return ok;
+  }
+
+ private:
+  bool put(const uint8_t* data, size_t n, bool last) {
+    constexpr size_t kBlock = 0xff00;
+    if (!f_) return false;
+    const size_t all = pend_.size() + n;
+    const size_t take = last ? all : all / kBlock * kBlock;  // bytes that become blocks now
+    if (take == 0 && !last) {
+      pend_.insert(pend_.end(), data, data + n);
+      return true;
+    }
+    const size_t from_data = take - pend_.size();  // (take > 0: at least one block, which holds all of pend_ - fewer than kBlock bytes)
+    std::vector<uint8_t> out;
+    if (!bgzf_deflate_parallel({{pend_.data(), pend_.size()}, {data, from_data}}, level_, out)) return false;
+    pend_.assign(data + from_data, data + n);
+    const size_t bytes = last ? out.size() : out.size() - 28;  // (the end-of-file block belongs to close())
+    return fwrite(out.data(), 1, bytes, f_) == bytes;
+  }
+  FILE* f_ = nullptr;
+  int level_ = Z_DEFAULT_COMPRESSION;
+  std::vector<uint8_t> pend_;
+};
+
 }  // namespace fqhost

@@ -348,7 +348,8 @@ typedef struct {
   int32_t interleaved[2];      /* {0,0}: none; else the two file references of --interleaved */
   int32_t umi_read, cell_read, sample_read; /* 1..5, -1 = not set */
   int32_t phred_encoding, min_qual;
-  int32_t out_sam, tenx;       /* --sam, --10x */
+  int32_t out_sam, tenx;       /* out_sam: 0 FASTQ, 1 SAM lines (--sam), FQG_OUT_BAM: the same lines as the alignment
+                                  records libbam makes of them (--bam; below); tenx: --10x */
   int32_t emit[3];             /* FASTQ mode: outfile1 / outfile2 wanted */
   int64_t umi_offset, umi_size, cell_offset, cell_size, sample_offset, sample_size; /* offset -1 = not set */
   int64_t read_offset[3], read_size[3];
@@ -360,16 +361,25 @@ typedef struct {
                              file pointers are out of step (src/fastq_pre_barcodes.c:653 vs :722) */
   uint64_t n_discarded;   /* among the n_done */
   uint64_t n_short;       /* of those, "Warning: Read too short - barcode not found" cases */
-  uint64_t out_bytes[3];  /* [0] SAM text, [1] / [2] FASTQ text of outfile1 / outfile2 */
+  uint64_t out_bytes[3];  /* [0] SAM text or BAM records, [1] / [2] FASTQ text of outfile1 / outfile2 */
   uint64_t iteration;     /* finding: iteration (== n_done) */
-  int32_t code;           /* FQG_OK, FQG_E_NAME_MISMATCH, FQG_E_WRONG_HEADER */
-  int32_t file;           /* finding: which input (1..5) */
+  int32_t code;           /* FQG_OK, FQG_E_NAME_MISMATCH, FQG_E_WRONG_HEADER, FQG_E_BAM_RECORD */
+  int32_t file;           /* finding: which input (1..5); FQG_E_BAM_RECORD: the mate (1, 2) whose line is refused */
 } fqg_barcode_result;
 
 int fqg_barcodes_transform(fqg_ctx *ctx, const fqg_frame *const frames[6], const fqg_file_state states[6],
                            const uint64_t first_record[6], const fqg_barcode_params *params,
                            uint64_t n_iterations, uint64_t first_read_number, fqg_barcode_result *out);
-/* copy output `which` (0 SAM, 1, 2) of the last transform to host memory */
+/* out_sam == FQG_OUT_BAM: output 0 is, for every SAM line of out_sam == 1, the alignment record (block_size first, as
+ * in an inflated BAM file) that samtools 0.1.19's sam_read1 + bam_write1 make of it.  A line on which libbam aborts or
+ * reads memory it does not own ends the batch with FQG_E_BAM_RECORD (fqg_codes.h).  fqg_bam_header makes the header
+ * that goes in front of the first record: "BAM\1", l_text, the two lines fastq_pre_barcodes prints in SAM mode (@HD,
+ * and @PG with argv[0] .. argv[argc-2] joined by blanks: the reference leaves the last argument out), n_ref = 0.
+ * Returns the header's length; writes it when cap is large enough. */
+#define FQG_OUT_SAM 1
+#define FQG_OUT_BAM 2
+uint64_t fqg_bam_header(int argc, const char *const *argv, void *out, uint64_t cap);
+/* copy output `which` (0 SAM / BAM, 1, 2) of the last transform to host memory */
 int fqg_barcodes_output(fqg_ctx *ctx, int which, void *host_dst, uint64_t nbytes);
 /* ... the same copy on a stream of its own: it returns at once and runs beside whatever the context does next in the
  * OTHER direction of the link (fqg_validate of the next piece of input: host to device).  host_dst must be pinned

@@ -95,7 +95,13 @@ enum fqg_code {
   FQG_E_INFLATE_CODE = 35,
   FQG_E_INFLATE_DISTANCE = 36,
   FQG_E_INFLATE_SIZE = 37,
-  FQG_E_INFLATE_INPUT = 38
+  FQG_E_INFLATE_INPUT = 38,
+  /* Not a reference outcome.  fastq_pre_barcodes --bam (fqg_barcode_params.out_sam == FQG_OUT_BAM) writes the record
+   * that samtools 0.1.19's sam_read1 (bam_import.c:237-467) makes of the SAM line; this line is one on which sam_read1
+   * aborts or reads memory it does not own: SEQ and QUAL of different lengths (QUAL not "*"), an empty SEQ, QUAL or
+   * aux value, a base byte >= 0x80 (a negative index into bam_nt16_table), a byte 9..13 inside a string (libbam cuts
+   * fields at every isspace() byte but the blank), a SEQ of exactly "*".  Refused; file = the mate (1, 2). */
+  FQG_E_BAM_RECORD = 39
 };
 
 /* read-name formats, src/fastq.h:25-28 (INTEGERNAME and NOP share the value 2) */

@@ -854,6 +854,94 @@ def gen_split_interleaved():
     print("fastq_split_interleaved invocations:", len(out), "by exit status:", by)
 
 
+# ---- fastq_pre_barcodes --bam: what the vendored libbam makes of the reference's SAM text (sh/fastq2bam's
+# `fastq_pre_barcodes --sam ... | samtools view -b -`) -------------------------------------------------------------------
+SAM2BAM_DRIVER = r"""
+/* samtools view -bSu - : SAM text on stdin through sam_header_read / sam_read1, BAM (BGZF, level 0) on stdout through
+   bam_header_write / bam_write1 */
+#include "sam.h"
+int main(void) {
+  samfile_t *in = samopen("-", "r", 0);
+  if (!in) return 2;
+  samfile_t *out = samopen("-", "wbu", in->header);
+  if (!out) return 2;
+  bam1_t *b = bam_init1();
+  while (samread(in, b) >= 0) samwrite(out, b);
+  bam_destroy1(b);
+  samclose(in);
+  samclose(out);
+  return 0;
+}
+"""
+
+
+def build_ref_sam2bam(tmp):
+    """the vendored libbam and a driver of its SAM reader and BAM writer, compiled into `tmp` (outside the repository)"""
+    subprocess.run(["tar", "-xjf", os.path.join(REF, "deps", "samtools-0.1.19.tar.bz2"), "-C", tmp], check=True)
+    sam = os.path.join(tmp, "samtools-0.1.19")
+    subprocess.run(["gcc", "-O2", "-w", "-c", "-D_FILE_OFFSET_BITS=64", "-D_LARGEFILE64_SOURCE", "-D_USE_KNETFILE", "-I."] + LIBBAM_SRC,
+                   cwd=sam, check=True)
+    drv = os.path.join(tmp, "sam2bam.c")
+    with open(drv, "w") as f:
+        f.write(SAM2BAM_DRIVER)
+    exe = os.path.join(tmp, "sam2bam")
+    subprocess.run(["gcc", "-O2", "-w", "-I" + sam, "-o", exe, drv] + glob.glob(os.path.join(sam, "*.o")) + ["-lz", "-lm", "-lpthread"], check=True)
+    return exe
+
+
+def gen_pre_barcodes_bam():
+    import hashlib
+    import tempfile
+
+    sys.path.insert(0, REPO)
+    from tests import pb_bam_gen
+    from tests.sam2bam_oracle import bgzf_inflate
+
+    def through_libbam(exe, sam_text):
+        p = subprocess.run([exe], input=sam_text, capture_output=True, timeout=120)
+        entry = {"libbam_exit": p.returncode, "libbam_stderr": p.stderr.decode("latin-1")}
+        if p.returncode == 0:
+            stream, _ = bgzf_inflate(p.stdout)
+            l_text = int.from_bytes(stream[4:8], "little")
+            recs = stream[12 + l_text:]   # (n_ref = 0: the first record follows)
+            n, at = 0, 0
+            while at < len(recs):
+                at += 4 + int.from_bytes(recs[at:at + 4], "little")
+                n += 1
+            entry.update({"header_text": stream[8:8 + l_text].decode("latin-1"), "records": n, "bytes": len(recs),
+                          "sha256": hashlib.sha256(recs).hexdigest()})
+            if len(recs) <= 2048:
+                entry["stream_hex"] = recs.hex()
+        return entry
+
+    golden = json.load(open(os.path.join(GOLD, "pre_barcodes.json")))
+    out = []
+    with tempfile.TemporaryDirectory() as build:
+        exe = build_ref_sam2bam(build)
+        for i, case in enumerate(golden):
+            if "--sam" not in case["args"] or case["exit"] != 0:
+                continue
+            entry = {"golden": i, "args": case["args"]}
+            entry.update(through_libbam(exe, case["stdout"].encode("latin-1")))
+            out.append(entry)
+        for name, (files, args, comment) in sorted(pb_bam_gen.cases().items()):
+            with tempfile.TemporaryDirectory() as tmp:
+                for fn, img in files.items():
+                    with open(os.path.join(tmp, fn), "wb") as f:
+                        f.write(img)
+                p = subprocess.run(["fastq_pre_barcodes"] + args, executable=PB_BIN, cwd=tmp, capture_output=True, timeout=120)
+                entry = {"made_up": name, "comment": comment, "args": args, "exit": p.returncode, "stderr": p.stderr.decode("latin-1"),
+                         "sam": p.stdout.decode("latin-1")}
+                entry.update(through_libbam(exe, p.stdout))
+                out.append(entry)
+    with open(os.path.join(GOLD, "pre_barcodes_bam.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    by = {}
+    for o in out:
+        by[o["libbam_exit"]] = by.get(o["libbam_exit"], 0) + 1
+    print("fastq_pre_barcodes --sam texts through libbam:", len(out), "by libbam's exit status:", by)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("all", "fastq_info"):
@@ -872,3 +960,5 @@ if __name__ == "__main__":
         gen_bam2fastq()
     if which in ("all", "split_interleaved"):
         gen_split_interleaved()
+    if which in ("all", "pre_barcodes_bam"):   # (reads tests/golden/pre_barcodes.json: behind pre_barcodes)
+        gen_pre_barcodes_bam()
