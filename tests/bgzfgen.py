@@ -4,6 +4,7 @@ wrong frames - and zlib's verdict on every block, which is what the inflater und
 
 A payload comes from zlib (`deflate`: level, strategy, memLevel, flushes in mid-text) or from the two bit writers
 (`fixed_block`, `dynamic_block`: tokens under codes the caller chooses)."""
+import functools
 import random
 import struct
 import zlib
@@ -330,6 +331,8 @@ def well_formed():
         F["stray-%d" % stray] = text_block(text[:500]) + EOF + bytes([0x1f] * stray)
     F["no-eof-block"] = text_block(text[:500])
     F["nothing"] = b""
+    for made in (match_geometry, queue_rounds, sizes, payload_alignment, stored_at_the_window_edge):
+        F.update(made())
     return F
 
 
@@ -345,6 +348,239 @@ def many_blocks(n):
     """n blocks of about 64 bytes of text each"""
     text = contents()["fastq"]
     return b"".join(text_block(text[(k * 61) % 50000:][:64], level=1 if k & 1 else 6) for k in range(n)) + EOF
+
+
+# ---- the work around the walk -----------------------------------------------------------------
+# What the wavefront does around the one walking lane (staging, the copies of a round's queue, the CRC stripes, the
+# flush, the two atomicMin) decides nothing by itself, so a file made by zlib meets its edges only by chance.  These
+# files are built to meet them.
+def text_of(tokens, text=b""):
+    """what tokens (literals and (length, distance) matches) write behind text"""
+    out = bytearray(text)
+    for t in tokens:
+        if isinstance(t, int):
+            out.append(t)
+        else:
+            for _ in range(t[0]):
+                out.append(out[-t[1]])
+    return bytes(out[len(text):])
+
+
+GEOMETRY_DISTANCES = list(range(1, 131)) + [191, 192, 193, 255, 256, 257, 258, 259, 511, 512, 513]
+GEOMETRY_LENGTHS = [3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 66, 127, 128, 129, 191, 192, 193, 255, 256, 257, 258]
+
+
+def match_geometry():
+    """one fixed block per distance d: d + (0 .. 15) literals of noise, then every length around the wavefront's 64 lanes as
+    the match (length, d) with a literal of noise behind it.  Noise, so that a byte read too early, too late or from the
+    wrong place of the period is another byte."""
+    r = random.Random(1)
+    blocks = []
+    for d in GEOMETRY_DISTANCES:
+        toks = list(r.randbytes(d + r.randrange(16)))
+        for length in GEOMETRY_LENGTHS:
+            toks += [(length, d), r.randrange(256)]
+        blocks.append(text_block(text_of(toks), fixed_block(toks).bytes()))
+    return {"match-geometry": b"".join(blocks) + EOF}
+
+
+QUEUE_ENTRIES = (63, 64, 65, 127, 128, 129, 200)
+
+
+def chained_matches(r, n, text, literal_behind_the_last):
+    """n matches, one to three literals of noise between two of them; every match has the length of the one before it as
+    its distance, so it reads what that one wrote - the first reads the last bytes of text"""
+    toks, d = [], min(len(text), r.randrange(3, 40))
+    for k in range(n):
+        length = r.choice([3, 4, 17, 63, 64, 65, 128, 258, r.randrange(3, 259), r.randrange(3, 259)])
+        toks.append((length, d))
+        d = length
+        if k + 1 < n or literal_behind_the_last:
+            toks += list(r.randbytes(r.randrange(1, 4)))
+    return toks
+
+
+def queue_rounds():
+    """blocks of exactly 63 .. 200 queue entries (a match or a non-empty stored run is one, a literal is none; the queue
+    holds 64).  In the blocks of 64 and 128 the last entry is the last token and ends at ISIZE.  The last block's entries
+    are stored runs - more than the queue holds in a row - and matches that reach back into them."""
+    r = random.Random(2)
+    blocks = []
+    for n in QUEUE_ENTRIES:
+        start = r.randbytes(r.randrange(3, 40))
+        toks = list(start) + chained_matches(r, n, start, n % 64 != 0)
+        assert sum(isinstance(t, tuple) for t in toks) == n and isinstance(toks[-1], tuple) == (n % 64 == 0)
+        blocks.append(text_block(text_of(toks), fixed_block(toks).bytes()))
+    b, text = Bits(), b""
+    for k in range(70):
+        run = r.randbytes(r.randrange(1, 40))
+        b, text = stored_block(run, False, b), text + run
+    for n_stored, n_matches, final in ((0, 30, False), (3, 0, False), (0, 40, True)):
+        for k in range(n_stored):
+            run = r.randbytes(r.randrange(1, 300))
+            b, text = stored_block(run, False, b), text + run
+        if n_matches:
+            toks = [(r.randrange(3, 259), r.randrange(1, len(text) + 1)), r.randrange(256)] + chained_matches(r, n_matches - 1, text, True)
+            b, text = fixed_block(toks, final, b), text + text_of(toks, text)
+    blocks.append(text_block(text, b.bytes()))
+    return {"queue-rounds": b"".join(blocks) + EOF}
+
+
+SIZES = list(range(1, 50)) + [254, 255, 256, 257, 509, 510, 511, 4095, 4096, 4097, 65279, 65280, 65281, 65535, 65536]
+SIZES_WRONG_CRC = (1, 2, 3, 4, 255, 256, 65280, 65281, 65535, 65536)
+
+
+@functools.lru_cache(None)
+def sizes_blocks():
+    """one block per ISIZE of SIZES: the CRC's path for less than four bytes, one stripe and one more, all 256 stripes, a
+    head of 1, 255 and 256 bytes in front of them; fastq text and noise in turn under levels 0 to 9, the two largest a
+    period of 997 bytes of noise (65 536 bytes of noise are no BGZF block)"""
+    r = random.Random(31)
+    noise, fastq = r.randbytes(70000), contents()["fastq"]
+    period = (r.randbytes(997) * 66)[:65536]
+    blocks = []
+    for k, n in enumerate(SIZES):
+        if n >= 65535:
+            data, level = period[65536 - n:], (1, 9)[k & 1]
+        elif n >= 65279:
+            data, level = noise[k:k + n], (0, 1, 6)[k % 3]
+        else:
+            data, level = (fastq, noise)[k & 1][5 * k:5 * k + n], (0, 1, 6, 9)[(k // 2) % 4]
+        assert len(data) == n
+        blocks.append(text_block(data, level=level))
+    assert {sum(SIZES[:k]) % 16 for k in range(len(SIZES))} == set(range(16))   # where a block's text starts in the output
+    return blocks
+
+
+def sizes():
+    return {"sizes": b"".join(sizes_blocks()) + EOF}
+
+
+@functools.lru_cache(None)
+def sizes_wrong_crc():
+    """name -> (file, block): the file above with one bit of one block's stored CRC-32 changed"""
+    blocks, out = sizes_blocks(), {}
+    for n in SIZES_WRONG_CRC:
+        at, bit = SIZES.index(n), (7 * n) % 32
+        b = bytearray(blocks[at])
+        b[len(b) - 8 + (bit >> 3)] ^= 1 << (bit & 7)
+        out["sizes-wrong-crc-%d" % n] = (b"".join(blocks[:at]) + bytes(b) + b"".join(blocks[at + 1:]) + EOF, at)
+    return out
+
+
+def skewed_text(r, n):
+    """bytes a Huffman code shortens by a few per cent: Z_HUFFMAN_ONLY makes ONE dynamic block of them, every bit of
+    which is read through the staging windows (noise, which zlib stores, would be copied from the file itself)"""
+    return bytes(min(255, int(r.expovariate(0.012))) for _ in range(n))
+
+
+def huffman_payload(data):
+    payload = deflate(data, strategy=Z_HUFFMAN_ONLY)
+    assert (payload[0] >> 1) & 3 == 2 and len(payload) > 3 * 4096, len(payload)   # dynamic; more than three windows
+    return payload
+
+
+def payload_alignment():
+    """16 blocks; block k has a subfield of k bytes in front of BC, and its payload - of a text of 14 000 + k bytes, more
+    than three staging windows long - has the length that puts the NEXT payload's start three residues mod 16 further,
+    so the starts take all 16 (the file's first byte lies at a multiple of 16 on the device) and the ends eight"""
+    r = random.Random(41)
+    out, starts, ends = b"", set(), set()
+    for k in range(16):
+        extra = b"XY" + struct.pack("<H", k) + r.randbytes(k)
+        start = len(out) + 12 + len(extra) + 6
+        for attempt in range(2000):
+            data = skewed_text(r, 14000 + k)
+            payload = huffman_payload(data)
+            if k == 15 or (len(payload) + 8 + 12 + len(extra) + 1 + 6) % 16 == 3:   # (the next subfield is a byte longer)
+                break
+        else:
+            raise AssertionError("no payload of the length block %d needs" % k)
+        starts.add(start % 16)
+        ends.add((start + len(payload)) % 16)
+        out += text_block(data, payload, extra)
+        assert walk(out)[0][k][0] == payload and out[start:start + len(payload)] == payload
+    assert starts == set(range(16)) and len(ends) >= 8, (starts, ends)
+    return {"payload-alignment": out + EOF}
+
+
+def stored_at_the_window_edge():
+    """for k in -6 .. 6 a payload that starts at a multiple of 16 and whose first stored block ends at byte 4096 + k, the
+    end of the first staged window: the header of the fixed block behind it, and that of the stored block behind that
+    one, lie on every offset around a window's edge, and twice the walk jumps over bytes that were never staged"""
+    r = random.Random(43)
+    out = b""
+    for k in range(-6, 7):
+        extra = b"XY" + struct.pack("<H", -(len(out) + 22) % 16) + bytes(-(len(out) + 22) % 16)
+        assert (len(out) + 12 + len(extra) + 6) % 16 == 0
+        text = r.randbytes(4096 + k - 5)
+        b = stored_block(text, False)
+        assert len(b.bytes()) == 4096 + k
+        toks = ([r.randrange(256), (40, len(text) - 7), r.randrange(256), (258, 300), (5, 1), (200, len(text) + 40 + 2)] +
+                list(r.randbytes((k + 6) % 5)) + [(70, 64), (3, 4096 + k - 9)])
+        b, text = fixed_block(toks, False, b), text + text_of(toks, text)
+        last = r.randbytes(5000)
+        b, text = stored_block(last, True, b), text + last
+        out += text_block(text, b.bytes(), extra)
+    return {"stored-at-the-window-edge": out + EOF}
+
+
+def cut_payloads():
+    """name -> (whole text, payload): the dynamic block of payload_alignment, and 14 000 bytes of noise, which zlib stores"""
+    r = random.Random(47)
+    data, noise = skewed_text(r, 14000), r.randbytes(14000)
+    stored = deflate(noise, strategy=Z_HUFFMAN_ONLY)
+    assert len(stored) == 14005 and stored[0] == 1
+    return {"cut-at-the-window-edge": (data, huffman_payload(data)), "cut-stored-at-the-window-edge": (noise, stored)}
+
+
+@functools.lru_cache(None)
+def cut_at_the_window_edge():
+    """payloads cut short at their end and around the ends of the staged windows, behind a good block; ISIZE and CRC are
+    those of the whole text.  What follows a cut payload is its CRC-32, which is not zero: a walk that read on there
+    instead of taking zeros would not stop where zlib does.  zlib refuses every one, or this sweep has lost its purpose."""
+    D = {}
+    good = text_block(contents()["fastq"][:100])
+    for name, (data, payload) in cut_payloads().items():
+        n = len(payload)
+        cuts = sorted({n - k for k in (1, 2, 3, 4, 5, 8, 9)} | {4096 + k for k in range(-3, 4)} | {8192 + k for k in range(-3, 4)} |
+                      {3072 + k for k in (-1, 0, 1)})
+        assert len(cuts) == 24 and zlib.crc32(data) & 0xFF and zlib.crc32(data) >> 24
+        for c in cuts:
+            D["%s-%d" % (name, c)] = good + block(payload[:c], len(data), zlib.crc32(data)) + EOF
+            assert verdict(D["%s-%d" % (name, c)])["bad_block"] == 1, (name, c)
+    return D
+
+
+def several_findings():
+    """150 small blocks with three refused ones (each for another reason) and three wrong CRCs among them: the first of
+    either kind is chosen among candidates that workgroups report in any order.  In the second file the first wrong CRC
+    lies behind the first refused block."""
+    text = contents()["fastq"]
+    r = random.Random(53)
+    good, at = [], 0
+    for k in range(150):
+        n = r.randrange(20, 200)
+        good.append(text_block(text[at:at + n], level=(1, 6, 9, 0)[k % 4]))
+        at += n
+    b = Bits()
+    b.put(1, 1)
+    b.put(3, 2)
+    refused = {"type-3": block(b.bytes() + b"\0\0\0\0", 5, zlib.crc32(b"hello")),
+               "distance": block(fixed_block([97, 98, 99, (6, 4)]).bytes(), 9, zlib.crc32(b"abcabcabc")),
+               "isize": block(deflate(text[:301]), 300, zlib.crc32(text[:300]))}
+
+    def wrong(raw):
+        return raw[:-8] + bytes([raw[-8] ^ 0x10]) + raw[-7:]
+
+    D = {}
+    for name, bad, crc in (("several-findings", {5: "type-3", 9: "distance", 40: "isize"}, (3, 7, 60)),
+                           ("several-findings-crc-behind", {5: "distance", 9: "isize", 40: "type-3"}, (7, 60))):
+        blocks = [refused[bad[k]] if k in bad else wrong(g) if k in crc else g for k, g in enumerate(good)]
+        D[name] = b"".join(blocks) + EOF
+        v = verdict(D[name])
+        assert (v["bad_block"], v["crc_block"]) == (5, crc[0]) and v["good"].count(False) == 3
+    return D
 
 
 def malformed_frames():
@@ -406,4 +642,33 @@ def damaged():
     D["stored-past-the-input"] = one(b"hello", stored_block(b"hello").bytes()[:-2])
     D["stored-past-isize"] = one(b"hello", stored_block(b"hello!").bytes(), 5)
     D["wrong-crc"] = text_block(text[:200]) + block(deflate(text[200:700]), 500, 12345) + text_block(text[700:900]) + EOF  # accepted
+    D.update(cut_at_the_window_edge())
+    D.update(several_findings())
+    D.update({name: raw for name, (raw, _) in sizes_wrong_crc().items()})   # accepted
     return D
+
+
+def sweeps():
+    """the names in damaged() of the two sweeps, which have tests of their own"""
+    return sorted(cut_at_the_window_edge()), sorted(sizes_wrong_crc())
+
+
+# Why the decoder core refuses the first refused block of the hand-made files of damaged() (fqg_inflate_core.h: kInfBad*;
+# include/fqg_codes.h: FQG_E_INFLATE_*).  zlib has no such number; these were read off the core once and are kept.
+REASONS = {
+    "type-3": 32,
+    "len-nlen": 33,
+    "hlit-287": 34, "hdist-31": 34, "no-end-of-block-code": 34, "oversubscribed-literals": 34, "incomplete-literals": 34,
+    "incomplete-distances": 34, "oversubscribed-distances": 34, "code-length-code-incomplete": 34,
+    "code-length-code-oversubscribed": 34, "repeat-with-nothing-before": 34, "repeat-past-the-end": 34,
+    "length-symbol-286": 35, "distance-symbol-30": 35, "unused-distance-code": 35,
+    "distance-beyond-the-start": 36,
+    "isize-plus-one": 37, "isize-minus-one": 37, "stored-past-isize": 37,
+    "cut-short": 38, "stored-past-the-input": 38,
+    "several-findings": 32, "several-findings-crc-behind": 36,
+}
+
+
+def reason(name):
+    """the reason a file of damaged() is refused for, or None where this table does not say (the flipped bits)"""
+    return 38 if name in cut_at_the_window_edge() else REASONS.get(name)

@@ -29,6 +29,16 @@ def run(check, path, member):
 
 
 def contents():
+    """(name, bytes) pairs; made once, the other test modules that read them included"""
+    if not _CONTENTS:
+        _CONTENTS.extend(_make_contents())
+    return iter(_CONTENTS)
+
+
+_CONTENTS = []
+
+
+def _make_contents():
     r = random.Random(5)
     yield "empty", b""
     yield "one_byte", b"@"

@@ -3,8 +3,9 @@
 The golden invocations of bam2fastq, bam_add_tags and bam_umi_count run once more with the variable: exit status, stdout,
 stderr and every output file are the golden's, byte for byte; on every fourth run FQGPU_INFLATE_DEBUG=1 adds the line
 that says which inflate ran.  Fixed cases: a block zlib refuses (the message and status of the host path), a wrong stored
-CRC-32 (not looked at, as the host path does not), FQGPU_INFLATE_GPU=0, and bam_umi_count over two contexts, which keeps
-the host inflate."""
+CRC-32 (not looked at, as the host path does not), FQGPU_INFLATE_GPU=0, bam_umi_count over two contexts, which keeps
+the host inflate, and the chain of two programs: a BAM file that fastq_pre_barcodes --bam compressed on the device,
+inflated on the device by bam2fastq."""
 import gzip
 import hashlib
 import os
@@ -200,3 +201,27 @@ def test_bam_umi_count_over_two_contexts_keeps_the_host_inflate():
     assert runs["two"][3][0].startswith("[inflate] host: ") and runs["one"][3][0].startswith("[inflate] device: ")
     assert runs["off"][0] == 0 and runs["off"][3] == []
     assert runs["two"][:3] == runs["one"][:3] == runs["off"][:3]
+
+
+def test_a_file_compressed_on_the_device_is_inflated_on_the_device():
+    from tests import test_gpu_pre_barcodes_bam as t_pb
+    r1, r2 = t_pb.plain_pairs(np.random.default_rng(19), 700)
+    with tempfile.TemporaryDirectory() as d:
+        for fn, img in (("r1.fastq", r1), ("r2.fastq", r2)):
+            with open(os.path.join(d, fn), "wb") as f:
+                f.write(img)
+        rc, bam, err = t_pb.run(t_pb.PAIRED, d, {"FQGPU_GZIP_GPU": "1"})
+    assert rc == 0, err
+    v = bgzfgen.verdict(bam)
+    assert v["n_blocks"] >= 4 and v["bad_block"] == v["crc_block"] == bgzfgen.NONE   # three blocks of records or more
+    runs = {}
+    for name, env in (("device", dict(ON, FQGPU_INFLATE_DEBUG="1")), ("host", {})):
+        rc, out, err, files = with_file(bam, lambda rel, tmp: t_b2f.run_program(["--bam", rel, "--out", "OUT"], env=env))
+        err, said = split_debug(re.sub(r"\S*in\.bam", "IN", err))
+        runs[name] = (rc, out, err, files, said)
+    assert runs["device"][4] == ["[inflate] device: %d blocks\n" % v["n_blocks"]] and runs["host"][4] == []
+    assert runs["device"][:4] == runs["host"][:4]
+    rc, out, err, files = runs["device"][:4]
+    assert rc == 0 and out == b"", err
+    assert files["o_1.fastq.gz"] == r1.replace(b" 1:N:0", b"@1:N:0")
+    assert files["o_2.fastq.gz"] == r2.replace(b" 2:N:0", b"@2:N:0")
