@@ -2,10 +2,14 @@
 fqg_deflate_output_begin / _wait, through abi.py.  The output is walked by BSIZE: every block has BGZF's fixed sixteen
 header bytes and BSIZE = its length - 1, every block but the last holds FQG_GZ_MEMBER_TEXT bytes of text, a final call
 ends in the 28-byte end-of-file block, and behind the eighteen header bytes a block is byte for byte the gzip member
-fqg_deflate makes of the same text behind ITS ten - the compressor tests/cxx/deflate_model.cpp models."""
+fqg_deflate makes of the same text behind ITS ten - the compressor tests/cxx/deflate_model.cpp models.  The model's
+member behind the eighteen header bytes, BSIZE set, is what a block must be: compared on the families of
+tests/deflgen.py (what each reaches: tests/test_gpu_deflate.py), on every alignment of a device source behind every
+carry, and on more blocks than workgroups from a device tensor."""
 import ctypes as C
 import gzip
 import random
+import time
 import zlib
 
 import numpy as np
@@ -13,7 +17,7 @@ import pytest
 
 import fastq_utils_amd as fq
 from oracle import bam_tags_oracle as bto
-from tests import bamgen
+from tests import bamgen, deflgen
 from tests.test_gpu_bam_tags import make_stream
 from tests.test_pgzip import fastq_text
 
@@ -46,6 +50,17 @@ def contents():
     fastq = fastq_text(1500, 2)
     return {"fastq": (fastq * (need // len(fastq) + 1))[:need], "bam_records": b"".join(recs)[:need], "zeros": bytes(need),
             "noise": random.Random(3).randbytes(need)}
+
+
+@pytest.fixture(scope="module")
+def model():
+    """tests/cxx/deflate_model.cpp, built once (tests/test_gpu_deflate.py shares it)"""
+    return deflgen.shared()[0]
+
+
+@pytest.fixture(scope="module")
+def families():
+    return deflgen.shared()[1]
 
 
 def blocks_of(raw):
@@ -111,6 +126,58 @@ def test_blocks(ctx, contents, name, n, final):
         assert all(len(b) == len(t) + 31 and b[18] == 1 for b, t in blocks)  # stored
     if name == "zeros":
         assert all(len(b) < 1000 for b, _ in blocks)
+
+
+FAMILIES = ["sizes_" + c for c in deflgen.SIZE_CONTENTS] + ["tie", "parse_geometry", "same_slot", "window", "wide_tokens", "member_cycle"]
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_generated_texts_are_the_models_blocks(ctx, families, name):
+    """every text of a family of tests/deflgen.py, one call from host memory each"""
+    f = families[name]
+    for k, text in enumerate(f.texts):
+        r = ctx.bgzf_deflate(text)
+        assert r["n_members"] == (len(text) > 0) and r["members"] == f.bgzf(k), (name, k, len(text), f.reports[k][0]["written"])
+
+
+def test_every_alignment_of_a_device_source_behind_every_carry(ctx, model):
+    import torch
+    texts = deflgen.alignment_texts()
+    want = {}
+    for key, gz, reports in zip(texts, *model.run(list(texts.values()))):
+        want[key] = deflgen.bgzf_of(deflgen.split_members(gz, reports))
+    t = torch.zeros(M + 700 + 64, dtype=torch.uint8, device="cuda")
+    assert t.data_ptr() % 16 == 0
+    for (c, n), text in texts.items():
+        src = torch.frombuffer(bytearray(text[c:]), dtype=torch.uint8).cuda()
+        for s in range(16):
+            t.fill_(0x5A)
+            t[16 + s:16 + s + n - c] = src
+            torch.cuda.synchronize()
+            for again in range(1 + (n > M)):
+                r = ctx.bgzf_deflate(t.data_ptr() + 16 + s, carry=text[:c], nbytes=n - c)
+                assert r["n_members"] == -(-n // M) and r["members"] == want[c, n], (c, n, s, again)
+
+
+def test_more_blocks_than_workgroups_and_than_a_span_of_offsets(ctx, model, families):
+    """the member cycle of tests/deflgen.py from a device tensor (tests/test_gpu_deflate.py: the same from host memory)"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_members = max(2049 + 2, 2 * cus + 3)
+    assert n_members >= 2049 + 2 and n_members > 2 * cus + 2
+    f = families["member_cycle"]
+    text, order, last = deflgen.cycle_text(f.texts, n_members)
+    blocks = [deflgen.bgzf_block(gz) for gz in f.gz]
+    want = b"".join(blocks[k] for k in order) + deflgen.bgzf_of(model.run([last], report=False)[0])
+    t = torch.zeros(len(text) + 64, dtype=torch.uint8, device="cuda")
+    t[21:21 + len(text)] = torch.frombuffer(bytearray(text), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    for again in range(2):
+        t0 = time.perf_counter()
+        r = ctx.bgzf_deflate(t.data_ptr() + 21, nbytes=len(text))
+        print("%d blocks, %d bytes of text: %.2f s" % (n_members, len(text), time.perf_counter() - t0))
+        assert r["n_members"] == n_members and r["text_bytes"] == len(text)
+        assert r["members"] == want, again
 
 
 def test_empty_text(ctx):

@@ -1,18 +1,24 @@
 """fqg_deflate / fqg_text_deflate / fqg_deflate_output (gzip members compressed on the device) through abi.py.  Python's
 zlib reads every member by itself: it must end where the next one starts, hold exactly its cut of the text (zlib checks
 the CRC-32 and ISIZE of the trailer while it does; ISIZE is compared once more here), and be no larger than its text +
-23 bytes.  The members of a text do not depend on where the text lies or on how it was cut into calls."""
+23 bytes.  The members of a text do not depend on where the text lies or on how it was cut into calls.
+
+They are byte for byte what tests/cxx/deflate_model.cpp, the kernel's decisions in one byte loop, writes for the same
+text: on eight plain texts, and on the families of tests/deflgen.py, each made to reach one thing the workgroup adds to
+the model - every member size, both sides of stored | dynamic, matches at the edges of the parse's windows and steps,
+hash slots that many positions of a step share, the window's edge, tokens that need a third word, every alignment of a
+device source against every carry, and more members than workgroups, so that a workgroup's LDS goes from one member to
+the next and the gather reads behind its first span of offsets."""
 import ctypes as C
-import os
 import random
-import subprocess
+import time
 import zlib
 
 import numpy as np
 import pytest
 
 import fastq_utils_amd as fq
-from tests import b2f_gen, split_gen
+from tests import b2f_gen, deflgen, split_gen
 from tests.test_fastdeflate import contents
 from tests.test_pgzip import fastq_text
 
@@ -39,6 +45,17 @@ def named():
 @pytest.fixture(scope="module")
 def fastq():
     return fastq_text(1500, 1)
+
+
+@pytest.fixture(scope="module")
+def model():
+    """tests/cxx/deflate_model.cpp, built once (tests/test_gpu_bgzf.py shares it)"""
+    return deflgen.shared()[0]
+
+
+@pytest.fixture(scope="module")
+def families():
+    return deflgen.shared()[1]
 
 
 def members_of(gz):
@@ -142,18 +159,63 @@ def test_random_structures(ctx, seed):
     check(ctx, "structure_%d" % seed, structure(seed))
 
 
-def test_bytes_of_the_sequential_model(ctx, named, fastq, tmp_path):
+def test_bytes_of_the_sequential_model(ctx, model, named, fastq):
     """tests/cxx/deflate_model.cpp makes the kernel's decisions in one byte loop: the same bytes"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "deflate_model")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(root, "tests", "cxx", "deflate_model.cpp"), "-lz"], check=True)
     r = random.Random(11)
-    for name, data in (("fastq", fastq[:2 * M + 7]), ("text", named["text"][:M + 1]), ("runs", named["runs"][:M]),
-                       ("skewed", named["skewed"][:M]), ("noise", named["noise"][:M]), ("period_32768", (r.randbytes(32768) * 2)[:M]),
-                       ("seven", b"ACGTACG"), ("empty", b"")):
-        (tmp_path / "in").write_bytes(data)
-        subprocess.run([exe, str(tmp_path / "in"), str(tmp_path / "out.gz")], check=True, capture_output=True, timeout=120)
-        assert ctx.deflate(data)["members"] == (tmp_path / "out.gz").read_bytes(), name
+    cases = (("fastq", fastq[:2 * M + 7]), ("text", named["text"][:M + 1]), ("runs", named["runs"][:M]),
+             ("skewed", named["skewed"][:M]), ("noise", named["noise"][:M]), ("period_32768", (r.randbytes(32768) * 2)[:M]),
+             ("seven", b"ACGTACG"), ("empty", b""))
+    for (name, data), want in zip(cases, model.run([data for _, data in cases], report=False)[0]):
+        assert ctx.deflate(data)["members"] == want, name
+
+
+FAMILIES = ["sizes_" + c for c in deflgen.SIZE_CONTENTS] + ["tie", "parse_geometry", "same_slot", "window", "wide_tokens", "member_cycle"]
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_generated_texts_are_the_models_bytes(ctx, families, name):
+    """every text of a family of tests/deflgen.py, one call from host memory each"""
+    f = families[name]
+    for k, text in enumerate(f.texts):
+        r = ctx.deflate(text)
+        assert r["n_members"] == 1 and r["members"] == f.gz[k], (name, k, len(text), f.reports[k][0]["written"])
+
+
+def test_every_alignment_of_a_device_source_behind_every_carry(ctx, model):
+    """the first 16-byte word staged holds the source's skew and the carry's end, the last one the skew and the member's
+    end; the source has sixteen bytes and more of the tensor on either side"""
+    import torch
+    texts = deflgen.alignment_texts()
+    want = dict(zip(texts, model.run(list(texts.values()), report=False)[0]))
+    t = torch.zeros(M + 700 + 64, dtype=torch.uint8, device="cuda")
+    assert t.data_ptr() % 16 == 0
+    for (c, n), text in texts.items():
+        src = torch.frombuffer(bytearray(text[c:]), dtype=torch.uint8).cuda()
+        for s in range(16):
+            t.fill_(0xA5)
+            t[16 + s:16 + s + n - c] = src
+            torch.cuda.synchronize()
+            for again in range(1 + (n > M)):
+                r = ctx.deflate(t.data_ptr() + 16 + s, carry=text[:c], nbytes=n - c)
+                assert r["n_members"] == -(-n // M) and r["members"] == want[c, n], (c, n, s, again)
+
+
+def test_more_members_than_workgroups_and_than_a_span_of_offsets(ctx, model, families):
+    """the member cycle of tests/deflgen.py from host memory: every workgroup compresses a third member and more, each
+    unlike the one before it in everything the workgroup keeps in LDS; k_deflate_gather reads the second span's sum"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_members = max(2049 + 2, 2 * cus + 3)
+    assert n_members >= 2049 + 2 and n_members > 2 * cus + 2
+    f = families["member_cycle"]
+    text, order, last = deflgen.cycle_text(f.texts, n_members)
+    want = b"".join(f.gz[k] for k in order) + model.run([last], report=False)[0][0]
+    for again in range(2):
+        t0 = time.perf_counter()
+        r = ctx.deflate(text)
+        print("%d members, %d bytes of text: %.2f s" % (n_members, len(text), time.perf_counter() - t0))
+        assert r["n_members"] == n_members and r["text_bytes"] == len(text)
+        assert r["members"] == want, again
 
 
 def test_members_depend_on_the_text_alone(ctx, fastq):
