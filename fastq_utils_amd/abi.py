@@ -44,6 +44,7 @@ EXPORTS = [
     "fqg_bam2fastq", "fqg_bam2fastq_output", "fqg_deflate", "fqg_text_deflate", "fqg_deflate_output",
     "fqg_bgzf_deflate", "fqg_text_bgzf_deflate", "fqg_deflate_output_begin", "fqg_deflate_output_wait",
     "fqg_bgzf_inflate", "fqg_inflate_output", "fqg_inflate_device",
+    "fqg_bam_header_end", "fqg_bam_index_device", "fqg_bam_index_offsets", "fqg_bam_index_output",
     "fqg_umi_count", "fqg_umi_features", "fqg_umi_record_features", "fqg_umi_replayed_features", "fqg_umi_umis",
     "fqg_umi_cells", "fqg_umi_entries", "fqg_umi_emit",
     "fqg_fp_owner", "fqg_names_fingerprints", "fqg_names_fingerprints_acct", "fqg_names_fingerprints_named", "fqg_frame_name_records", "fqg_frame_names_equal", "fqg_device_alloc", "fqg_device_free",
@@ -71,6 +72,11 @@ class InflateResult(C.Structure):
 
 
 NO_BLOCK = 2 ** 64 - 1  # bad_block / crc_block: none
+NEED_MORE = 1  # FQG_NEED_MORE
+
+
+class BamIndexResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("used", C.c_uint64)]
 
 
 class FileState(C.Structure):
@@ -341,6 +347,11 @@ def load():
     L.fqg_inflate_output.argtypes = [vp, u64, vp, u64]
     L.fqg_inflate_device.argtypes = [vp]
     L.fqg_inflate_device.restype = vp
+    L.fqg_bam_header_end.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.fqg_bam_index_device.argtypes = [vp, vp, u64, u64, C.POINTER(BamIndexResult)]
+    L.fqg_bam_index_offsets.argtypes = [vp]
+    L.fqg_bam_index_offsets.restype = vp
+    L.fqg_bam_index_output.argtypes = [vp, u64, vp, u64]
     L.fqg_umi_emit.argtypes = [vp, C.POINTER(C.c_uint32), u64, C.c_uint32, C.POINTER(UmiResult)]
     L.fqg_umi_features.argtypes = [vp, vp, u64]
     L.fqg_umi_cells.argtypes = [vp, C.POINTER(u64), u64]
@@ -981,7 +992,7 @@ class Context:
         return a
 
     def bam_add_tags(self, stream, tenx=False, tx_tag=False, targets=(), genes=None, offsets=None, nbytes=None,
-                     want_output=True):
+                     want_output=True, offsets_device=None):
         """bam_add_tags' alignment loop (src/bam_add_tags.c:250-294) on an inflated BAM stream: bytes (host) or an
         int device pointer (then `nbytes` and `offsets` are required).  targets: the header's reference names;
         genes: {transcript name: gene} (--tx_2_gx) or None.  Returns the result fields and, with want_output, the
@@ -991,7 +1002,7 @@ class Context:
         if host:
             buf = (C.c_char * max(1, len(stream))).from_buffer_copy(stream)
             nbytes = len(stream)
-        offs, n_rec, _ = _bam_offsets(buf if host else None, nbytes, offsets)
+        offs, n_rec, mem = _bam_offsets_arg(buf if host else None, nbytes, offsets, offsets_device, host)
         nt = len(targets)
         blob, tx_off, tx_len, gx_off, gx_len = bytearray(), [], [], [], []
         for t in targets:
@@ -1008,8 +1019,7 @@ class Context:
         p.tx_off, p.tx_len, p.gx_off, p.gx_len = keep[0], keep[1], keep[2], keep[3]
         p.names, p.names_bytes = keep[4], len(blob)
         r = BamTagsResult()
-        self._check(L.fqg_bam_add_tags(self.h, buf if host else C.c_void_p(int(stream)), nbytes,
-                                       MEM_HOST if host else MEM_DEVICE, offs,
+        self._check(L.fqg_bam_add_tags(self.h, buf if host else C.c_void_p(int(stream)), nbytes, mem, offs,
                                        n_rec, C.byref(p), C.byref(r)))
         out = {k: getattr(r, k) for k, _ in BamTagsResult._fields_ if k != "reserved"}
         if r.code == 0 and want_output:
@@ -1018,7 +1028,7 @@ class Context:
             out["records"] = dst.raw[:r.out_bytes]
         return out
 
-    def bam2fastq(self, stream, tenx=False, offsets=None, nbytes=None, first_alignment=0):
+    def bam2fastq(self, stream, tenx=False, offsets=None, nbytes=None, first_alignment=0, offsets_device=None):
         """bam2fastq's alignment loop (src/bam2fastq.c:249-355) on an inflated BAM stream: bytes (host) or an int device
         pointer (then `nbytes` and `offsets` are required).  Returns the result fields (out_bytes and first_record as
         lists of six) and `streams`: the six output byte strings (FILE_LOC order; three used with tenx).  With a
@@ -1028,11 +1038,11 @@ class Context:
         if host:
             buf = (C.c_char * max(1, len(stream))).from_buffer_copy(stream)
             nbytes = len(stream)
-        offs, n_rec, _ = _bam_offsets(buf if host else None, nbytes, offsets)
+        offs, n_rec, mem = _bam_offsets_arg(buf if host else None, nbytes, offsets, offsets_device, host)
         p = B2fParams()
         p.tenx, p.first_alignment = int(tenx), first_alignment
         r = B2fResult()
-        self._check(L.fqg_bam2fastq(self.h, buf if host else C.c_void_p(int(stream)), nbytes, MEM_HOST if host else MEM_DEVICE,
+        self._check(L.fqg_bam2fastq(self.h, buf if host else C.c_void_p(int(stream)), nbytes, mem,
                                     offs, n_rec, C.byref(p), C.byref(r)))
         out = {k: getattr(r, k) for k in ("n_alignments", "warn_record", "record", "entry", "aux", "code")}
         out["out_bytes"], out["first_record"] = list(r.out_bytes), list(r.first_record)
@@ -1119,6 +1129,23 @@ class Context:
     def inflate_device(self):
         return load().fqg_inflate_device(self.h) or 0
 
+    def bam_index_device(self, stream_dev, nbytes, first_record):
+        """fqg_bam_index_device: the records of [first_record, nbytes) of the stream at the int device pointer
+        `stream_dev`.  Returns n_records and used; the offsets stay on the device (bam_index_offsets is where,
+        bam_index_output fetches a range) and go to umi_count / bam_add_tags / bam2fastq as
+        offsets_device=(pointer, how many)."""
+        r = BamIndexResult()
+        self._check(load().fqg_bam_index_device(self.h, C.c_void_p(int(stream_dev)), nbytes, first_record, C.byref(r)))
+        return {"n_records": int(r.n_records), "used": int(r.used)}
+
+    def bam_index_offsets(self):
+        return load().fqg_bam_index_offsets(self.h) or 0
+
+    def bam_index_output(self, first, n):
+        dst = (C.c_uint64 * max(1, n))()
+        self._check(load().fqg_bam_index_output(self.h, first, dst, n))
+        return list(dst)[:n]
+
     def _deflate_result(self, r, want_output):
         out = {k: int(getattr(r, k)) for k, _ in DeflateResult._fields_}
         if want_output:
@@ -1156,6 +1183,23 @@ class Context:
     def synth_fastq(self, device_ptr, n_records, read_len=150, first_index=0, seed=12345, mate=1):
         self._check(load().fqg_synth_fastq(self.h, C.c_void_p(int(device_ptr)), n_records, read_len,
                                            first_index, seed, mate))
+
+
+def bam_header_end(prefix, nbytes_total):
+    """fqg_bam_header_end on the bytes `prefix` of a stream of nbytes_total: (return code, first_record, need) - the code
+    is 0, NEED_MORE or -3 (FQG_ERR_ARG)"""
+    first, need = C.c_uint64(), C.c_uint64()
+    rc = load().fqg_bam_header_end(bytes(prefix), len(prefix), nbytes_total, C.byref(first), C.byref(need))
+    return rc, first.value, need.value
+
+
+def _bam_offsets_arg(buf, nbytes, offsets, offsets_device, host):
+    """(the offsets argument, how many, mem) of a bulk BAM call; offsets_device = (device pointer, number of records)"""
+    if offsets_device is not None:
+        assert not host
+        return C.cast(C.c_void_p(int(offsets_device[0])), C.POINTER(C.c_uint64)), int(offsets_device[1]), MEM_DEVICE_INDEXED
+    offs, n_rec, _ = _bam_offsets(buf, nbytes, offsets)
+    return offs, n_rec, MEM_HOST if host else MEM_DEVICE
 
 
 def _bam_offsets(buf, nbytes, offsets=None):

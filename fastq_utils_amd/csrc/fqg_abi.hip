@@ -32,6 +32,7 @@
 #include "fqg_bam2fastq_kernels.hip"
 #include "fqg_deflate_kernels.hip"
 #include "fqg_inflate_kernels.hip"
+#include "fqg_bam_index_kernels.hip"
 
 using namespace fqg;
 
@@ -178,6 +179,12 @@ struct fqg_ctx {
   DevBuf inf_out, inf_raw, inf_rows, inf_status, inf_first;
   uint64_t inf_bytes = 0;
   bool inf_valid = false;
+  // fqg_bam_index_device: the offsets of the last call in a buffer no other call moves, and the call's scratch - the two
+  // tables of one window, its stretches, the follower's state
+  DevBuf bx_offsets, bx_entries, bx_counts, bx_stretch, bx_state;
+  uint64_t bx_n = 0;
+  bool bx_valid = false;
+  const unsigned long long* bam_offs = nullptr;  // the offsets of the running fqg_bam_add_tags / fqg_bam2fastq call
   IndexCall* d_icall = nullptr;
   IndexCall* h_icall = nullptr;  // pinned
 
@@ -332,28 +339,43 @@ int grid_for_waves(fqg_ctx* c, uint64_t n_records) {
 // ---- what fqg_bam_add_tags and fqg_bam2fastq (`name`) share --------------------------------------
 // The input side: the argument checks, then `begin()` (the call's own checks; its result and its last output
 // cleared), the offsets, and the stream on the device at a 16-byte boundary (the tiles are staged with 16-byte
-// loads) with its offsets in c->bam_off.  *d_buf: the stream there; nothing is copied for a call without records.
+// loads) with its offsets in c->bam_off (c->bam_offs: where they are).  *d_buf: the stream there; nothing is copied for
+// a call without records.  FQG_MEM_DEVICE_INDEXED: the offsets are device memory and are read where they lie - the host
+// cannot look at them, so that they ascend inside the stream is the caller's word (fqg_bam_index_device keeps it); the
+// first one comes back (*first_offset: eight bytes) for the mean record size, as a piece of a stream that is handed over
+// with its front has nbytes far above what its records take.
 template <class Begin>
 int bam_input(fqg_ctx* c, const char* name, bool have_args, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets,
-              uint64_t n_records, Begin begin, const uint8_t** d_buf) {
+              uint64_t n_records, Begin begin, const uint8_t** d_buf, uint64_t* first_offset) {
   if (!c || !have_args || (n_records && (!stream || !offsets))) return FQG_ERR_ARG;
-  if (mem != FQG_MEM_HOST && mem != FQG_MEM_DEVICE) return FQG_ERR_ARG;
+  if (mem != FQG_MEM_HOST && mem != FQG_MEM_DEVICE && mem != FQG_MEM_DEVICE_INDEXED) return FQG_ERR_ARG;
   if (n_records >= 0x7FFFFFFFull) return fail(c, FQG_ERR_ARG, (std::string(name) + ": more than 2^31 alignments in one call").c_str());
   NEED(begin());
   HIP_TRY(c, hipSetDevice(c->device));
   *d_buf = nullptr;
   if (!n_records) return 0;
   const uint32_t n = (uint32_t)n_records;
-  for (uint32_t k = 0; k < n; ++k)  // (a tile is the span from its first record to the end of its last)
-    if (offsets[k] + 36 > nbytes || (k && offsets[k] <= offsets[k - 1]))
-      return fail(c, FQG_ERR_ARG, (std::string(name) + ": offsets must ascend and lie inside the stream (fqg_bam_index_records)").c_str());
+  if (mem != FQG_MEM_DEVICE_INDEXED)
+    for (uint32_t k = 0; k < n; ++k)  // (a tile is the span from its first record to the end of its last)
+      if (offsets[k] + 36 > nbytes || (k && offsets[k] <= offsets[k - 1]))
+        return fail(c, FQG_ERR_ARG, (std::string(name) + ": offsets must ascend and lie inside the stream (fqg_bam_index_records)").c_str());
   if (mem == FQG_MEM_HOST || ((uintptr_t)stream & 15u)) {
     NEED(ensure(c, c->bam_in, nbytes + 64));
     HIP_TRY(c, hipMemcpyAsync(c->bam_in.p, stream, nbytes, mem == FQG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     *d_buf = (const uint8_t*)c->bam_in.p;
   } else *d_buf = (const uint8_t*)stream;
+  if (mem == FQG_MEM_DEVICE_INDEXED) {
+    c->bam_offs = reinterpret_cast<const unsigned long long*>(offsets);  // (the caller's, in HBM)
+    HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[5], offsets, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *first_offset = c->h_scalar[5];
+    if (*first_offset + 36 > nbytes) return fail(c, FQG_ERR_ARG, (std::string(name) + ": the first offset lies outside the stream").c_str());
+    return 0;
+  }
+  *first_offset = offsets[0];
   NEED(ensure(c, c->bam_off, (size_t)n * 8));
   HIP_TRY(c, hipMemcpyAsync(c->bam_off.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  c->bam_offs = (const unsigned long long*)c->bam_off.p;
   return 0;
 }
 
@@ -484,7 +506,8 @@ void fqg_close(fqg_ctx* c) {
   for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call,
                     &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf, &c->gz_text.buf, &c->gz_in, &c->gz_carry,
                     &c->gz_slots, &c->gz_sizes, &c->gz_off, &c->gz_sums, &c->gz_toks, &c->gz_tab, &c->inf_out, &c->inf_raw,
-                    &c->inf_rows, &c->inf_status, &c->inf_first})
+                    &c->inf_rows, &c->inf_status, &c->inf_first, &c->bx_offsets, &c->bx_entries, &c->bx_counts, &c->bx_stretch,
+                    &c->bx_state})
     release(*b);
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
@@ -548,10 +571,13 @@ int fqg_release_scratch(fqg_ctx* c) {
   for (DevBuf* b : {&c->image, &c->tile_counts, &c->tile_local, &c->span_sums, &c->line_end, &c->records, &c->suspect, &c->list,
                     &c->stage, &c->cinfo, &c->queue, &c->redo, &c->lines_slow, &c->build_keys[0], &c->build_keys[1],
                     &c->build_cursor, &c->build_spill, &c->name_recs, &c->name_hcount, &c->name_redo, &c->name_redo_chunks,
-                    &c->bc_status, &c->bc_tile_big, &c->inf_out, &c->inf_raw, &c->inf_rows, &c->inf_status, &c->inf_first})
+                    &c->bc_status, &c->bc_tile_big, &c->inf_out, &c->inf_raw, &c->inf_rows, &c->inf_status, &c->inf_first,
+                    &c->bx_offsets, &c->bx_entries, &c->bx_counts, &c->bx_stretch, &c->bx_state})
     release(*b);
   c->inf_valid = false;  // (fqg_inflate_device: valid until here)
   c->inf_bytes = 0;
+  c->bx_valid = false;  // (fqg_bam_index_offsets: valid until here)
+  c->bx_n = 0;
   for (int i = 0; i < 3; ++i) {
     release(c->bc_len[i]);
     release(c->bc_off[i]);
@@ -2817,5 +2843,6 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 #include "fqg_split_abi.inc"
 #include "fqg_deflate_abi.inc"
 #include "fqg_inflate_abi.inc"
+#include "fqg_bam_index_abi.inc"
 
 }  // extern "C"

@@ -24,7 +24,7 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
   bam_tile_shape(A, kB2fInCap, kB2fOutCap, mean_in, 2.3 * mean_in, 16u * 2u * (uint32_t)ns, "FQGPU_B2F_T");
   A.buf = d_buf;
   A.nbytes = nbytes;
-  A.offs = (const unsigned long long*)c->bam_off.p;
+  A.offs = c->bam_offs;
   A.n = n;
   A.tenx = prm->tenx ? 1 : 0;
   A.n_streams = ns;
@@ -76,16 +76,17 @@ int b2f_run(fqg_ctx* c, const uint8_t* d_buf, uint64_t nbytes, uint32_t n, doubl
 int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets, uint64_t n_records,
                   const fqg_b2f_params* prm, fqg_b2f_result* out) {
   const uint8_t* d_buf;
+  uint64_t first_offset = 0;
   auto begin = [&] {
     memset(out, 0, sizeof(*out));
     out->warn_record = FQG_B2F_UNUSED;
     for (int s = 0; s < FQG_B2F_STREAMS; ++s) out->first_record[s] = FQG_B2F_UNUSED;
     return text_begin(c, c->b2f_text);
   };
-  NEED(bam_input(c, "fqg_bam2fastq", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
+  NEED(bam_input(c, "fqg_bam2fastq", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf, &first_offset));
   if (!n_records) return 0;
   const uint32_t n = (uint32_t)n_records;
-  const double mean_in = (double)(nbytes - offsets[0]) / (double)n;
+  const double mean_in = (double)(nbytes - first_offset) / (double)n;
   B2fCall call;
   NEED(b2f_run(c, d_buf, nbytes, n, mean_in, prm, out, &call));
   if (call.first_finding != ~0ull) {
@@ -102,7 +103,15 @@ int fqg_bam2fastq(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
     out->record = k;
     out->entry = prm->first_alignment + k + 1;
     out->code = code;
-    out->aux = code == FQG_E_B2F_SAMPLE_QUAL ? offsets[k] + aux : 0;
+    uint64_t at = 0;
+    if (code == FQG_E_B2F_SAMPLE_QUAL) {
+      if (mem == FQG_MEM_DEVICE_INDEXED) {
+        HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[5], offsets + k, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        at = c->h_scalar[5];
+      } else at = offsets[k];
+    }
+    out->aux = code == FQG_E_B2F_SAMPLE_QUAL ? at + aux : 0;
   }
   return 0;
 }

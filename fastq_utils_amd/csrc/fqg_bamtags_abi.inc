@@ -3,6 +3,7 @@
 int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets, uint64_t n_records,
                      const fqg_bam_tags_params* prm, fqg_bam_tags_result* out) {
   const uint8_t* d_buf;
+  uint64_t first_offset = 0;
   auto begin = [&] {
     if (prm->n_targets && (!prm->tx_off || !prm->tx_len || !prm->gx_off || !prm->gx_len || !prm->names)) return (int)FQG_ERR_ARG;
     memset(out, 0, sizeof(*out));
@@ -10,7 +11,7 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
     c->bt_begun = true;
     return text_begin(c, c->bt_text);
   };
-  NEED(bam_input(c, "fqg_bam_add_tags", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf));
+  NEED(bam_input(c, "fqg_bam_add_tags", out && prm, stream, nbytes, mem, offsets, n_records, begin, &d_buf, &first_offset));
   if (!n_records) return 0;
   const uint32_t n = (uint32_t)n_records;
   hipStream_t st = c->stream;
@@ -55,14 +56,14 @@ int fqg_bam_add_tags(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, c
   BtCall* d_call = (BtCall*)c->bt_call.p;
   unsigned long long* d_total = (unsigned long long*)((char*)c->bt_call.p + sizeof(BtCall));
   HIP_TRY(c, hipMemcpyAsync(d_call, &h_call, sizeof(h_call), hipMemcpyHostToDevice, st));
-  const double mean_in = (double)(nbytes - offsets[0]) / (double)n;
+  const double mean_in = (double)(nbytes - first_offset) / (double)n;
   BtTiles A;
   memset(&A, 0, sizeof(A));
   bam_tile_shape(A, kBtInCap, kBtOutCap, mean_in, 1.15 * (mean_in + 16.0 * 4 + (prm->tx_tag ? 40.0 : 0.0)), 0, "FQGPU_BT_T");
   const unsigned lds = A.in_cap + A.out_cap + 64;
   A.buf = d_buf;
   A.nbytes = nbytes;
-  A.offs = (const unsigned long long*)c->bam_off.p;
+  A.offs = c->bam_offs;
   A.n = n;
   A.new_size = (uint32_t*)c->bam_size.p;
   A.out_local = (const unsigned long long*)c->bam_local.p;

@@ -258,7 +258,9 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   {
     ProfScope ps(c, "k_umi_parse");
     // records per tile and the LDS area: what the mean record needs
-    // (the index on the device: the header in front of the first record is small beside the records)
+    // (the index on the device: the header in front of the first record is small beside the records, and this call
+    // always gets the whole stream - no first offset is fetched.  fqg_bam_add_tags / fqg_bam2fastq do fetch it, eight
+    // bytes and a synchronisation: bam2fastq hands a later PIECE over from byte 0, where nbytes / n is far off)
     const double mean = mem == FQG_MEM_DEVICE_INDEXED ? (double)nbytes / (double)n : (double)(nbytes - offsets[0]) / (double)n;
     const uint32_t T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)kParseStage - 64.0) / (1.1 * mean + 1.0))));
     const uint32_t cap = std::min<uint32_t>((uint32_t)kParseStage, ((uint32_t)(1.15 * mean * T) + 256u + 15u) & ~15u);

@@ -108,6 +108,7 @@ int main(int argc, char* argv[]) {
   BamInput bam;
   bam.inflate(in, bam_file, g_ctx);
   bam.index(bam_file);  // (a record cut short ends the loop, :249)
+  bam.fetch_offsets();  // (the index on the device: 8 bytes per alignment come back, to cut the pieces)
   const std::vector<uint8_t>& stream = bam.stream;
   const std::vector<uint64_t>& offsets = bam.offsets;
   const uint64_t n_rec = bam.n_rec, used = bam.used;
@@ -126,17 +127,19 @@ int main(int argc, char* argv[]) {
     // a piece: whole alignments, up to `piece` bytes of the stream (one alignment at least)
     uint64_t last = done + 1;
     while (last < n_rec && last - done < 0x7FFFFFF0ull && offsets[last] + 4 - offsets[done] <= piece) ++last;
-    const uint64_t p0 = offsets[done] & ~(uint64_t)15;  // (a 16-byte boundary: the library stages with 16-byte loads)
+    // (a 16-byte boundary: the library stages with 16-byte loads; the offsets on the device count from byte 0 of the
+    // stream, which then is what is handed over - it lies at such a boundary)
+    const uint64_t p0 = bam.device_offsets ? 0 : offsets[done] & ~(uint64_t)15;
     const uint64_t p1 = last < n_rec ? offsets[last] : used;
-    std::vector<uint64_t> local(last - done);
-    for (uint64_t k = done; k < last; ++k) local[k - done] = offsets[k] - p0;
+    std::vector<uint64_t> local(bam.device_offsets ? 0 : last - done);
+    for (uint64_t k = done; k < last && !bam.device_offsets; ++k) local[k - done] = offsets[k] - p0;
     fqg_b2f_params prm;
     memset(&prm, 0, sizeof(prm));
     prm.tenx = tenx != 0;
     prm.first_alignment = done;
     fqg_b2f_result res;
-    rc = fqg_bam2fastq(g_ctx, bam.device ? bam.device + p0 : stream.data() + p0, p1 - p0, bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST,
-                       local.data(), last - done, &prm, &res);
+    rc = fqg_bam2fastq(g_ctx, bam.device ? bam.device + p0 : stream.data() + p0, p1 - p0, bam.mem(),
+                       bam.device_offsets ? bam.offs(done) : local.data(), last - done, &prm, &res);
     if (rc != 0) {
       PRINT_ERROR("GPU library failure in fqg_bam2fastq (%d): %s", rc, fqg_last_error(g_ctx));
       leave(2);
@@ -176,7 +179,7 @@ int main(int argc, char* argv[]) {
         case FQG_E_B2F_UMI: PRINT_ERROR("missing umi tag in entry  %llu\n", entry); leave(3);
         case FQG_E_B2F_UMI_QUAL: PRINT_ERROR("missing umi quality tag in entry  %llu\n", entry); leave(3);
         case FQG_E_B2F_SAMPLE_QUAL:
-          PRINT_ERROR("missing sample quality tag in entry  %llu for sample %s\n", entry, (const char*)stream.data() + p0 + res.aux);
+          PRINT_ERROR("missing sample quality tag in entry  %llu for sample %s\n", entry, bam.c_string(p0 + res.aux).c_str());
           leave(3);
         case FQG_E_B2F_TOO_LONG:
           PRINT_ERROR("%s: alignment %llu: a read of %d bases or more; the reference writes behind its %d-byte buffers there, this "

@@ -132,9 +132,8 @@ int main(int argc, char* argv[]) {
   bam.inflate(in, inbam_file, g_ctx);
   bam.index(inbam_file);
   const std::vector<uint8_t>& stream = bam.stream;
-  const std::vector<uint64_t>& offsets = bam.offsets;
   const uint64_t n_rec = bam.n_rec, used = bam.used;
-  const uint64_t header_end = n_rec ? offsets[0] : used;
+  const uint64_t header_end = bam.header_end;
   if (header_end > stream.size()) {
     PRINT_ERROR("%s is not a BAM file", inbam_file);
     leave(2);
@@ -199,8 +198,7 @@ int main(int argc, char* argv[]) {
   prm.names = names.data();
   prm.names_bytes = names.size();
   fqg_bam_tags_result res;
-  rc = fqg_bam_add_tags(g_ctx, bam.device ? bam.device : stream.data(), used, bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(),
-                        n_rec, &prm, &res);
+  rc = fqg_bam_add_tags(g_ctx, bam.data(), used, bam.mem(), bam.offs(), n_rec, &prm, &res);
   if (rc != 0) {
     PRINT_ERROR("GPU library failure in fqg_bam_add_tags (%d): %s", rc, fqg_last_error(g_ctx));
     leave(2);

@@ -291,8 +291,7 @@ int main(int argc, char* argv[]) {
     res.rl_changed = multi.rl_changed;
     res.rl_undefined = multi.rl_undefined;
   } else
-    LIB(fqg_umi_count(g_ctx, bam.device ? bam.device : stream.data(), stream.size(), bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(), n_rec,
-                      &prm, &res));
+    LIB(fqg_umi_count(g_ctx, bam.data(), bam.total, bam.mem(), bam.offs(), n_rec, &prm, &res));
   if (res.rl_unresolved) {  // never silently different from the reference
     fprintf(stderr, "\nERROR: bam_umi_count: a UMI set could not be replayed within this build's limits\n");
     leave(2);
@@ -310,8 +309,7 @@ int main(int argc, char* argv[]) {
   auto cells_in_front = [&] {
     fqg_umi_result part;
     if (!bam_sorted_by_cell || res.record == 0 ||
-        fqg_umi_count(g_ctx, bam.device ? bam.device : stream.data(), stream.size(), bam.device ? FQG_MEM_DEVICE : FQG_MEM_HOST, offsets.data(),
-                      res.record, &prm, &part) != 0 ||
+        fqg_umi_count(g_ctx, bam.data(), bam.total, bam.mem(), bam.offs(), res.record, &prm, &part) != 0 ||
         part.code != FQG_OK || part.rl_unresolved || part.n_cells < 2)
       return;
     const uint64_t written = part.n_cells - 1;

@@ -37,10 +37,12 @@ extern "C" {
 #define FQG_ERR_ARG (-3)         /* invalid argument */
 #define FQG_ERR_NOMEM (-4)       /* device or pinned allocation failed */
 #define FQG_ERR_STATE (-5)       /* call sequence violated (e.g. no frame to index) */
+#define FQG_NEED_MORE 1          /* fqg_bam_header_end: not an error - the prefix handed over is too short to tell */
 
 #define FQG_MEM_HOST 0
 #define FQG_MEM_DEVICE 1
-#define FQG_MEM_DEVICE_INDEXED 2 /* fqg_umi_count: the record stream AND the array of record offsets are device memory */
+#define FQG_MEM_DEVICE_INDEXED 2 /* fqg_umi_count, fqg_bam_add_tags, fqg_bam2fastq: the record stream AND the array of \
+                                    record offsets are device memory (fqg_bam_index_offsets makes such an array) */
 
 typedef struct fqg_ctx fqg_ctx;
 typedef struct fqg_acc fqg_acc;
@@ -547,7 +549,7 @@ int fqg_bam_index_records(const void *stream, uint64_t nbytes, uint64_t *offsets
                           uint64_t *used);
 /* mem: where `stream` lies.  offsets is host memory - 8 bytes per alignment to upload, 1 ms of a 6 ms call on
  * BASELINE configs[3] - unless mem is FQG_MEM_DEVICE_INDEXED (a caller that keeps the inflated records in HBM keeps
- * their index there too). */
+ * their index there too; fqg_bam_index_device makes it there). */
 int fqg_umi_count(fqg_ctx *ctx, const void *stream, uint64_t nbytes, int mem, const uint64_t *offsets,
                   uint64_t n_records, const fqg_umi_params *params, fqg_umi_result *out);
 /* After fqg_umi_count(defer_output = 1): apply the output rules with feature ids mapped through
@@ -599,7 +601,10 @@ int fqg_synth_fastq(fqg_ctx *ctx, void *device_out, uint64_t n_records, uint32_t
  * order; it stays on the device until fqg_bam_add_tags_output copies it.  The header (everything before the first
  * alignment) is not touched: the caller writes it as it read it (bam_header_write after bam_header_read).
  * The transcript -> gene map (--tx_2_gx, :203-232, get_gene :118-129) is resolved by the caller once per reference
- * of the header: gx_len[t] = FQG_NO_GENE when reference t has no gene. */
+ * of the header: gx_len[t] = FQG_NO_GENE when reference t has no gene.
+ * mem FQG_MEM_DEVICE_INDEXED, here and for fqg_bam2fastq: `offsets` is device memory, read where it lies (a pointer into
+ * the array of fqg_bam_index_offsets is fine: a piece of the records).  The host cannot check such offsets; that they
+ * ascend, each a record inside [0, nbytes), is the caller's word. */
 #define FQG_NO_GENE 0xFFFFFFFFu
 typedef struct {
   int32_t tenx;           /* --10x: the UMI goes to UB instead of RX (src/sam_tags.h:40-47) */
@@ -734,6 +739,41 @@ typedef struct {
 int fqg_bgzf_inflate(fqg_ctx *ctx, const void *raw, uint64_t nbytes, fqg_inflate_result *out);
 int fqg_inflate_output(fqg_ctx *ctx, uint64_t first, void *host_dst, uint64_t nbytes);
 const void *fqg_inflate_device(const fqg_ctx *ctx);
+
+/* ---- the record index of a BAM stream made on the device ----------------------------------------------------
+ * What fqg_bam_index_records does on the host, for a stream that lies in device memory (the one fqg_bgzf_inflate left
+ * there, a record store, any buffer of the caller's) - in two parts, because the header is a chain of tiny steps whose
+ * bytes the caller needs on the host anyway, and the records are the bulk.
+ *
+ * fqg_bam_header_end is host side, no GPU: the header walk of fqg_bam_index_records (magic, l_text, n_ref, the chain of
+ * the references) over the first `have` bytes of a stream of nbytes_total.  0: *first_record is where the first record
+ * would start (it may lie behind `have`).  FQG_NEED_MORE: the walk came to the end of the prefix; *need is the prefix
+ * length with which it gets further (a caller fetches at least that, better a good deal more).  FQG_ERR_ARG: exactly the
+ * streams fqg_bam_index_records refuses, judged against nbytes_total - or have > nbytes_total.
+ *
+ * fqg_bam_index_device walks the records of [first_record, nbytes) of the device buffer stream_dev (any alignment; it
+ * is read in whole aligned 16-byte words: up to 15 bytes in front of stream_dev and behind stream_dev + nbytes are loaded,
+ * never used, when they share such a word with a byte of the stream - a caller who sub-allocates must own those words).
+ * For EVERY content and every first_record <= nbytes, n_records, used and the offsets are what the loop of
+ * fqg_bam_index_records gives when it starts at first_record: offsets of the block_size fields, counted from byte 0 of
+ * the stream; used is where that loop stops.  Scratch: 6 bytes per stream byte of one window (FQGPU_BAMIDX_WINDOW,
+ * 128 MiB) and the offsets, 8 bytes for every 36 bytes behind first_record; fqg_release_scratch frees both.
+ *
+ * The offsets stay on the device in a buffer no other call moves or writes: fqg_bam_index_offsets is its address (null
+ * before the first call), valid until the next fqg_bam_index_device, fqg_release_scratch or fqg_close, and may be handed
+ * - with a record offset - to fqg_umi_count, fqg_bam_add_tags and fqg_bam2fastq as FQG_MEM_DEVICE_INDEXED together with
+ * stream_dev (the offsets count from byte 0 of the stream, so that is the `stream` of those calls; `nbytes` may end at
+ * the end of the last record handed over).  fqg_bam_index_output copies offsets [first, first + n) to the host; a range
+ * that passes n_records is FQG_ERR_ARG. */
+typedef struct {
+  uint64_t n_records;
+  uint64_t used; /* where the walk stopped: the end of the last complete record */
+} fqg_bam_index_result;
+int fqg_bam_header_end(const void *prefix, uint64_t have, uint64_t nbytes_total, uint64_t *first_record, uint64_t *need);
+int fqg_bam_index_device(fqg_ctx *ctx, const void *stream_dev, uint64_t nbytes, uint64_t first_record,
+                         fqg_bam_index_result *out);
+const uint64_t *fqg_bam_index_offsets(const fqg_ctx *ctx);
+int fqg_bam_index_output(fqg_ctx *ctx, uint64_t first, uint64_t *host_dst, uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -25,50 +25,12 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-
 from tests import bamgen  # noqa: E402
+from tools.quick_bam_files import reads_and_tagged  # noqa: E402
 
 RUNS = max(3, int(sys.argv[1])) if len(sys.argv) > 1 else 5
 BIN = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(REPO, "bin")
 OURS = BIN == os.path.join(REPO, "bin")
-
-
-def bam_of(text, n, R):
-    """an unaligned BAM stream of the first n synthetic records (R bytes each, 150 bases): the names as
-    fastq_pre_barcodes writes them (STAGS_CELL=.._UMI=.._SAMPLE=.._ETAGS_<name>), the reads' bases and qualities"""
-    L = 150
-    a = np.frombuffer(text, dtype=np.uint8, count=n * R).reshape(n, R)
-    rng = np.random.default_rng(1)
-    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
-    name = a[:, 1:R - (2 * L + 5)].copy()
-    name[name == 32] = 95
-    parts = [np.broadcast_to(np.frombuffer(b"STAGS_CELL=", dtype=np.uint8), (n, 11)), acgt[rng.integers(0, 4, (n, 16))],
-             np.broadcast_to(np.frombuffer(b"_UMI=", dtype=np.uint8), (n, 5)), acgt[rng.integers(0, 4, (n, 10))],
-             np.broadcast_to(np.frombuffer(b"_SAMPLE=", dtype=np.uint8), (n, 8)), acgt[rng.integers(0, 4, (n, 8))],
-             np.broadcast_to(np.frombuffer(b"_ETAGS_", dtype=np.uint8), (n, 7)), name, np.zeros((n, 1), dtype=np.uint8)]
-    qname = np.concatenate(parts, axis=1)
-    code = np.full(256, 15, dtype=np.uint8)
-    for ch, v in zip(b"ACGT", (1, 2, 4, 8)):
-        code[ch] = v
-    nib = code[a[:, R - (2 * L + 4):R - (L + 4)]]
-    seq = (nib[:, 0::2] << 4) | nib[:, 1::2]
-    qual = a[:, R - (L + 1):R - 1] - 33
-    body = 32 + qname.shape[1] + 4 + L // 2 + L
-    core = np.zeros((n, 36), dtype=np.uint8)
-    core[:, 0:4] = np.frombuffer(np.uint32(body).tobytes(), dtype=np.uint8)
-    core[:, 4:8] = 255                                                 # refID -1
-    core[:, 8:12] = 255                                                # pos -1
-    core[:, 12] = qname.shape[1]                                       # l_read_name, mapq 0
-    core[:, 14:16] = np.frombuffer(np.uint16(4680).tobytes(), dtype=np.uint8)  # bin
-    core[:, 16] = 1                                                    # one CIGAR operation
-    core[:, 18] = 4                                                    # flag: unmapped
-    core[:, 20:24] = np.frombuffer(np.uint32(L).tobytes(), dtype=np.uint8)
-    core[:, 24:32] = 255                                               # mate refID, mate pos -1
-    cigar = np.broadcast_to(np.frombuffer(np.uint32(L << 4).tobytes(), dtype=np.uint8), (n, 4))
-    recs = np.concatenate([core, qname, cigar, seq, qual], axis=1)
-    head = b"@HD\tVN:1.0\tSO:unsorted\n"
-    return b"BAM\x01" + len(head).to_bytes(4, "little") + head + (0).to_bytes(4, "little") + recs.tobytes()
 
 
 def med(xs):
@@ -77,24 +39,14 @@ def med(xs):
 
 out = {"runs": RUNS, "bin": os.path.relpath(BIN, REPO), "cpus_in_affinity_mask": len(os.sched_getaffinity(0)), "files": {}, "programs": {}}
 with tempfile.TemporaryDirectory() as tmp:
-    import torch
-
-    import fastq_utils_amd as fq
-    with fq.Context(0) as ctx:
-        R = fq.abi.synth_record_bytes(150)
-        img = torch.empty(500000 * R + 64, dtype=torch.uint8, device="cuda:0")
-        ctx.synth_fastq(img.data_ptr(), 500000, 150)
-        ctx.synchronize()
-        reads = bam_of(bytes(img[:500000 * R].cpu().numpy()), 500000, R)
-        del img
-    rec, _, _, _ = bamgen.config4(np.random.default_rng(4), n_cells=2000, n_genes=5000, n_triples=385000)
-    rec = rec[:500000]
+    reads, tagged = reads_and_tagged()
+    first_1k = tagged[:len(bamgen.header()) + 1000 * bamgen.REC_BYTES]
     files = {}
-    for name, stream in (("reads_500k", reads), ("tagged_500k", bamgen.header() + rec.tobytes()), ("tagged_1k", bamgen.header() + rec[:1000].tobytes())):
+    for name, stream in (("reads_500k", reads), ("tagged_500k", tagged), ("tagged_1k", first_1k)):
         files[name] = os.path.join(tmp, name + ".bam")
         with open(files[name], "wb") as f:
             f.write(bamgen.bgzf(stream))
-    del reads
+    del reads, tagged
     golden = os.path.join(REPO, "tests", "golden", "data_b2f", "test10e6.bam")
     if os.path.exists(golden):
         files["golden_test10e6"] = golden
