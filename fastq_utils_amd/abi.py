@@ -37,6 +37,7 @@ EXPORTS = [
     "fqg_index_alive", "fqg_index_n_frames", "fqg_index_frame", "fqg_index_names_captured", "fqg_index_expect_lookups", "fqg_records_gather",
     "fqg_records_gather_output", "fqg_records_split", "fqg_records_split_output", "fqg_records_split_info", "fqg_names_compare",
     "fqg_bam_header", "fqg_barcodes_transform", "fqg_barcodes_output", "fqg_barcodes_output_begin", "fqg_barcodes_output_wait", "fqg_records_filter", "fqg_records_filter_output",
+    "fqg_records_filter_info",
     "fqg_whitelist_create", "fqg_whitelist_destroy", "fqg_barcodes_whitelist",
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
@@ -300,6 +301,7 @@ def load():
     L.fqg_barcodes_output_wait.argtypes = [vp]
     L.fqg_records_filter.argtypes = [vp, vp, u64, u64, C.POINTER(FilterParams), C.POINTER(FilterResult)]
     L.fqg_records_filter_output.argtypes = [vp, vp, u64]
+    L.fqg_records_filter_info.argtypes = [vp, C.POINTER(u64)]
     L.fqg_fp_owner.argtypes = [u64, C.c_uint32]
     L.fqg_fp_owner.restype = C.c_uint32
     L.fqg_names_fingerprints.argtypes = [vp, vp, C.POINTER(FileState), u64, C.c_uint32, vp, C.POINTER(u64)]
@@ -775,6 +777,13 @@ class Context:
         buf = C.create_string_buffer(max(1, nbytes))
         self._check(load().fqg_records_filter_output(self.h, buf, nbytes))
         return buf.raw[:nbytes]
+
+    def records_filter_info(self):
+        """how the last records_filter ran: tiles, tiles on the direct path, wavefronts of the tile kernel, records per
+        tile, the bytes of LDS a tile has for its input span and for its output"""
+        v = (C.c_uint64 * 6)()
+        self._check(load().fqg_records_filter_info(self.h, v))
+        return dict(zip(("tiles", "big_tiles", "grid", "T", "in_cap", "out_cap"), (int(x) for x in v)))
 
     def barcodes_whitelist(self, frame, whitelist, offset, size, n_records=None, first_record=0, step=1, want_flags=False):
         """valid_barcode (src/bam_umi_count.c:523-535) on the `size` characters at `offset` of every record's sequence;

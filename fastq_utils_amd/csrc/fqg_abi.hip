@@ -166,6 +166,7 @@ struct fqg_ctx {
   OutText bc_text, bt_text, b2f_text;
   bool bt_begun = false;  // fqg_bam_add_tags has been called: FQG_TEXT_BAM_TAGS names a store
   uint64_t split_info[4] = {0, 0, 0, 0};  // of the last fqg_records_split: tiles, tiles on the direct path, emit grid, T
+  uint64_t filter_info[6] = {0, 0, 0, 0, 0, 0};  // of the last fqg_records_filter: the same four, then in_cap and out_cap
   DevBuf bam_in, bam_off, bam_size, bam_local, bam_sums;  // scratch of one fqg_bam_add_tags / fqg_bam2fastq call
   DevBuf bt_tables, bt_call;  // fqg_bam_add_tags
   DevBuf b2f_call;            // fqg_bam2fastq
@@ -2626,8 +2627,10 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   if (!c || !frame || !fp || !out) return FQG_ERR_ARG;
   NEED(text_begin(c, c->bc_text));
   memset(out, 0, sizeof(*out));
+  for (uint64_t& v : c->filter_info) v = 0;
   if (fp->mode != FQG_FILTER_N && fp->mode != FQG_FILTER_POLY_AT) return fail(c, FQG_ERR_ARG, "fqg_records_filter: unknown mode");
-  if (first_record + n_rec > frame->fv.n_records) return fail(c, FQG_ERR_ARG, "fqg_records_filter: records beyond the frame");
+  if (first_record > frame->fv.n_records || n_rec > frame->fv.n_records - first_record)
+    return fail(c, FQG_ERR_ARG, "fqg_records_filter: records beyond the frame");
   HIP_TRY(c, hipSetDevice(c->device));
   out->n_records = n_rec;
   if (!n_rec) return 0;
@@ -2688,12 +2691,13 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   uint8_t* text[2];
   NEED(text_reserve(c, c->bc_text, totals, 2, text));
   text_publish(c->bc_text, totals, 2);
+  unsigned grid_t = 0;
   if (h_tot[1]) {
     ProfScope ps(c, "k_rf_emit");
     const EmitOut eo{(const uint32_t*)c->bc_len[1].p, (const unsigned long long*)c->bc_off[1].p,
                      (const unsigned long long*)c->bc_sum[1].p, text[1]};
     const unsigned lds = tc.in_cap + tc.out_cap;
-    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_rf_emit_tile, lds));
+    const unsigned grid = grid_t = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_rf_emit_tile, lds));
     hipLaunchKernelGGL(k_rf_emit_tile, dim3(grid), dim3(kWave), lds, c->stream, F, P, tc, n_rec,
                        (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo);
     if (c->h_bcall->big) {
@@ -2704,6 +2708,18 @@ int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
+  c->filter_info[0] = n_tiles;
+  c->filter_info[1] = c->h_bcall->big;
+  c->filter_info[2] = grid_t;  // (0: every record was dropped, nothing was emitted)
+  c->filter_info[3] = tc.T;
+  c->filter_info[4] = tc.in_cap;
+  c->filter_info[5] = tc.out_cap;
+  return 0;
+}
+
+int fqg_records_filter_info(const fqg_ctx* c, uint64_t info[6]) {
+  if (!c || !info) return FQG_ERR_ARG;
+  for (int i = 0; i < 6; ++i) info[i] = c->filter_info[i];
   return 0;
 }
 

@@ -95,10 +95,18 @@ int text_copy_begin(fqg_ctx* c, OutText& o, int s, void* host_dst, uint64_t nbyt
 // ---- the small pieces beside them -----------------------------------------------------------------
 // A persistent grid of one-wavefront workgroups: exactly the wavefronts that are resident at once (tiles are dealt
 // round-robin, so a wavefront that starts late would do its whole share after the others have finished).
+// FQGPU_TILE_WAVES=n (n >= 1) caps the grid: a wavefront then walks many tiles of a small image (measurement and tests
+// only - results do not depend on it).
 unsigned resident_waves(fqg_ctx* c, const void* kernel, unsigned lds) {
+  static const unsigned env_cap = [] {
+    const char* e = getenv("FQGPU_TILE_WAVES");
+    const long v = e ? atol(e) : 0;
+    return (unsigned)(v >= 1 && v <= 0x7FFFFFFFl ? v : 0);
+  }();
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kWave, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  return (unsigned)per_cu * (unsigned)c->cu_count;
+  const unsigned waves = (unsigned)per_cu * (unsigned)c->cu_count;
+  return env_cap ? std::min(env_cap, waves) : waves;
 }
 
 // the call's counters zeroed on the device; `none`: what first_finding and first_discard start from

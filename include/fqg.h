@@ -442,7 +442,10 @@ int fqg_barcodes_whitelist(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_
  * (src/fastq_trim_poly_at.c:77-119 trim_poly_at, :214-222 the min_len test and the counters).
  * Works on records [first_record, first_record + n_records) of a retained frame; the kept (and
  * trimmed) records are left as FASTQ text in device memory, fetched with fqg_records_filter_output.
- * read_len is strlen(seq) with its '\n', as in the reference (src/fastq.c:259). */
+ * read_len is strlen(seq) with its '\n', as in the reference (src/fastq.c:259).
+ * fqg_records_filter_info tells how the last call ran: info[0] tiles, info[1] tiles that took the direct path (they do
+ * not fit LDS, or the image holds NUL bytes), info[2] wavefronts of the tile kernel, info[3] records per tile, info[4]
+ * and info[5] the bytes of LDS a tile has for its input span and for its output; zeros after a call without records. */
 typedef struct {
   int32_t mode;             /* FQG_FILTER_N or FQG_FILTER_POLY_AT (fqg_codes.h) */
   uint32_t max_n_percent;   /* FILTER_N: -n (0: any N drops the record); values above 100 count as 100 */
@@ -456,6 +459,7 @@ typedef struct {
 int fqg_records_filter(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_record, uint64_t n_records,
                        const fqg_filter_params *params, fqg_filter_result *out);
 int fqg_records_filter_output(fqg_ctx *ctx, void *host_dst, uint64_t nbytes);
+int fqg_records_filter_info(const fqg_ctx *ctx, uint64_t info[6]);
 
 /* ---- ordered gather of records (fastq_filterpair) -----------------------------------------------
  * The output side of fastq_filterpair (src/fastq_filterpair.c:150-216): records of a retained frame written in a

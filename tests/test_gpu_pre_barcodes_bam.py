@@ -65,8 +65,8 @@ def test_abi_out_sam_1_still_writes_sam_text():
             f.release()
 
 
-def _abi_other_tiles(lds):
-    e = dict(os.environ, FQGPU_BC_LDS=lds)
+def _abi_other_tiles(lds, **more):
+    e = dict(os.environ, FQGPU_BC_LDS=lds, **more) if lds else dict({k: v for k, v in os.environ.items() if k != "FQGPU_BC_LDS"}, **more)
     p = subprocess.run([sys.executable, "-m", "tests.pb_bam_cases"], cwd=REPO, env=e, capture_output=True, timeout=600)
     return p.returncode, p.stdout.decode(), p.stderr.decode()
 
@@ -81,6 +81,15 @@ def test_abi_records_at_other_tile_sizes(lds):
     assert out.strip(), err[-2000:]
     res = json.loads(out.strip().split("\n")[-1])
     assert res["lds"] == lds and res["cases"] == len(ABI_CASES)
+    assert res["failed"] == [] and rc == 0
+
+
+def test_abi_records_with_two_wavefronts_in_the_grid():
+    """every case once more with FQGPU_TILE_WAVES=2: a wavefront of the plan and of the emit kernel walks many tiles"""
+    rc, out, err = _abi_other_tiles(None, FQGPU_TILE_WAVES="2")
+    assert out.strip(), err[-2000:]
+    res = json.loads(out.strip().split("\n")[-1])
+    assert res["lds"] is None and res["cases"] == len(ABI_CASES)
     assert res["failed"] == [] and rc == 0
 
 

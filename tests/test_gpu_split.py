@@ -1,7 +1,7 @@
 """fqg_records_split (the de-interleave behind fastq_split_interleaved) against a plain Python de-interleave of the
-image's records and against fqg_records_gather with the even and the odd list.  FQGPU_SPLIT_T and FQGPU_BC_LDS are read
-once per process: every environment runs its cases in ONE child process (this file as a program), which prints a line
-per case and leaves with status 0 when all of them held."""
+image's records and against fqg_records_gather with the even and the odd list.  FQGPU_SPLIT_T, FQGPU_BC_LDS and
+FQGPU_TILE_WAVES are read once per process: every environment runs its cases in ONE child process (this file as a
+program), which prints a line per case and leaves with status 0 when all of them held."""
 import os
 import subprocess
 import sys
@@ -137,15 +137,18 @@ def child(group):
 
 # ---- the tests ---------------------------------------------------------------------------------------------------------
 GROUPS = {"default": {}, "T2": {"FQGPU_SPLIT_T": "2"}, "T8": {"FQGPU_SPLIT_T": "8"}, "T64": {"FQGPU_SPLIT_T": "64"},
-          "lds4096": {"FQGPU_BC_LDS": "4096"}}
+          "lds4096": {"FQGPU_BC_LDS": "4096"},
+          # the cases of "default" with two wavefronts in k_split_emit_tile's grid: each walks many tiles (tile after next,
+          # the prefetch for it, a direct tile in between)
+          "default@waves2": {"FQGPU_TILE_WAVES": "2"}}
 
 
 @pytest.mark.parametrize("group", sorted(GROUPS))
 def test_records_split(group):
-    env = {k: v for k, v in os.environ.items() if k not in ("FQGPU_SPLIT_T", "FQGPU_BC_LDS")}
+    env = {k: v for k, v in os.environ.items() if k not in ("FQGPU_SPLIT_T", "FQGPU_BC_LDS", "FQGPU_TILE_WAVES")}
     env.update(GROUPS[group])
     env["PYTHONPATH"] = REPO + os.pathsep + env.get("PYTHONPATH", "")
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), group], cwd=REPO, env=env, capture_output=True, timeout=300)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), group.split("@")[0]], cwd=REPO, env=env, capture_output=True, timeout=300)
     out = p.stdout.decode("latin-1") + p.stderr.decode("latin-1")[-3000:]
     print(out)
     assert p.returncode == 0, out
