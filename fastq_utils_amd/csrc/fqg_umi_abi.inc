@@ -61,6 +61,9 @@ int fqg_bam_index_records(const void* stream, uint64_t nbytes, uint64_t* offsets
   return (offsets && k > cap) ? FQG_ERR_ARG : 0;
 }
 
+#define UMI_NEED(ptr) \
+  if (!(ptr)) return fail(c, FQG_ERR_NOMEM, "fqg_umi_count: device allocation failed")
+
 extern "C++" {
 namespace {
 // Device memory of one call.  A call makes about fifty allocations; hipMalloc / hipFree for each of
@@ -92,20 +95,23 @@ struct Scratch {
     return (T*)p;
   }
 };
-// Grows the arena to what the call that just ended asked for - at the END of that call (declared before the
-// call's Scratch, so destroyed after it), unless a deferred state still lives in the arena.  The next call then
-// starts with its memory in place.
+// Moves the arena to what the calls so far asked for - only while nothing lives in it: no Scratch of a running
+// call, no deferred state.  (When the allocation fails the arena stays empty: hipMalloc per buffer.)  ArenaGrow does so
+// at the END of the call that asked for more (declared before what holds the call's Scratch, so destroyed after it):
+// the next call then starts with its memory in place.
+int arena_regrow(fqg_ctx* c) {
+  if (c->umi_state || c->umi_arena_wanted <= c->umi_arena.cap) return 0;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  release(c->umi_arena);
+  (void)ensure(c, c->umi_arena, c->umi_arena_wanted + (c->umi_arena_wanted >> 3));
+  return 0;
+}
 struct ArenaGrow {
   fqg_ctx* c;
-  ~ArenaGrow() {
-    if (c->umi_state || c->umi_arena_wanted <= c->umi_arena.cap) return;
-    (void)hipStreamSynchronize(c->stream);
-    release(c->umi_arena);
-    (void)ensure(c, c->umi_arena, c->umi_arena_wanted + (c->umi_arena_wanted >> 3));  // (on failure: hipMalloc per buffer)
-  }
+  ~ArenaGrow() { (void)arena_regrow(c); }
 };
-struct UmiState {  // what fqg_umi_emit needs from the counting step
-  Scratch* scratch = nullptr;
+struct UmiState {  // what fqg_umi_emit needs from the counting step, with the scratch memory it points into
+  std::unique_ptr<Scratch> scratch;
   EmitArgs A;
   UmiCall* d_call = nullptr;
   unsigned long long* d_tot = nullptr;
@@ -116,10 +122,7 @@ struct UmiState {  // what fqg_umi_emit needs from the counting step
   uint64_t n_records = 0, n_features = 0;
 };
 void umi_drop_state(fqg_ctx* c) {
-  UmiState* us = (UmiState*)c->umi_state;
-  if (!us) return;
-  delete us->scratch;
-  delete us;
+  delete (UmiState*)c->umi_state;
   c->umi_state = nullptr;
 }
 uint64_t pow2_at_least(uint64_t v) {
@@ -128,11 +131,759 @@ uint64_t pow2_at_least(uint64_t v) {
   return p;
 }
 unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
+
+// What the phases of one fqg_umi_count call share: what the caller passed, then what each phase settles for the
+// ones behind it.  Lives for the call; the Scratch moves on to the UmiState (umi_keep_state).
+struct UmiCount {
+  uint64_t nbytes;
+  uint32_t n;
+  const fqg_umi_params* prm;
+  fqg_umi_result* out;
+  std::unique_ptr<Scratch> S;
+  hipStream_t st;
+  // inputs and parameters on the device (the host copies of the whitelists live until the uploads have run)
+  const uint8_t* d_buf = nullptr;
+  const unsigned long long* d_off = nullptr;
+  double mean_record = 0;
+  std::vector<unsigned long long> ku_sorted, kc_sorted;
+  std::vector<uint32_t> ku_order;
+  UmiParams P{};
+  UmiCall *d_call = nullptr, h_call{};
+  UmiRec* d_rec = nullptr;
+  uint8_t* d_stage = nullptr;
+  // the tables of UMIs, cells and feature names (cap slots each), the slot of every record in them, the dense ids
+  uint64_t cap = 0;
+  KeyTable U{}, C{};
+  NameTable F{};
+  uint32_t *d_uslot = nullptr, *d_cslot = nullptr, *d_fslot = nullptr;
+  Prefix pu{}, pc{}, pf{};
+  UmiIds ids{};
+  unsigned long long *d_tot = nullptr, h_tot[8] = {};
+  uint32_t* d_cell_first = nullptr;  // sorted mode: first record of every cell
+  // known after the first synchronisation
+  bool stopped = false;  // the reference ends at a record of this call: `out` says which, nothing is counted
+  uint64_t n_cells = 0, n_feat = 0;
+  bool unit = false, by_cells = false;
+  // what counting leaves for the output step (either path)
+  PairTable Pt{};
+  uint8_t* d_new = nullptr;
+  uint32_t *d_cell_reads = nullptr, *d_cell_umis = nullptr, *d_cell_pairs = nullptr, *d_pair_of = nullptr;
+  float *d_pair_reads = nullptr, *d_pair_umis = nullptr, *d_cellf_reads = nullptr, *d_cellf_umis = nullptr;
+  unsigned long long *d_cloc = nullptr, *d_cspan = nullptr;
+  uint64_t n_pairs = 0;
+  const uint8_t* d_feat_replayed = nullptr;  // (null: no set was replayed)
+  template <class T>
+  T* get(uint64_t count, int fill = -1) { return S->get<T>(count, fill); }
+};
+
+// phase 1: the stream and the record offsets where the kernels read them, for the three kinds of `mem`; the mean record
+// (the index on the device: the header in front of the first record is small beside the records, and this call
+// always gets the whole stream - no first offset is fetched.  fqg_bam_add_tags / fqg_bam2fastq do fetch it, eight
+// bytes and a synchronisation: bam2fastq hands a later PIECE over from byte 0, where nbytes / n is far off)
+int umi_inputs(fqg_ctx* c, UmiCount& u, const void* stream, int mem, const uint64_t* offsets) {
+  u.mean_record = mem == FQG_MEM_DEVICE_INDEXED ? (double)u.nbytes / (double)u.n : (double)(u.nbytes - offsets[0]) / (double)u.n;
+  if (mem == FQG_MEM_HOST) {
+    uint8_t* p = u.get<uint8_t>(u.nbytes + 16);
+    UMI_NEED(p);
+    HIP_TRY(c, hipMemcpyAsync(p, stream, u.nbytes, hipMemcpyHostToDevice, u.st));
+    u.d_buf = p;
+  } else u.d_buf = (const uint8_t*)stream;
+  if (mem == FQG_MEM_DEVICE_INDEXED) u.d_off = reinterpret_cast<const unsigned long long*>(offsets);  // (the caller's, in HBM)
+  else {
+    unsigned long long* p = u.get<unsigned long long>(u.n);
+    UMI_NEED(p);
+    HIP_TRY(c, hipMemcpyAsync(p, offsets, (size_t)u.n * 8, hipMemcpyHostToDevice, u.st));
+    u.d_off = p;
+  }
+  return 0;
+}
+
+// phase 2: the parameters as the kernels take them, the whitelists and the UMI table uploaded, the call's counters
+int umi_parameters(fqg_ctx* c, UmiCount& u) {
+  const fqg_umi_params* prm = u.prm;
+  UmiParams& P = u.P;
+  memcpy(P.feat_tag, prm->feat_tag, 2);
+  memcpy(P.cell_tag, prm->cell_tag, 2);
+  memcpy(P.umi_tag, prm->umi_tag, 2);
+  P.sorted_by_cell = prm->sorted_by_cell;
+  P.uniq_mapped_only = prm->uniq_mapped_only;
+  P.max_cells = prm->max_cells;
+  P.max_features = prm->max_features;
+  P.min_reads = prm->min_reads;
+  P.min_umis = prm->min_umis;
+  // whitelists: the UMI list numbers its distinct entries 1..K in file order (load_whitelist :543-579 with
+  // map = umis_map); the cell list is a plain set
+  if (prm->known_umis) {
+    P.have_known_umis = 1;
+    std::vector<std::pair<unsigned long long, uint32_t>> v;
+    for (uint64_t i = 0; i < prm->n_known_umis; ++i) {
+      const unsigned long long x = prm->known_umis[i];
+      bool dup = false;
+      for (auto& e : v) dup |= e.first == x;  // (whitelists are small; keep file order exact)
+      if (!dup) v.push_back({x, (uint32_t)v.size()});
+    }
+    std::sort(v.begin(), v.end());
+    for (auto& e : v) {
+      u.ku_sorted.push_back(e.first);
+      u.ku_order.push_back(e.second);
+    }
+    P.n_known_umis = (uint32_t)v.size();
+    unsigned long long* a = u.get<unsigned long long>(v.size());
+    uint32_t* b = u.get<uint32_t>(v.size());
+    UMI_NEED(a && b);
+    if (!v.empty()) {
+      HIP_TRY(c, hipMemcpyAsync(a, u.ku_sorted.data(), v.size() * 8, hipMemcpyHostToDevice, u.st));
+      HIP_TRY(c, hipMemcpyAsync(b, u.ku_order.data(), v.size() * 4, hipMemcpyHostToDevice, u.st));
+    }
+    P.known_umis_sorted = a;
+    P.known_umis_order = b;
+  }
+  if (prm->known_cells) {
+    P.have_known_cells = 1;
+    u.kc_sorted.assign(prm->known_cells, prm->known_cells + prm->n_known_cells);
+    std::sort(u.kc_sorted.begin(), u.kc_sorted.end());
+    u.kc_sorted.erase(std::unique(u.kc_sorted.begin(), u.kc_sorted.end()), u.kc_sorted.end());
+    P.n_known_cells = (uint32_t)u.kc_sorted.size();
+    unsigned long long* a = u.get<unsigned long long>(u.kc_sorted.size());
+    UMI_NEED(a);
+    if (!u.kc_sorted.empty())
+      HIP_TRY(c, hipMemcpyAsync(a, u.kc_sorted.data(), u.kc_sorted.size() * 8, hipMemcpyHostToDevice, u.st));
+    P.known_cells_sorted = a;
+  }
+  if (prm->umi_table_keys) {
+    if (!prm->umi_table_ids || prm->n_umi_table >= 0xFFFFFFFFull) return fail(c, FQG_ERR_ARG, "fqg_umi_count: umi_table_ids / n_umi_table");
+    unsigned long long* a = u.get<unsigned long long>(prm->n_umi_table);
+    uint32_t* b = u.get<uint32_t>(prm->n_umi_table);
+    UMI_NEED(a && b);
+    if (prm->n_umi_table) {
+      HIP_TRY(c, hipMemcpyAsync(a, prm->umi_table_keys, (size_t)prm->n_umi_table * 8, hipMemcpyHostToDevice, u.st));
+      HIP_TRY(c, hipMemcpyAsync(b, prm->umi_table_ids, (size_t)prm->n_umi_table * 4, hipMemcpyHostToDevice, u.st));
+    }
+    P.umi_table_keys = a;
+    P.umi_table_ids = b;
+    P.n_umi_table = (uint32_t)prm->n_umi_table;
+  }
+  u.d_call = u.get<UmiCall>(1);
+  UMI_NEED(u.d_call);
+  memset(&u.h_call, 0, sizeof(u.h_call));
+  u.h_call.first_key = ~0ull;
+  u.h_call.all_unit = 1;
+  HIP_TRY(c, hipMemcpyAsync(u.d_call, &u.h_call, sizeof(u.h_call), hipMemcpyHostToDevice, u.st));
+  return 0;
+}
+
+// phase 3: the fields of every record (records per tile and the LDS area: what the mean record needs), then the key
+// tables with every record's UMI, cell and feature name inserted
+int umi_parse_and_insert(fqg_ctx* c, UmiCount& u) {
+  u.d_rec = u.get<UmiRec>(u.n);
+  u.d_stage = u.get<uint8_t>(u.n);
+  UMI_NEED(u.d_rec && u.d_stage);
+  {
+    ProfScope ps(c, "k_umi_parse");
+    const double mean = u.mean_record;
+    const uint32_t T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)kParseStage - 64.0) / (1.1 * mean + 1.0))));
+    const uint32_t lds = std::min<uint32_t>((uint32_t)kParseStage, ((uint32_t)(1.15 * mean * T) + 256u + 15u) & ~15u);
+    hipLaunchKernelGGL(k_umi_parse, dim3((u.n + T - 1) / T), dim3(kWave), lds + 32, u.st, u.d_buf, u.nbytes, u.d_off, u.n, T, lds, u.P,
+                       u.d_rec, u.d_stage, u.d_call);
+  }
+  const uint64_t cap = u.cap = pow2_at_least(2ull * u.n);
+  {  // the seven arrays of the three tables start out all ones: one block, one fill
+    unsigned long long* blk = u.get<unsigned long long>(6 * cap + (3 * cap + 1) / 2 + 8, 0xFF);
+    UMI_NEED(blk);
+    u.U.keys = blk;
+    u.C.keys = blk + cap;
+    u.F.slots = blk + 2 * cap;
+    u.F.words = blk + 3 * cap;
+    uint32_t* firsts32 = reinterpret_cast<uint32_t*>(blk + 6 * cap);
+    u.U.first = firsts32;
+    u.C.first = firsts32 + cap;
+    u.F.first = firsts32 + 2 * cap;
+  }
+  u.U.mask = u.C.mask = u.F.mask = cap - 1;
+  u.d_uslot = u.get<uint32_t>(u.n);
+  u.d_cslot = u.get<uint32_t>(u.n);
+  u.d_fslot = u.get<uint32_t>(u.n);
+  UMI_NEED(u.d_uslot && u.d_cslot && u.d_fslot);
+  ProfScope ps(c, "k_umi_insert");
+  hipLaunchKernelGGL(k_umi_insert, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.d_buf, u.nbytes, u.n, u.P, (const UmiRec*)u.d_rec,
+                     u.d_stage, u.U, u.C, u.F, u.d_uslot, u.d_cslot, u.d_fslot, u.d_call, measure_int("FQGPU_UMI_INSERT_ABL"));
+  return 0;
+}
+
+// phase 4: dense ids in order of first appearance: flags on the record axis + exclusive prefix, for the three tables
+int umi_dense_ids(fqg_ctx* c, UmiCount& u) {
+  const uint64_t cap = u.cap, nb = scan64_spans(u.n);
+  uint32_t* d_flag[3];
+  unsigned long long *d_loc[3], *d_span[3];
+  u.d_tot = u.get<unsigned long long>(8);
+  UMI_NEED(u.d_tot);
+  const uint32_t* firsts[3] = {u.U.first, u.C.first, u.F.first};
+  {
+    ProfScope ps(c, "k_umi_ids");
+    // the three flag arrays are one block (one fill), the three scans one launch each
+    uint32_t* flags3 = u.get<uint32_t>(3ull * u.n + 64, 0);
+    UMI_NEED(flags3);
+    Scan3 t3;
+    Scan64 s3{};
+    for (int k = 0; k < 3; ++k) {
+      d_flag[k] = flags3 + (uint64_t)k * u.n;
+      d_loc[k] = u.get<unsigned long long>(u.n);
+      d_span[k] = u.get<unsigned long long>(nb);
+      UMI_NEED(d_loc[k] && d_span[k]);
+      t3.first[k] = firsts[k];
+      s3.in[k] = t3.flag[k] = d_flag[k];
+      s3.local[k] = d_loc[k];
+      s3.sums[k] = d_span[k];
+    }
+    s3.total = u.d_tot;
+    hipLaunchKernelGGL(k_umi_flag3, dim3(blocks_for(cap), 3), dim3(kBlock), 0, u.st, t3, cap);
+    scan64(c, s3, 3, u.n);
+  }
+  u.pu = Prefix{d_loc[0], d_span[0]};
+  u.pc = Prefix{d_loc[1], d_span[1]};
+  u.pf = Prefix{d_loc[2], d_span[2]};
+  u.ids.umi = u.get<uint32_t>(u.n);
+  u.ids.cell = u.get<uint32_t>(u.n);
+  u.ids.feat = u.get<uint32_t>(u.n);
+  UMI_NEED(u.ids.umi && u.ids.cell && u.ids.feat);
+  {
+    ProfScope ps(c, "k_umi_assign");
+    hipLaunchKernelGGL(k_umi_assign, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, u.P, (const UmiRec*)u.d_rec,
+                       (const uint8_t*)u.d_stage, u.U, u.C, u.F, (const uint32_t*)u.d_uslot, (const uint32_t*)u.d_cslot,
+                       (const uint32_t*)u.d_fslot, u.pu, u.pc, u.pf, (const uint32_t*)d_flag[1], u.ids, u.d_call);
+  }
+  // sorted mode: first record and size of every cell (the per-cell counting path works on record ranges) - launched
+  // before the host has seen the number of cells (at most n: the arrays are sized for that, the kernels read the
+  // count from the device), so that ONE synchronisation brings back everything the host decides on
+  if (u.prm->sorted_by_cell) {
+    u.d_cell_first = u.get<uint32_t>((uint64_t)u.n + 2);
+    UMI_NEED(u.d_cell_first);
+    ProfScope ps(c, "k_umi_cell_first");
+    hipLaunchKernelGGL(k_umi_cell_first, dim3(blocks_for(cap)), dim3(kBlock), 0, u.st, cap, u.C, u.pc, u.n, u.d_cell_first);
+    hipLaunchKernelGGL(k_umi_cell_sizes, dim3(blocks_for((uint64_t)u.n + 1)), dim3(kBlock), 0, u.st,
+                       (const unsigned long long*)u.d_tot, u.n, u.d_cell_first, u.d_call);
+  }
+  return 0;
+}
+
+// phase 5: the one synchronisation in front of counting, and what the host decides with it: the tables held
+// everything, the numbers of cells and features, the first finding (u.stopped), which counting path
+int umi_first_results(fqg_ctx* c, UmiCount& u) {
+  fqg_umi_result* out = u.out;
+  UmiCall& h_call = u.h_call;
+  HIP_TRY(c, hipMemcpyAsync(&h_call, u.d_call, sizeof(h_call), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipMemcpyAsync(u.h_tot, u.d_tot, sizeof(u.h_tot), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  if (h_call.table_full & 2u) return fail(c, FQG_ERR_ARG, "fqg_umi_count: a UMI of the call is missing from umi_table_keys");
+  if (h_call.table_full) return fail(c, FQG_ERR_STATE, "fqg_umi_count: hash table full");
+  for (int k = 0; k < 64; ++k) h_call.n_tags += h_call.spread[0][k];
+  out->n_tags_found = h_call.n_tags;
+  if (u.prm->defer_output) {  // the UMIs of the call that are not whitelisted, in order of first appearance (fqg_umi_umis: shards)
+    int rc;
+    c->umi_n_umis = u.h_tot[0];
+    if ((rc = ensure(c, c->umi_umis, (size_t)std::max<uint64_t>(u.h_tot[0], 1) * 8))) return rc;
+    hipLaunchKernelGGL(k_umi_export_cells, dim3(blocks_for(u.cap)), dim3(kBlock), 0, u.st, u.cap, u.U, u.pu, (unsigned long long*)c->umi_umis.p);
+  }
+  out->n_umis_discarded = h_call.n_umis_disc;
+  out->n_cells_discarded = h_call.n_cells_disc;
+  out->n_cells = u.n_cells = u.h_tot[1];
+  out->n_features = u.n_feat = u.h_tot[2];
+  if (h_call.first_key != ~0ull) {
+    out->code = (int32_t)(h_call.first_key & 0xFF);
+    out->record = h_call.first_key >> 8;
+    const uint32_t* src = out->code == FQG_E_UMI_TOO_MANY_UMIS ? u.ids.umi
+                          : out->code == FQG_E_UMI_TOO_MANY_FEATURES ? u.ids.feat : u.ids.cell;
+    uint32_t v = 0;
+    HIP_TRY(c, hipMemcpy(&v, src + out->record, 4, hipMemcpyDeviceToHost));
+    out->aux = v;
+    // counters as they stood when the reference stopped are not reproduced: it prints none of them
+    u.stopped = true;
+    return 0;
+  }
+  u.unit = h_call.all_unit != 0;
+  // CR-sorted input with unit increments: one workgroup per cell, LDS (fqg_umi_cell_kernels.hip).  Anything else -
+  // unsorted mode, fractional increments, features or cells beyond the key's bit fields - takes the hash tables.
+  static const bool force_hash = getenv("FQGPU_UMI_HASH_PATH") != nullptr;
+  u.by_cells = u.prm->sorted_by_cell && u.unit && !force_hash && u.n_feat < (1ull << kCellFeatBits) &&
+               h_call.max_cell_records < (1u << kCellIdxBits) && u.n_cells > 0;
+  return 0;
+}
+
+// ---- the RL_Tree replay: the reference's UMI container where it is not a set (fqg_umi_rl_kernels.hip, fqg_rl_sim.h) ----
+// Both counting paths come to it with the runs and the list of flagged ones on the device, RlCall fetched and the
+// flagged runs' lengths on the host.  What the paths differ in they write into A themselves: `order`, the by_cell fields.
+struct RlReplay {
+  uint32_t n_flagged = 0, n_chain = 0;
+  RlRuns runs{};
+  // the chain - the runs a replayed set may look back into, by (feature, cell): keys and runs, unsorted and sorted
+  unsigned long long *ck = nullptr, *cko = nullptr;
+  uint32_t *cv = nullptr, *cvo = nullptr, *pos = nullptr;
+  uint32_t *d_flagged = nullptr, *d_fk0 = nullptr, *d_flen = nullptr, *d_foff = nullptr, *d_fext = nullptr;
+  RlCall *d_rl = nullptr, h_rl{};
+  std::vector<uint32_t> h_len, h_off;  // per flagged run: records, first node in the arena (alive until the fetch)
+  RlReplayArgs A{};
+};
+int rl_chain_get(fqg_ctx* c, UmiCount& u, RlReplay& r, uint32_t n_runs) {
+  r.ck = u.get<unsigned long long>(n_runs);
+  r.cko = u.get<unsigned long long>(n_runs);
+  r.cv = u.get<uint32_t>(n_runs);
+  r.cvo = u.get<uint32_t>(n_runs);
+  r.pos = u.get<uint32_t>(n_runs);
+  UMI_NEED(r.ck && r.cko && r.cv && r.cvo && r.pos);
+  r.n_chain = n_runs;
+  return 0;
+}
+
+// where every flagged run keeps its final array: at most 1 + 8 nodes per record of the run, 128-byte aligned
+int rl_lay_out(fqg_ctx* c, UmiCount& u, RlReplay& r) {
+  const uint32_t cap_nodes = r.A.cap = (1u + 8u * r.h_rl.max_flagged_len + 2048u + 63u) & ~63u;
+  r.A.mcap = 64;
+  while (r.A.mcap < r.h_rl.max_len) r.A.mcap <<= 1;  // (a power of two: the member sort pads to one)
+  uint64_t arena_nodes = 0;
+  r.h_off.resize(r.n_flagged);
+  for (uint32_t f = 0; f < r.n_flagged; ++f) {
+    r.h_off[f] = (uint32_t)arena_nodes;
+    arena_nodes += ((uint64_t)std::min<uint64_t>(cap_nodes, 1ull + 8ull * r.h_len[f]) + 63u) & ~63ull;
+    if (arena_nodes >= 0xFFFFFFFFull) return fail(c, FQG_ERR_STATE, "fqg_umi_count: too many replayed UMI sets");
+  }
+  r.A.arena = u.get<uint16_t>(arena_nodes + 64);
+  UMI_NEED(r.A.arena);
+  HIP_TRY(c, hipMemcpyAsync(r.d_foff, r.h_off.data(), (size_t)r.n_flagged * 4, hipMemcpyHostToDevice, u.st));
+  return 0;
+}
+
+// the order of the replay: the chain sorted by (feature, cell), the flagged runs by their place in it (inside the caller's "k_rl_chains")
+int rl_sort_chains(fqg_ctx* c, UmiCount& u, RlReplay& r) {
+  const uint32_t nf = r.n_flagged;
+  uint32_t* ik = u.get<uint32_t>(nf);
+  uint32_t* iko = u.get<uint32_t>(nf);
+  uint32_t* iv = u.get<uint32_t>(nf);
+  uint32_t* ivo = u.get<uint32_t>(nf);
+  UMI_NEED(ik && iko && iv && ivo);
+  size_t tb = 0, tb2 = 0;
+  HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tb, r.ck, r.cko, r.cv, r.cvo, (size_t)r.n_chain, 0, 64, u.st));
+  HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tb2, ik, iko, iv, ivo, (size_t)nf, 0, 32, u.st));
+  void* tmp2 = u.get<uint8_t>(std::max(tb, tb2) + 16);
+  UMI_NEED(tmp2);
+  HIP_TRY(c, rocprim::radix_sort_pairs(tmp2, tb, r.ck, r.cko, r.cv, r.cvo, (size_t)r.n_chain, 0, 64, u.st));
+  hipLaunchKernelGGL(k_rl_positions, dim3(blocks_for(r.n_chain)), dim3(kBlock), 0, u.st, r.n_chain, (const uint32_t*)r.cvo, r.pos);
+  hipLaunchKernelGGL(k_rl_item_keys, dim3(blocks_for(nf)), dim3(kBlock), 0, u.st, nf, (const uint32_t*)r.d_flagged, (const uint32_t*)r.pos, ik, iv);
+  HIP_TRY(c, rocprim::radix_sort_pairs(tmp2, tb2, ik, iko, iv, ivo, (size_t)nf, 0, 32, u.st));
+  r.A.chain_runs = r.cvo;
+  r.A.chain_key = r.cko;
+  r.A.pos_of_run = r.pos;
+  r.A.items = ivo;
+  return 0;
+}
+
+// the arguments both paths share, the worker's arrays in LDS where they fit, the launch, RlCall and what `out` takes from it
+int rl_run(fqg_ctx* c, UmiCount& u, RlReplay& r) {
+  RlReplayArgs& A = r.A;
+  A.flagged = r.d_flagged;
+  A.n_items = r.n_flagged;
+  A.runs = r.runs;
+  A.umi_id = u.ids.umi;
+  A.cell_id = u.ids.cell;
+  A.is_new = u.d_new;
+  A.flag_k0 = r.d_fk0;
+  A.flag_off = r.d_foff;
+  A.flag_ext = r.d_fext;
+  A.pair_umis = u.Pt.umis;
+  A.cell_umis = u.d_cell_umis;
+  A.n_new_spread = &u.d_call->spread[2][0];
+  A.call = r.d_rl;
+  const uint64_t work_bytes = rl_work_bytes(A.cap, A.mcap);
+  const unsigned grid = (unsigned)std::min<uint32_t>(A.n_items, 1024u);
+  A.in_lds = work_bytes <= 150u * 1024u;
+  if (!A.in_lds) {
+    A.scratch_stride = (work_bytes + 255) & ~255ull;
+    A.scratch = u.get<uint8_t>(A.scratch_stride * grid);
+    UMI_NEED(A.scratch);
+  }
+  if (A.in_lds && work_bytes > 48u * 1024u)  // (raised per device and kernel, for the whole process: raise_dynamic_lds)
+    NEED(raise_dynamic_lds(c, reinterpret_cast<const void*>(k_rl_replay), (size_t)work_bytes));
+  {
+    ProfScope ps(c, "k_rl_replay");
+    hipLaunchKernelGGL(k_rl_replay, dim3(grid), dim3(kWave), A.in_lds ? (size_t)work_bytes : 0, u.st, A);
+  }
+  HIP_TRY(c, hipMemcpyAsync(&r.h_rl, r.d_rl, sizeof(r.h_rl), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  HIP_TRY(c, hipGetLastError());
+  u.out->rl_changed = r.h_rl.changed;
+  u.out->rl_undefined = r.h_rl.undefined;
+  u.out->rl_unresolved = r.h_rl.overflow ? 1 : 0;
+  return 0;
+}
+
+// ---- counting through hash tables: unsorted mode, fractional increments, ids beyond the per-cell key's bit fields ----
+// the runs of the pair order (one per pair), the ones whose UMIs the reference's tree does not keep as a set, their replay
+int table_replay(fqg_ctx* c, UmiCount& u, const uint32_t* ko, const uint32_t* io) {
+  RlReplay r;
+  r.d_rl = u.get<RlCall>(1, 0);
+  uint32_t* d_sflag = u.get<uint32_t>(u.n);
+  unsigned long long* d_rloc = u.get<unsigned long long>(u.n);
+  unsigned long long* d_rspan = u.get<unsigned long long>(scan64_spans(u.n));
+  r.runs.start = u.get<uint32_t>(u.n);
+  r.runs.len = u.get<uint32_t>(u.n);
+  r.runs.pslot = u.get<uint32_t>(u.n);
+  r.runs.flag = u.get<uint32_t>(u.n, 0xFF);
+  r.d_flagged = u.get<uint32_t>(u.n);
+  r.d_fk0 = u.get<uint32_t>(u.n);
+  UMI_NEED(r.d_rl && d_sflag && d_rloc && d_rspan && r.runs.start && r.runs.len && r.runs.pslot && r.runs.flag && r.d_flagged && r.d_fk0);
+  {
+    ProfScope ps(c, "k_rl_detect");
+    hipLaunchKernelGGL(k_rl_starts, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, ko, d_sflag);
+    scan64(c, d_sflag, d_rloc, d_rspan, u.d_tot + 6, u.n);
+    hipLaunchKernelGGL(k_rl_detect, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, ko, io, (const uint32_t*)d_sflag, Prefix{d_rloc, d_rspan},
+                       (const uint32_t*)u.ids.umi, (const uint8_t*)u.d_new, r.runs, r.d_flagged, r.d_fk0, r.d_rl);
+  }
+  HIP_TRY(c, hipMemcpyAsync(&r.h_rl, r.d_rl, sizeof(r.h_rl), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipMemcpyAsync(u.h_tot, u.d_tot, sizeof(u.h_tot), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  const uint32_t n_runs = (uint32_t)u.h_tot[6], n_flagged = r.n_flagged = r.h_rl.n_flagged;
+  if (n_flagged) {
+    uint8_t* d_feat_flag = u.get<uint8_t>((uint64_t)u.n_feat + 2, 0);  // which features these sets belong to (fqg_umi_replayed_features)
+    UMI_NEED(d_feat_flag);
+    hipLaunchKernelGGL(k_umi_mark_replayed, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, u.st, n_flagged,
+                       (const uint32_t*)r.d_flagged, (const uint32_t*)r.runs.pslot, u.Pt, d_feat_flag);
+    u.d_feat_replayed = d_feat_flag;
+    r.h_len.resize(n_flagged);
+    r.d_flen = u.get<uint32_t>(n_flagged);
+    r.d_foff = u.get<uint32_t>(n_flagged);
+    r.d_fext = u.get<uint32_t>(n_flagged, 0);
+    UMI_NEED(r.d_flen && r.d_foff && r.d_fext);
+    hipLaunchKernelGGL(k_rl_flag_lens, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, u.st, n_flagged,
+                       (const uint32_t*)r.d_flagged, (const uint32_t*)r.runs.len, r.d_flen);
+    HIP_TRY(c, hipMemcpyAsync(r.h_len.data(), r.d_flen, (size_t)n_flagged * 4, hipMemcpyDeviceToHost, u.st));
+    HIP_TRY(c, hipStreamSynchronize(u.st));
+    NEED(rl_lay_out(c, u, r));
+    if (u.prm->sorted_by_cell) {
+      ProfScope ps(c, "k_rl_chains");
+      NEED(rl_chain_get(c, u, r, n_runs));
+      hipLaunchKernelGGL(k_rl_chain_keys, dim3(blocks_for(n_runs)), dim3(kBlock), 0, u.st, n_runs,
+                         (const uint32_t*)r.runs.pslot, u.Pt, r.ck, r.cv);
+      NEED(rl_sort_chains(c, u, r));
+    }  // else: every (cell, feature) has a tree of its own (src/bam_umi_count.c:468-479), no history
+    r.A.order = io;
+    NEED(rl_run(c, u, r));
+  }
+  if (getenv("FQGPU_RL_DEBUG"))
+    fprintf(stderr, "[rl] runs %u flagged %u max_len %u max_flagged_len %u overwrites %u lookback_runs %u changed %u undefined %u "
+            "ticks(100MHz): replay %llu (build %llu loop %llu) lookback %llu store %llu\n", n_runs, n_flagged, r.h_rl.max_len, r.h_rl.max_flagged_len,
+            r.h_rl.overwrites, r.h_rl.lookback_runs, r.h_rl.changed, (unsigned)r.h_rl.undefined, r.h_rl.clk_replay, r.h_rl.clk_build, r.h_rl.clk_loop, r.h_rl.clk_lookback, r.h_rl.clk_store);
+  u.out->rl_replayed = n_flagged;
+  return 0;
+}
+
+// phase 6, table path: (cell, feature) pairs and the (pair, UMI) set - reads and new UMIs per pair and cell; the records sorted
+// by (pair slot, record index) for the replay and the ordered float sums; the float32 counters; the pairs grouped by cell
+int umi_count_tables(fqg_ctx* c, UmiCount& u) {
+  const uint64_t cap = u.cap, n_cells = u.n_cells;
+  u.Pt.t.s = u.get<KeySlot>(u.cap, 0xFF);
+  u.Pt.t.mask = u.cap - 1;
+  u.Pt.reads = u.get<uint32_t>(u.cap, 0);
+  u.Pt.umis = u.get<uint32_t>(u.cap, 0);
+  SlotTable T;
+  T.s = u.get<KeySlot>(u.cap, 0xFF);
+  T.mask = u.cap - 1;
+  uint32_t* d_pslot = u.get<uint32_t>(u.n);
+  uint32_t* d_tslot = u.get<uint32_t>(u.n);
+  u.d_new = u.get<uint8_t>(u.n);
+  u.d_cell_reads = u.get<uint32_t>(u.n_cells + 2, 0);
+  u.d_cell_umis = u.get<uint32_t>(u.n_cells + 2, 0);
+  UMI_NEED(u.Pt.t.s && u.Pt.reads && u.Pt.umis && T.s && d_pslot && d_tslot && u.d_new && u.d_cell_reads && u.d_cell_umis);
+  {
+    ProfScope ps(c, "k_umi_count");
+    hipLaunchKernelGGL(k_umi_count, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, u.n, u.ids, T, u.Pt, d_pslot, d_tslot, u.d_call);
+    hipLaunchKernelGGL(k_umi_new, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, (const uint32_t*)d_tslot,
+                       (const uint32_t*)d_pslot, T, u.Pt, u.ids, u.d_new, u.d_cell_reads, u.d_cell_umis, u.d_call);
+  }
+  uint32_t* kp = u.get<uint32_t>(u.n);
+  uint32_t* kc = u.get<uint32_t>(u.n);
+  uint32_t* ix = u.get<uint32_t>(u.n);
+  uint32_t* ko = u.get<uint32_t>(u.n);
+  uint32_t* io = u.get<uint32_t>(u.n);
+  UMI_NEED(kp && kc && ix && ko && io);
+  size_t sort_tmp_bytes = 0;
+  HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_tmp_bytes, kp, ko, ix, io, (size_t)u.n, 0, 32, u.st));
+  void* sort_tmp = u.get<uint8_t>(sort_tmp_bytes + 16);
+  UMI_NEED(sort_tmp);
+  bool sorted_by_pair = false;
+  if (!u.prm->strict_set || !u.unit) {
+    ProfScope ps(c, "k_umi_sort_pairs");
+    hipLaunchKernelGGL(k_umi_sort_keys, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, (const uint32_t*)d_tslot,
+                       (const uint32_t*)d_pslot, (const uint32_t*)u.ids.cell, kp, kc, ix);
+    HIP_TRY(c, rocprim::radix_sort_pairs(sort_tmp, sort_tmp_bytes, kp, ko, ix, io, (size_t)u.n, 0, 32, u.st));
+    sorted_by_pair = true;
+  }
+  if (!u.prm->strict_set) NEED(table_replay(c, u, ko, io));
+  // ---- float32 counters ----
+  u.d_pair_reads = u.get<float>(cap, 0);
+  u.d_pair_umis = u.get<float>(cap, 0);
+  u.d_cellf_reads = u.get<float>(n_cells + 2, 0);
+  u.d_cellf_umis = u.get<float>(n_cells + 2, 0);
+  UMI_NEED(u.d_pair_reads && u.d_pair_umis && u.d_cellf_reads && u.d_cellf_umis);
+  if (u.unit) {
+    ProfScope ps(c, "k_umi_sums");
+    hipLaunchKernelGGL(k_umi_unit_sums, dim3(blocks_for(cap)), dim3(kBlock), 0, u.st, cap, (const uint32_t*)u.Pt.reads,
+                       (const uint32_t*)u.Pt.umis, u.d_pair_reads, u.d_pair_umis);
+    hipLaunchKernelGGL(k_umi_unit_sums, dim3(blocks_for(n_cells + 1)), dim3(kBlock), 0, u.st, n_cells + 1,
+                       (const uint32_t*)u.d_cell_reads, (const uint32_t*)u.d_cell_umis, u.d_cellf_reads, u.d_cellf_umis);
+  } else {
+    // fractional increments (NH > 1, several genes): replay the additions in record order
+    ProfScope ps(c, "k_umi_sums_ordered");
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pass || !sorted_by_pair)
+        HIP_TRY(c, rocprim::radix_sort_pairs(sort_tmp, sort_tmp_bytes, pass ? kc : kp, ko, ix, io, (size_t)u.n, 0, 32, u.st));
+      hipLaunchKernelGGL(k_umi_sums_sorted, dim3(blocks_for(u.n)), dim3(kBlock), 0, u.st, u.n, (const uint32_t*)ko,
+                         (const uint32_t*)io, (const UmiRec*)u.d_rec, (const uint8_t*)u.d_new,
+                         pass ? u.d_cellf_reads : u.d_pair_reads, pass ? u.d_cellf_umis : u.d_pair_umis);
+    }
+    hipLaunchKernelGGL(k_umi_db_totals, dim3(1), dim3(64), 0, u.st, u.n, u.n, (const UmiRec*)u.d_rec, (const uint32_t*)d_tslot,
+                       (const uint8_t*)u.d_new, u.d_call, u.prm->db_start_reads, u.prm->db_start_umi,
+                       (uint32_t)std::min<uint64_t>(u.prm->db_skip, u.n));
+  }
+  u.d_cell_pairs = u.get<uint32_t>(n_cells + 2, 0);
+  uint32_t* d_cursor = u.get<uint32_t>(n_cells + 2, 0);
+  u.d_cloc = u.get<unsigned long long>(n_cells + 2);
+  u.d_cspan = u.get<unsigned long long>(scan64_spans(n_cells + 2));
+  UMI_NEED(u.d_cell_pairs && d_cursor && u.d_cloc && u.d_cspan);
+  {
+    ProfScope ps(c, "k_umi_pairs");
+    hipLaunchKernelGGL(k_umi_pairs_count, dim3(blocks_for(cap)), dim3(kBlock), 0, u.st, cap, u.Pt, u.d_cell_pairs);
+    scan64(c, u.d_cell_pairs, u.d_cloc, u.d_cspan, u.d_tot + 3, n_cells + 2);
+  }
+  HIP_TRY(c, hipMemcpyAsync(u.h_tot, u.d_tot, sizeof(u.h_tot), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  u.n_pairs = u.h_tot[3];
+  u.d_pair_of = u.get<uint32_t>(u.n_pairs);
+  UMI_NEED(u.d_pair_of);
+  if (u.n_pairs) {
+    ProfScope ps(c, "k_umi_pairs");
+    hipLaunchKernelGGL(k_umi_pairs_fill, dim3(blocks_for(cap)), dim3(kBlock), 0, u.st, cap, u.Pt, Prefix{u.d_cloc, u.d_cspan}, d_cursor, u.d_pair_of);
+  }
+  return 0;
+}
+
+// ---- counting by one workgroup per cell (fqg_umi_cell_kernels.hip): CR-sorted input, unit increments.  The pair
+// arrays are laid out per cell: the pairs of a cell start at its first record's index ----
+struct CellPairs {  // what the replay on (cell, feature) runs takes over from the counting kernel
+  uint32_t *d_pair_mem = nullptr, *d_members = nullptr, *d_slot_hit = nullptr, *d_flagged_slot = nullptr, *d_run_of_slot = nullptr;
+  RlCall* d_rl = nullptr;
+  uint32_t n_flagged = 0;
+};
+// the replay on (cell, feature) runs: every pair is a run; the chain holds the runs of the features that have a flagged one
+int cells_replay(fqg_ctx* c, UmiCount& u, const CellPairs& p) {
+  const uint32_t n_runs = (uint32_t)u.n_pairs, n_flagged = p.n_flagged;
+  RlReplay r;
+  r.n_flagged = n_flagged;
+  r.d_rl = p.d_rl;
+  r.runs.start = u.get<uint32_t>(n_runs);
+  r.runs.len = u.get<uint32_t>(n_runs);
+  r.runs.pslot = u.d_pair_of;
+  r.runs.flag = u.get<uint32_t>(n_runs, 0xFF);
+  uint32_t* d_run_feat = u.get<uint32_t>(n_runs);
+  uint32_t* d_run_mem = u.get<uint32_t>(n_runs);
+  uint32_t* d_run_nmem = u.get<uint32_t>(n_runs);
+  r.d_flagged = u.get<uint32_t>(n_flagged);
+  r.d_fk0 = u.get<uint32_t>(n_flagged);
+  r.d_flen = u.get<uint32_t>(n_flagged);
+  r.d_foff = u.get<uint32_t>(n_flagged);
+  r.d_fext = u.get<uint32_t>(n_flagged, 0);
+  UMI_NEED(r.runs.start && r.runs.len && r.runs.flag && d_run_feat && d_run_mem && d_run_nmem && r.d_flagged && r.d_fk0 && r.d_flen &&
+           r.d_foff && r.d_fext);
+  HIP_TRY(c, hipMemsetAsync(r.d_rl, 0, sizeof(RlCall), u.st));
+  uint8_t* d_feat_flag = u.get<uint8_t>((uint64_t)u.n_feat + 2, 0);
+  UMI_NEED(d_feat_flag);
+  NEED(rl_chain_get(c, u, r, n_runs));
+  u.d_feat_replayed = d_feat_flag;
+  {
+    ProfScope ps(c, "k_rl_detect");
+    hipLaunchKernelGGL(k_rl_cell_flags, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, u.st, n_flagged,
+                       (const uint32_t*)p.d_flagged_slot, (const uint32_t*)p.d_slot_hit, (const uint32_t*)p.d_run_of_slot,
+                       (const KeySlot*)u.Pt.t.s, (const uint32_t*)u.Pt.reads, r.runs, r.d_flagged, r.d_fk0, r.d_flen, d_feat_flag, r.d_rl);
+    hipLaunchKernelGGL(k_rl_cell_chain, dim3(blocks_for(n_runs)), dim3(kBlock), 0, u.st, n_runs, (const uint32_t*)u.d_pair_of,
+                       (const KeySlot*)u.Pt.t.s, (const uint8_t*)d_feat_flag, (const uint32_t*)u.d_cell_first, (const uint32_t*)p.d_pair_mem,
+                       (const uint32_t*)u.Pt.umis, r.runs, d_run_feat, d_run_mem, d_run_nmem, r.ck, r.cv, r.d_rl);
+  }
+  r.h_len.resize(n_flagged);
+  HIP_TRY(c, hipMemcpyAsync(r.h_len.data(), r.d_flen, (size_t)n_flagged * 4, hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipMemcpyAsync(&r.h_rl, r.d_rl, sizeof(r.h_rl), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  r.n_chain = r.h_rl.n_chain;
+  NEED(rl_lay_out(c, u, r));
+  {
+    ProfScope ps(c, "k_rl_chains");
+    NEED(rl_sort_chains(c, u, r));
+  }
+  r.A.by_cell = 1;
+  r.A.rec_feat = u.ids.feat;
+  r.A.run_feat = d_run_feat;
+  r.A.run_mem = d_run_mem;
+  r.A.run_nmem = d_run_nmem;
+  r.A.members = p.d_members;
+  NEED(rl_run(c, u, r));
+  if (getenv("FQGPU_RL_DEBUG"))
+    fprintf(stderr, "[rl/cells] runs %u flagged %u max_len %u max_flagged_len %u overwrites %u lookback_runs %u changed %u "
+            "ticks(100MHz): replay %llu (build %llu loop %llu) lookback %llu store %llu; slowest run: %llu ticks, %llu records, %llu inserts; most look-back (waiting included) in one run: %llu ticks\n", n_runs, n_flagged, r.h_rl.max_len, r.h_rl.max_flagged_len,
+            r.h_rl.overwrites, r.h_rl.lookback_runs, r.h_rl.changed, r.h_rl.clk_replay, r.h_rl.clk_build, r.h_rl.clk_loop, r.h_rl.clk_lookback, r.h_rl.clk_store, r.h_rl.clk_max >> 32, (r.h_rl.clk_max >> 16) & 0xFFFF, r.h_rl.clk_max & 0xFFFF, r.h_rl.clk_max_wait);
+  return 0;
+}
+
+// phase 6, per-cell path: the counting kernel; the pairs in compact order (they are grouped by cell already: a prefix over the
+// cells' pair counts); the replay; the float32 counters (the counts as floats, saturating like repeated += 1.0f)
+int umi_count_cells(fqg_ctx* c, UmiCount& u) {
+  CellPairs p;
+  const uint64_t slots = u.n, n_cells = u.n_cells;
+  u.Pt.t.s = u.get<KeySlot>(slots);
+  u.Pt.t.mask = 0;
+  u.Pt.reads = u.get<uint32_t>(slots);
+  u.Pt.umis = u.get<uint32_t>(slots);
+  p.d_pair_mem = u.get<uint32_t>(slots);
+  uint32_t* d_pair_pos = u.get<uint32_t>(slots);
+  p.d_members = u.get<uint32_t>(slots);
+  p.d_slot_hit = u.get<uint32_t>(slots, 0xFF);
+  p.d_flagged_slot = u.get<uint32_t>(slots);
+  p.d_run_of_slot = u.get<uint32_t>(slots);
+  u.d_new = u.get<uint8_t>(u.n);
+  u.d_cell_reads = u.get<uint32_t>(n_cells + 2, 0);
+  u.d_cell_umis = u.get<uint32_t>(n_cells + 2, 0);
+  u.d_cell_pairs = u.get<uint32_t>(n_cells + 2, 0);
+  u.d_cloc = u.get<unsigned long long>(n_cells + 2);
+  u.d_cspan = u.get<unsigned long long>(scan64_spans(n_cells + 2));
+  p.d_rl = u.get<RlCall>(1, 0);
+  UMI_NEED(u.Pt.t.s && u.Pt.reads && u.Pt.umis && p.d_pair_mem && d_pair_pos && p.d_members && p.d_slot_hit && p.d_flagged_slot &&
+           p.d_run_of_slot && u.d_new && u.d_cell_reads && u.d_cell_umis && u.d_cell_pairs && u.d_cloc && u.d_cspan && p.d_rl);
+  CellArgs CA;
+  memset(&CA, 0, sizeof(CA));
+  CA.n = u.n;
+  CA.n_cells = (uint32_t)n_cells;
+  CA.feat = u.ids.feat;
+  CA.umi = u.ids.umi;
+  CA.cell_first = u.d_cell_first;
+  CA.is_new = u.d_new;
+  CA.pair_key = u.Pt.t.s;
+  CA.pair_reads = u.Pt.reads;
+  CA.pair_umis = u.Pt.umis;
+  CA.pair_mem = p.d_pair_mem;
+  CA.pair_pos = d_pair_pos;
+  CA.members = p.d_members;
+  CA.cell_pairs = u.d_cell_pairs;
+  CA.cell_reads = u.d_cell_reads;
+  CA.cell_umis = u.d_cell_umis;
+  CA.slot_hit = p.d_slot_hit;
+  CA.flagged_slot = p.d_flagged_slot;
+  CA.rl = p.d_rl;
+  CA.call = u.d_call;
+  // LDS keys: the smallest power of two that holds the largest cell, up to 8192 (64 KiB); larger cells sort in memory
+  uint32_t lds_keys = 64;
+  while (lds_keys < u.h_call.max_cell_records && lds_keys < 8192u) lds_keys <<= 1;
+  CA.lds_keys = lds_keys;
+  if (u.h_call.max_cell_records > lds_keys) {
+    CA.big_keys = u.get<unsigned long long>(2ull * u.n + 128);
+    UMI_NEED(CA.big_keys);
+  }
+  if (lds_keys * 8u > 48u * 1024u) NEED(raise_dynamic_lds(c, reinterpret_cast<const void*>(k_umi_cells), (size_t)lds_keys * 8u));
+  {
+    ProfScope ps(c, "k_umi_cells");
+    hipLaunchKernelGGL(k_umi_cells, dim3((unsigned)n_cells), dim3(kBlock), (size_t)lds_keys * 8u, u.st, CA);
+  }
+  {
+    ProfScope ps(c, "k_umi_pairs");
+    scan64(c, u.d_cell_pairs, u.d_cloc, u.d_cspan, u.d_tot + 3, n_cells + 2);
+  }
+  RlCall h_rl;
+  HIP_TRY(c, hipMemcpyAsync(u.h_tot, u.d_tot, sizeof(u.h_tot), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipMemcpyAsync(&h_rl, p.d_rl, sizeof(h_rl), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  u.n_pairs = u.h_tot[3];
+  p.n_flagged = u.prm->strict_set ? 0u : h_rl.n_flagged;
+  u.d_pair_of = u.get<uint32_t>(u.n_pairs);
+  UMI_NEED(u.d_pair_of);
+  if (u.n_pairs) {
+    ProfScope ps(c, "k_umi_pairs");
+    hipLaunchKernelGGL(k_umi_cell_pairs_fill, dim3((unsigned)n_cells), dim3(kBlock), 0, u.st, (uint32_t)n_cells, (const uint32_t*)u.d_cell_first,
+                       (const uint32_t*)u.d_cell_pairs, Prefix{u.d_cloc, u.d_cspan}, u.d_pair_of, p.d_run_of_slot);
+  }
+  if (p.n_flagged) NEED(cells_replay(c, u, p));
+  u.out->rl_replayed = p.n_flagged;
+  u.d_pair_reads = u.get<float>(slots);
+  u.d_pair_umis = u.get<float>(slots);
+  u.d_cellf_reads = u.get<float>(n_cells + 2, 0);
+  u.d_cellf_umis = u.get<float>(n_cells + 2, 0);
+  UMI_NEED(u.d_pair_reads && u.d_pair_umis && u.d_cellf_reads && u.d_cellf_umis);
+  ProfScope ps(c, "k_umi_sums");
+  hipLaunchKernelGGL(k_umi_cell_unit_sums, dim3((unsigned)n_cells), dim3(kBlock), 0, u.st, (uint32_t)n_cells, (const uint32_t*)u.d_cell_first,
+                     (const uint32_t*)u.d_cell_pairs, (const uint32_t*)u.Pt.reads, (const uint32_t*)u.Pt.umis, u.d_pair_reads, u.d_pair_umis);
+  hipLaunchKernelGGL(k_umi_unit_sums, dim3(blocks_for(n_cells + 1)), dim3(kBlock), 0, u.st, n_cells + 1,
+                     (const uint32_t*)u.d_cell_reads, (const uint32_t*)u.d_cell_umis, u.d_cellf_reads, u.d_cellf_umis);
+  return 0;
+}
+
+// phase 7: what the output step needs, kept with the scratch memory it points into; names and cells in id order
+int umi_keep_state(fqg_ctx* c, UmiCount& u) {
+  UmiState* us = new UmiState();
+  us->scratch = std::move(u.S);
+  us->A.Pt = u.Pt;
+  us->A.start = Prefix{u.d_cloc, u.d_cspan};
+  us->A.cell_pairs = u.d_cell_pairs;
+  us->A.pair_of = u.d_pair_of;
+  us->A.pair_reads = u.d_pair_reads;
+  us->A.pair_umis = u.d_pair_umis;
+  us->A.cell_umis = u.d_cellf_umis;
+  us->A.P = u.P;
+  us->A.n_cells = (uint32_t)u.n_cells;
+  us->A.remap = nullptr;
+  us->A.pairs_by_feature = u.by_cells ? 1 : 0;
+  us->A.cell_offset = 0;
+  us->d_call = u.d_call;
+  us->d_tot = u.d_tot;
+  us->n_pairs = u.n_pairs;
+  us->rec_feat = u.ids.feat;
+  us->feat_replayed = u.d_feat_replayed;
+  us->n_records = u.n;
+  us->n_features = u.n_feat;
+  c->umi_state = us;
+  NEED(ensure(c, c->umi_names, (size_t)std::max<uint64_t>(u.n_feat, 1) * kFeatIdMaxLen));
+  NEED(ensure(c, c->umi_cells, (size_t)std::max<uint64_t>(u.n_cells, 1) * 8));
+  ProfScope ps(c, "k_umi_export");
+  hipLaunchKernelGGL(k_umi_export_features, dim3(blocks_for(u.cap)), dim3(kBlock), 0, u.st, u.d_buf, u.cap, u.F, u.pf,
+                     (const UmiRec*)u.d_rec, (char*)c->umi_names.p);
+  hipLaunchKernelGGL(k_umi_export_cells, dim3(blocks_for(u.cap)), dim3(kBlock), 0, u.st, u.cap, u.C, u.pc, (unsigned long long*)c->umi_cells.p);
+  return 0;
+}
+
+// phase 8: the counters of the call, and the output itself unless the caller asks for it later (fqg_umi_emit)
+int umi_finish(fqg_ctx* c, UmiCount& u) {
+  fqg_umi_result* out = u.out;
+  UmiCall& h_call = u.h_call;
+  HIP_TRY(c, hipMemcpyAsync(&h_call, u.d_call, sizeof(h_call), hipMemcpyDeviceToHost, u.st));
+  HIP_TRY(c, hipStreamSynchronize(u.st));
+  HIP_TRY(c, hipGetLastError());
+  if (h_call.table_full) return fail(c, FQG_ERR_STATE, "fqg_umi_count: hash table full");
+  for (int k = 0; k < 64; ++k) {
+    h_call.n_counted += h_call.spread[1][k];
+    h_call.n_new += h_call.spread[2][k];
+  }
+  out->n_counted = h_call.n_counted;
+  out->n_new = h_call.n_new;
+  out->unit_increments = u.unit ? 1 : 0;
+  if (u.unit) {
+    out->tot_reads = h_call.n_counted > 16777216ull ? 16777216.0f : (float)h_call.n_counted;
+    out->tot_umi = h_call.n_new > 16777216ull ? 16777216.0f : (float)h_call.n_new;
+  } else {
+    out->tot_reads = h_call.db_reads;
+    out->tot_umi = h_call.db_umi;
+  }
+  c->umi_n_features = u.n_feat;
+  c->umi_n_cells = u.n_cells;
+  if (u.prm->defer_output) return 0;
+  const int rc_emit = fqg_umi_emit(c, nullptr, 0, 0, out);
+  umi_drop_state(c);
+  return rc_emit;
+}
 }  // namespace
 }  // extern "C++"
-
-#define UMI_NEED(ptr) \
-  if (!(ptr)) return fail(c, FQG_ERR_NOMEM, "fqg_umi_count: device allocation failed")
 
 int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, const uint64_t* offsets,
                   uint64_t n_records, const fqg_umi_params* prm, fqg_umi_result* out) {
@@ -145,551 +896,20 @@ int fqg_umi_count(fqg_ctx* c, const void* stream, uint64_t nbytes, int mem, cons
   out->n_alignments = n_records;
   HIP_TRY(c, hipSetDevice(c->device));
   if (!n_records) return 0;
-  const uint32_t n = (uint32_t)n_records;
   umi_drop_state(c);
-  if (c->umi_arena_wanted > c->umi_arena.cap) {  // nothing of an earlier call is alive here: the arena may move
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    release(c->umi_arena);
-    (void)ensure(c, c->umi_arena, c->umi_arena_wanted + (c->umi_arena_wanted >> 3));  // (on failure: hipMalloc per buffer)
-  }
+  NEED(arena_regrow(c));  // (nothing of an earlier call is alive here)
   ArenaGrow grow_afterwards{c};
-  Scratch* Sp = new Scratch(c);
-  std::unique_ptr<Scratch> S_owner(Sp);
-  Scratch& S = *Sp;
-  hipStream_t st = c->stream;
-
-  // ---- inputs ----
-  const uint8_t* d_buf;
-  if (mem == FQG_MEM_HOST) {
-    uint8_t* p = S.get<uint8_t>(nbytes + 16);
-    UMI_NEED(p);
-    HIP_TRY(c, hipMemcpyAsync(p, stream, nbytes, hipMemcpyHostToDevice, st));
-    d_buf = p;
-  } else d_buf = (const uint8_t*)stream;
-  const unsigned long long* d_off;
-  if (mem == FQG_MEM_DEVICE_INDEXED) d_off = reinterpret_cast<const unsigned long long*>(offsets);  // (the caller's, in HBM)
-  else {
-    unsigned long long* p = S.get<unsigned long long>(n);
-    UMI_NEED(p);
-    HIP_TRY(c, hipMemcpyAsync(p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    d_off = p;
-  }
-
-  UmiParams P;
-  memset(&P, 0, sizeof(P));
-  memcpy(P.feat_tag, prm->feat_tag, 2);
-  memcpy(P.cell_tag, prm->cell_tag, 2);
-  memcpy(P.umi_tag, prm->umi_tag, 2);
-  P.sorted_by_cell = prm->sorted_by_cell;
-  P.uniq_mapped_only = prm->uniq_mapped_only;
-  P.max_cells = prm->max_cells;
-  P.max_features = prm->max_features;
-  P.min_reads = prm->min_reads;
-  P.min_umis = prm->min_umis;
-  // whitelists: the UMI list numbers its distinct entries 1..K in file order (load_whitelist :543-579 with
-  // map = umis_map); the cell list is a plain set
-  std::vector<unsigned long long> ku_sorted, kc_sorted;
-  std::vector<uint32_t> ku_order;
-  if (prm->known_umis) {
-    P.have_known_umis = 1;
-    std::vector<std::pair<unsigned long long, uint32_t>> v;
-    std::vector<unsigned long long> seen;
-    for (uint64_t i = 0; i < prm->n_known_umis; ++i) {
-      const unsigned long long x = prm->known_umis[i];
-      bool dup = false;
-      for (auto& e : v) dup |= e.first == x;  // (whitelists are small; keep file order exact)
-      if (!dup) v.push_back({x, (uint32_t)v.size()});
-    }
-    std::sort(v.begin(), v.end());
-    for (auto& e : v) {
-      ku_sorted.push_back(e.first);
-      ku_order.push_back(e.second);
-    }
-    P.n_known_umis = (uint32_t)v.size();
-    unsigned long long* a = S.get<unsigned long long>(v.size());
-    uint32_t* b = S.get<uint32_t>(v.size());
-    UMI_NEED(a && b);
-    if (!v.empty()) {
-      HIP_TRY(c, hipMemcpyAsync(a, ku_sorted.data(), v.size() * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(b, ku_order.data(), v.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    P.known_umis_sorted = a;
-    P.known_umis_order = b;
-  }
-  if (prm->known_cells) {
-    P.have_known_cells = 1;
-    kc_sorted.assign(prm->known_cells, prm->known_cells + prm->n_known_cells);
-    std::sort(kc_sorted.begin(), kc_sorted.end());
-    kc_sorted.erase(std::unique(kc_sorted.begin(), kc_sorted.end()), kc_sorted.end());
-    P.n_known_cells = (uint32_t)kc_sorted.size();
-    unsigned long long* a = S.get<unsigned long long>(kc_sorted.size());
-    UMI_NEED(a);
-    if (!kc_sorted.empty())
-      HIP_TRY(c, hipMemcpyAsync(a, kc_sorted.data(), kc_sorted.size() * 8, hipMemcpyHostToDevice, st));
-    P.known_cells_sorted = a;
-  }
-
-  if (prm->umi_table_keys) {
-    if (!prm->umi_table_ids || prm->n_umi_table >= 0xFFFFFFFFull) return fail(c, FQG_ERR_ARG, "fqg_umi_count: umi_table_ids / n_umi_table");
-    unsigned long long* a = S.get<unsigned long long>(prm->n_umi_table);
-    uint32_t* b = S.get<uint32_t>(prm->n_umi_table);
-    UMI_NEED(a && b);
-    if (prm->n_umi_table) {
-      HIP_TRY(c, hipMemcpyAsync(a, prm->umi_table_keys, (size_t)prm->n_umi_table * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(b, prm->umi_table_ids, (size_t)prm->n_umi_table * 4, hipMemcpyHostToDevice, st));
-    }
-    P.umi_table_keys = a;
-    P.umi_table_ids = b;
-    P.n_umi_table = (uint32_t)prm->n_umi_table;
-  }
-
-  UmiCall* d_call = S.get<UmiCall>(1);
-  UMI_NEED(d_call);
-  UmiCall h_call;
-  memset(&h_call, 0, sizeof(h_call));
-  h_call.first_key = ~0ull;
-  h_call.all_unit = 1;
-  HIP_TRY(c, hipMemcpyAsync(d_call, &h_call, sizeof(h_call), hipMemcpyHostToDevice, st));
-
-  // ---- parse ----
-  UmiRec* d_rec = S.get<UmiRec>(n);
-  uint8_t* d_stage = S.get<uint8_t>(n);
-  UMI_NEED(d_rec && d_stage);
-  {
-    ProfScope ps(c, "k_umi_parse");
-    // records per tile and the LDS area: what the mean record needs
-    // (the index on the device: the header in front of the first record is small beside the records, and this call
-    // always gets the whole stream - no first offset is fetched.  fqg_bam_add_tags / fqg_bam2fastq do fetch it, eight
-    // bytes and a synchronisation: bam2fastq hands a later PIECE over from byte 0, where nbytes / n is far off)
-    const double mean = mem == FQG_MEM_DEVICE_INDEXED ? (double)nbytes / (double)n : (double)(nbytes - offsets[0]) / (double)n;
-    const uint32_t T = (uint32_t)std::max(1.0, std::min(64.0, std::floor(((double)kParseStage - 64.0) / (1.1 * mean + 1.0))));
-    const uint32_t cap = std::min<uint32_t>((uint32_t)kParseStage, ((uint32_t)(1.15 * mean * T) + 256u + 15u) & ~15u);
-    hipLaunchKernelGGL(k_umi_parse, dim3((n + T - 1) / T), dim3(kWave), cap + 32, st, d_buf, nbytes, d_off, n, T, cap, P, d_rec,
-                       d_stage, d_call);
-  }
-
-  // ---- key tables ----
-  const uint64_t cap = pow2_at_least(2ull * n);
-  KeyTable U, C;
-  NameTable F;
-  {  // the seven arrays of the three tables start out all ones: one block, one fill
-    unsigned long long* blk = S.get<unsigned long long>(6 * cap + (3 * cap + 1) / 2 + 8, 0xFF);
-    UMI_NEED(blk);
-    U.keys = blk;
-    C.keys = blk + cap;
-    F.slots = blk + 2 * cap;
-    F.words = blk + 3 * cap;
-    uint32_t* firsts32 = reinterpret_cast<uint32_t*>(blk + 6 * cap);
-    U.first = firsts32;
-    C.first = firsts32 + cap;
-    F.first = firsts32 + 2 * cap;
-  }
-  U.mask = C.mask = F.mask = cap - 1;
-  uint32_t* d_uslot = S.get<uint32_t>(n);
-  uint32_t* d_cslot = S.get<uint32_t>(n);
-  uint32_t* d_fslot = S.get<uint32_t>(n);
-  UMI_NEED(d_uslot && d_cslot && d_fslot);
-  {
-    ProfScope ps(c, "k_umi_insert");
-    hipLaunchKernelGGL(k_umi_insert, dim3(blocks_for(n)), dim3(kBlock), 0, st, d_buf, nbytes, n, P, (const UmiRec*)d_rec, d_stage,
-                       U, C, F, d_uslot, d_cslot, d_fslot, d_call, measure_int("FQGPU_UMI_INSERT_ABL"));
-  }
-
-  // ---- dense ids: flags on the record axis + exclusive prefix ----
-  const uint64_t nb = scan64_spans(n);
-  uint32_t* d_flag[3];
-  unsigned long long *d_loc[3], *d_span[3], *d_tot = S.get<unsigned long long>(8);
-  UMI_NEED(d_tot);
-  const uint32_t* firsts[3] = {U.first, C.first, F.first};
-  {
-    ProfScope ps(c, "k_umi_ids");
-    // the three flag arrays are one block (one fill), the three scans one launch each
-    uint32_t* flags3 = S.get<uint32_t>(3ull * n + 64, 0);
-    UMI_NEED(flags3);
-    Scan3 t3;
-    Scan64 s3{};
-    for (int k = 0; k < 3; ++k) {
-      d_flag[k] = flags3 + (uint64_t)k * n;
-      d_loc[k] = S.get<unsigned long long>(n);
-      d_span[k] = S.get<unsigned long long>(nb);
-      UMI_NEED(d_loc[k] && d_span[k]);
-      t3.first[k] = firsts[k];
-      s3.in[k] = t3.flag[k] = d_flag[k];
-      s3.local[k] = d_loc[k];
-      s3.sums[k] = d_span[k];
-    }
-    s3.total = d_tot;
-    hipLaunchKernelGGL(k_umi_flag3, dim3(blocks_for(cap), 3), dim3(kBlock), 0, st, t3, cap);
-    scan64(c, s3, 3, n);
-  }
-  Prefix pu{d_loc[0], d_span[0]}, pc{d_loc[1], d_span[1]}, pf{d_loc[2], d_span[2]};
-  UmiIds ids;
-  ids.umi = S.get<uint32_t>(n);
-  ids.cell = S.get<uint32_t>(n);
-  ids.feat = S.get<uint32_t>(n);
-  UMI_NEED(ids.umi && ids.cell && ids.feat);
-  {
-    ProfScope ps(c, "k_umi_assign");
-    hipLaunchKernelGGL(k_umi_assign, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, P, (const UmiRec*)d_rec,
-                       (const uint8_t*)d_stage, U, C, F, (const uint32_t*)d_uslot, (const uint32_t*)d_cslot,
-                       (const uint32_t*)d_fslot, pu, pc, pf, (const uint32_t*)d_flag[1], ids, d_call);
-  }
-  // sorted mode: first record and size of every cell (the per-cell counting path works on record ranges) - launched
-  // before the host has seen the number of cells (at most n: the arrays are sized for that, the kernels read the
-  // count from the device), so that ONE synchronisation brings back everything the host decides on
-  uint32_t* d_cell_first = nullptr;
-  if (prm->sorted_by_cell) {
-    d_cell_first = S.get<uint32_t>((uint64_t)n + 2);
-    UMI_NEED(d_cell_first);
-    ProfScope ps(c, "k_umi_cell_first");
-    hipLaunchKernelGGL(k_umi_cell_first, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, C, pc, n, d_cell_first);
-    hipLaunchKernelGGL(k_umi_cell_sizes, dim3(blocks_for((uint64_t)n + 1)), dim3(kBlock), 0, st,
-                       (const unsigned long long*)d_tot, n, d_cell_first, d_call);
-  }
-  unsigned long long h_tot[8];
-  HIP_TRY(c, hipMemcpyAsync(&h_call, d_call, sizeof(h_call), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, sizeof(h_tot), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  if (h_call.table_full & 2u) return fail(c, FQG_ERR_ARG, "fqg_umi_count: a UMI of the call is missing from umi_table_keys");
-  if (h_call.table_full) return fail(c, FQG_ERR_STATE, "fqg_umi_count: hash table full");
-  for (int k = 0; k < 64; ++k) h_call.n_tags += h_call.spread[0][k];
-  out->n_tags_found = h_call.n_tags;
-  if (prm->defer_output) {  // the UMIs of the call that are not whitelisted, in order of first appearance (fqg_umi_umis: shards)
-    int rc;
-    c->umi_n_umis = h_tot[0];
-    if ((rc = ensure(c, c->umi_umis, (size_t)std::max<uint64_t>(h_tot[0], 1) * 8))) return rc;
-    hipLaunchKernelGGL(k_umi_export_cells, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, U, pu,
-                       (unsigned long long*)c->umi_umis.p);
-  }
-  out->n_umis_discarded = h_call.n_umis_disc;
-  out->n_cells_discarded = h_call.n_cells_disc;
-  const uint64_t n_cells = h_tot[1], n_feat = h_tot[2];
-  out->n_cells = n_cells;
-  out->n_features = n_feat;
-  if (h_call.first_key != ~0ull) {
-    out->code = (int32_t)(h_call.first_key & 0xFF);
-    out->record = h_call.first_key >> 8;
-    const uint32_t* src = out->code == FQG_E_UMI_TOO_MANY_UMIS ? ids.umi
-                          : out->code == FQG_E_UMI_TOO_MANY_FEATURES ? ids.feat : ids.cell;
-    uint32_t v = 0;
-    HIP_TRY(c, hipMemcpy(&v, src + out->record, 4, hipMemcpyDeviceToHost));
-    out->aux = v;
-    // counters as they stood when the reference stopped are not reproduced: it prints none of them
-    return 0;
-  }
-
-  // ---- counting: (cell, feature) pairs, new UMIs, the reference's tree where it is not a set, pairs by cell ----
-  PairTable Pt;
-  memset(&Pt, 0, sizeof(Pt));
-  uint8_t* d_new = nullptr;
-  uint32_t *d_cell_reads = nullptr, *d_cell_umis = nullptr, *d_cell_pairs = nullptr, *d_pair_of = nullptr;
-  float *d_pair_reads = nullptr, *d_pair_umis = nullptr, *d_cellf_reads = nullptr, *d_cellf_umis = nullptr;
-  unsigned long long *d_cloc = nullptr, *d_cspan = nullptr;
-  uint64_t n_pairs = 0;
-  const uint8_t* d_feat_replayed = nullptr;  // (set by the per-cell path when it replays sets)
-  const bool unit = h_call.all_unit != 0;
-  const uint64_t nbc = scan64_spans(n_cells + 2);
-  // CR-sorted input with unit increments: one workgroup per cell, LDS (fqg_umi_cell_kernels.hip).  Anything else -
-  // unsorted mode, fractional increments, features or cells beyond the key's bit fields - takes the hash tables.
-  static const bool force_hash = getenv("FQGPU_UMI_HASH_PATH") != nullptr;
-  const bool use_cells = prm->sorted_by_cell && unit && !force_hash && n_feat < (1ull << kCellFeatBits) &&
-                         h_call.max_cell_records < (1u << kCellIdxBits) && n_cells > 0;
-  auto hash_path = [&]() -> int {
-  // ---- (cell, feature) pairs, (pair, UMI) set ----
-  Pt.t.s = S.get<KeySlot>(cap, 0xFF);
-  Pt.t.mask = cap - 1;
-  Pt.reads = S.get<uint32_t>(cap, 0);
-  Pt.umis = S.get<uint32_t>(cap, 0);
-  SlotTable T;
-  T.s = S.get<KeySlot>(cap, 0xFF);
-  T.mask = cap - 1;
-  uint32_t* d_pslot = S.get<uint32_t>(n);
-  uint32_t* d_tslot = S.get<uint32_t>(n);
-  d_new = S.get<uint8_t>(n);
-  d_cell_reads = S.get<uint32_t>(n_cells + 2, 0);
-  d_cell_umis = S.get<uint32_t>(n_cells + 2, 0);
-  UMI_NEED(Pt.t.s && Pt.reads && Pt.umis && T.s && d_pslot && d_tslot && d_new &&
-           d_cell_reads && d_cell_umis);
-  {
-    ProfScope ps(c, "k_umi_count");
-    hipLaunchKernelGGL(k_umi_count, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, n, ids, T, Pt, d_pslot, d_tslot, d_call);
-    hipLaunchKernelGGL(k_umi_new, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)d_tslot,
-                       (const uint32_t*)d_pslot, T, Pt, ids, d_new, d_cell_reads, d_cell_umis, d_call);
-  }
-
-  // ---- the reference's UMI container where it is not a set (fqg_umi_rl_kernels.hip, fqg_rl_sim.h) ----
-  // records sorted by (pair slot, record index): needed by this stage and by the ordered float sums below
-  uint32_t* kp = S.get<uint32_t>(n);
-  uint32_t* kc = S.get<uint32_t>(n);
-  uint32_t* ix = S.get<uint32_t>(n);
-  uint32_t* ko = S.get<uint32_t>(n);
-  uint32_t* io = S.get<uint32_t>(n);
-  UMI_NEED(kp && kc && ix && ko && io);
-  size_t sort_tmp_bytes = 0;
-  HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_tmp_bytes, kp, ko, ix, io, (size_t)n, 0, 32, st));
-  void* sort_tmp = S.get<uint8_t>(sort_tmp_bytes + 16);
-  UMI_NEED(sort_tmp);
-  bool sorted_by_pair = false;
-  RlCall h_rl;
-  memset(&h_rl, 0, sizeof(h_rl));
-  if (!prm->strict_set || !unit) {
-    ProfScope ps(c, "k_umi_sort_pairs");
-    hipLaunchKernelGGL(k_umi_sort_keys, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)d_tslot,
-                       (const uint32_t*)d_pslot, (const uint32_t*)ids.cell, kp, kc, ix);
-    HIP_TRY(c, rocprim::radix_sort_pairs(sort_tmp, sort_tmp_bytes, kp, ko, ix, io, (size_t)n, 0, 32, st));
-    sorted_by_pair = true;
-  }
-  if (!prm->strict_set) {
-    RlCall* d_rl = S.get<RlCall>(1, 0);
-    uint32_t* d_sflag = S.get<uint32_t>(n);
-    unsigned long long* d_rloc = S.get<unsigned long long>(n);
-    unsigned long long* d_rspan = S.get<unsigned long long>(nb);
-    RlRuns runs;
-    runs.start = S.get<uint32_t>(n);
-    runs.len = S.get<uint32_t>(n);
-    runs.pslot = S.get<uint32_t>(n);
-    runs.flag = S.get<uint32_t>(n, 0xFF);
-    uint32_t* d_flagged = S.get<uint32_t>(n);
-    uint32_t* d_fk0 = S.get<uint32_t>(n);
-    UMI_NEED(d_rl && d_sflag && d_rloc && d_rspan && runs.start && runs.len && runs.pslot && runs.flag && d_flagged && d_fk0);
-    {
-      ProfScope ps(c, "k_rl_detect");
-      hipLaunchKernelGGL(k_rl_starts, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)ko, d_sflag);
-      scan64(c, d_sflag, d_rloc, d_rspan, d_tot + 6, n);
-      hipLaunchKernelGGL(k_rl_detect, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)ko, (const uint32_t*)io,
-                         (const uint32_t*)d_sflag, Prefix{d_rloc, d_rspan}, (const uint32_t*)ids.umi,
-                         (const uint8_t*)d_new, runs, d_flagged, d_fk0, d_rl);
-    }
-    HIP_TRY(c, hipMemcpyAsync(&h_rl, d_rl, sizeof(h_rl), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, sizeof(h_tot), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    const uint32_t n_runs = (uint32_t)h_tot[6], n_flagged = h_rl.n_flagged;
-    if (n_flagged) {
-      {  // which features these sets belong to (fqg_umi_replayed_features)
-        uint8_t* d_feat_flag = S.get<uint8_t>((uint64_t)n_feat + 2, 0);
-        UMI_NEED(d_feat_flag);
-        hipLaunchKernelGGL(k_umi_mark_replayed, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, st, n_flagged,
-                           (const uint32_t*)d_flagged, (const uint32_t*)runs.pslot, Pt, d_feat_flag);
-        d_feat_replayed = d_feat_flag;
-      }
-      // where every flagged run keeps its final array: at most 1 + 8 nodes per record of the run, 128-byte aligned
-      std::vector<uint32_t> h_len(n_flagged), h_off(n_flagged);
-      uint32_t* d_flen = S.get<uint32_t>(n_flagged);
-      uint32_t* d_foff = S.get<uint32_t>(n_flagged);
-      uint32_t* d_fext = S.get<uint32_t>(n_flagged, 0);
-      UMI_NEED(d_flen && d_foff && d_fext);
-      hipLaunchKernelGGL(k_rl_flag_lens, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, st, n_flagged,
-                         (const uint32_t*)d_flagged, (const uint32_t*)runs.len, d_flen);
-      HIP_TRY(c, hipMemcpyAsync(h_len.data(), d_flen, (size_t)n_flagged * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      uint32_t cap_nodes = 1u + 8u * h_rl.max_flagged_len + 2048u;
-      cap_nodes = (cap_nodes + 63u) & ~63u;
-      uint32_t mcap = 64;
-      while (mcap < h_rl.max_len) mcap <<= 1;  // (a power of two: the member sort pads to one)
-      uint64_t arena_nodes = 0;
-      for (uint32_t f = 0; f < n_flagged; ++f) {
-        h_off[f] = (uint32_t)arena_nodes;
-        arena_nodes += ((uint64_t)std::min<uint64_t>(cap_nodes, 1ull + 8ull * h_len[f]) + 63u) & ~63ull;
-        if (arena_nodes >= 0xFFFFFFFFull) return fail(c, FQG_ERR_STATE, "fqg_umi_count: too many replayed UMI sets");
-      }
-      uint16_t* d_arena = S.get<uint16_t>(arena_nodes + 64);
-      UMI_NEED(d_arena);
-      HIP_TRY(c, hipMemcpyAsync(d_foff, h_off.data(), (size_t)n_flagged * 4, hipMemcpyHostToDevice, st));
-      RlReplayArgs A;
-      memset(&A, 0, sizeof(A));
-      if (prm->sorted_by_cell) {
-        ProfScope ps(c, "k_rl_chains");
-        unsigned long long* ck = S.get<unsigned long long>(n_runs);
-        unsigned long long* cko = S.get<unsigned long long>(n_runs);
-        uint32_t* cv = S.get<uint32_t>(n_runs);
-        uint32_t* cvo = S.get<uint32_t>(n_runs);
-        uint32_t* pos = S.get<uint32_t>(n_runs);
-        uint32_t* ik = S.get<uint32_t>(n_flagged);
-        uint32_t* iko = S.get<uint32_t>(n_flagged);
-        uint32_t* iv = S.get<uint32_t>(n_flagged);
-        uint32_t* ivo = S.get<uint32_t>(n_flagged);
-        UMI_NEED(ck && cko && cv && cvo && pos && ik && iko && iv && ivo);
-        hipLaunchKernelGGL(k_rl_chain_keys, dim3(blocks_for(n_runs)), dim3(kBlock), 0, st, n_runs,
-                           (const uint32_t*)runs.pslot, Pt, ck, cv);
-        size_t tb = 0, tb2 = 0;
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tb, ck, cko, cv, cvo, (size_t)n_runs, 0, 64, st));
-        HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tb2, ik, iko, iv, ivo, (size_t)n_flagged, 0, 32, st));
-        void* tmp2 = S.get<uint8_t>(std::max(tb, tb2) + 16);
-        UMI_NEED(tmp2);
-        HIP_TRY(c, rocprim::radix_sort_pairs(tmp2, tb, ck, cko, cv, cvo, (size_t)n_runs, 0, 64, st));
-        hipLaunchKernelGGL(k_rl_positions, dim3(blocks_for(n_runs)), dim3(kBlock), 0, st, n_runs, (const uint32_t*)cvo, pos);
-        hipLaunchKernelGGL(k_rl_item_keys, dim3(blocks_for(n_flagged)), dim3(kBlock), 0, st, n_flagged,
-                           (const uint32_t*)d_flagged, (const uint32_t*)pos, ik, iv);
-        HIP_TRY(c, rocprim::radix_sort_pairs(tmp2, tb2, ik, iko, iv, ivo, (size_t)n_flagged, 0, 32, st));
-        A.chain_runs = cvo;
-        A.chain_key = cko;
-        A.pos_of_run = pos;
-        A.items = ivo;
-      }  // else: every (cell, feature) has a tree of its own (src/bam_umi_count.c:468-479), no history
-      A.flagged = d_flagged;
-      A.n_items = n_flagged;
-      A.runs = runs;
-      A.order = io;
-      A.umi_id = ids.umi;
-      A.cell_id = ids.cell;
-      A.is_new = d_new;
-      A.flag_k0 = d_fk0;
-      A.flag_off = d_foff;
-      A.flag_ext = d_fext;
-      A.arena = d_arena;
-      A.cap = cap_nodes;
-      A.mcap = mcap;
-      A.pair_umis = Pt.umis;
-      A.cell_umis = d_cell_umis;
-      A.n_new_spread = &d_call->spread[2][0];
-      A.call = d_rl;
-      const uint64_t work_bytes = rl_work_bytes(cap_nodes, mcap);
-      const unsigned grid = (unsigned)std::min<uint32_t>(A.n_items, 1024u);
-      A.in_lds = work_bytes <= 150u * 1024u;
-      if (!A.in_lds) {
-        A.scratch_stride = (work_bytes + 255) & ~255ull;
-        A.scratch = S.get<uint8_t>(A.scratch_stride * grid);
-        UMI_NEED(A.scratch);
-      }
-      if (A.in_lds && work_bytes > 48u * 1024u) {  // (raised per device and kernel, for the whole process: raise_dynamic_lds)
-        const int rcl = raise_dynamic_lds(c, reinterpret_cast<const void*>(k_rl_replay), (size_t)work_bytes);
-        if (rcl) return rcl;
-      }
-      {
-        ProfScope ps(c, "k_rl_replay");
-        hipLaunchKernelGGL(k_rl_replay, dim3(grid), dim3(kWave), A.in_lds ? (size_t)work_bytes : 0, st, A);
-      }
-      HIP_TRY(c, hipMemcpyAsync(&h_rl, d_rl, sizeof(h_rl), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      HIP_TRY(c, hipGetLastError());
-    }
-    if (getenv("FQGPU_RL_DEBUG"))
-      fprintf(stderr, "[rl] runs %u flagged %u max_len %u max_flagged_len %u overwrites %u lookback_runs %u changed %u undefined %u "
-              "ticks(100MHz): replay %llu (build %llu loop %llu) lookback %llu store %llu\n", n_runs, n_flagged, h_rl.max_len, h_rl.max_flagged_len,
-              h_rl.overwrites, h_rl.lookback_runs, h_rl.changed, (unsigned)h_rl.undefined, h_rl.clk_replay, h_rl.clk_build, h_rl.clk_loop, h_rl.clk_lookback, h_rl.clk_store);
-    out->rl_replayed = n_flagged;
-    out->rl_changed = h_rl.changed;
-    out->rl_undefined = h_rl.undefined;
-    out->rl_unresolved = h_rl.overflow ? 1 : 0;
-  }
-
-  // ---- float32 counters ----
-  d_pair_reads = S.get<float>(cap, 0);
-  d_pair_umis = S.get<float>(cap, 0);
-  d_cellf_reads = S.get<float>(n_cells + 2, 0);
-  d_cellf_umis = S.get<float>(n_cells + 2, 0);
-  UMI_NEED(d_pair_reads && d_pair_umis && d_cellf_reads && d_cellf_umis);
-  if (unit) {
-    ProfScope ps(c, "k_umi_sums");
-    hipLaunchKernelGGL(k_umi_unit_sums, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, (const uint32_t*)Pt.reads,
-                       (const uint32_t*)Pt.umis, d_pair_reads, d_pair_umis);
-    hipLaunchKernelGGL(k_umi_unit_sums, dim3(blocks_for(n_cells + 1)), dim3(kBlock), 0, st, n_cells + 1,
-                       (const uint32_t*)d_cell_reads, (const uint32_t*)d_cell_umis, d_cellf_reads, d_cellf_umis);
-  } else {
-    // fractional increments (NH > 1, several genes): replay the additions in record order
-    ProfScope ps(c, "k_umi_sums_ordered");
-    for (int pass = 0; pass < 2; ++pass) {
-      if (pass || !sorted_by_pair)
-        HIP_TRY(c, rocprim::radix_sort_pairs(sort_tmp, sort_tmp_bytes, pass ? kc : kp, ko, ix, io, (size_t)n, 0, 32, st));
-      hipLaunchKernelGGL(k_umi_sums_sorted, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, (const uint32_t*)ko,
-                         (const uint32_t*)io, (const UmiRec*)d_rec, (const uint8_t*)d_new,
-                         pass ? d_cellf_reads : d_pair_reads, pass ? d_cellf_umis : d_pair_umis);
-    }
-    hipLaunchKernelGGL(k_umi_db_totals, dim3(1), dim3(64), 0, st, n, n, (const UmiRec*)d_rec, (const uint32_t*)d_tslot,
-                       (const uint8_t*)d_new, d_call, prm->db_start_reads, prm->db_start_umi,
-                       (uint32_t)std::min<uint64_t>(prm->db_skip, n));
-  }
-
-  // ---- pairs grouped by cell, output ----
-  d_cell_pairs = S.get<uint32_t>(n_cells + 2, 0);
-  uint32_t* d_cursor = S.get<uint32_t>(n_cells + 2, 0);
-  d_cloc = S.get<unsigned long long>(n_cells + 2);
-  d_cspan = S.get<unsigned long long>(nbc);
-  UMI_NEED(d_cell_pairs && d_cursor && d_cloc && d_cspan);
-  {
-    ProfScope ps(c, "k_umi_pairs");
-    hipLaunchKernelGGL(k_umi_pairs_count, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, Pt, d_cell_pairs);
-    scan64(c, d_cell_pairs, d_cloc, d_cspan, d_tot + 3, n_cells + 2);
-  }
-  HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, sizeof(h_tot), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  n_pairs = h_tot[3];
-  const Prefix cstart{d_cloc, d_cspan};
-  d_pair_of = S.get<uint32_t>(n_pairs);
-  UMI_NEED(d_pair_of);
-  if (n_pairs) {
-    ProfScope ps(c, "k_umi_pairs");
-    hipLaunchKernelGGL(k_umi_pairs_fill, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, Pt, cstart, d_cursor, d_pair_of);
-  }
-    return 0;
-  };
-  auto cell_path = [&]() -> int {
-#include "fqg_umi_cell_path.inc"
-    return 0;
-  };
-  {
-    const int rc_count = use_cells ? cell_path() : hash_path();
-    if (rc_count) return rc_count;
-  }
-  const Prefix cstart{d_cloc, d_cspan};
-  // what the output step needs, kept with the scratch memory it points into
-  UmiState* us = new UmiState();
-  us->scratch = S_owner.release();
-  us->A.Pt = Pt;
-  us->A.start = cstart;
-  us->A.cell_pairs = d_cell_pairs;
-  us->A.pair_of = d_pair_of;
-  us->A.pair_reads = d_pair_reads;
-  us->A.pair_umis = d_pair_umis;
-  us->A.cell_umis = d_cellf_umis;
-  us->A.P = P;
-  us->A.n_cells = (uint32_t)n_cells;
-  us->A.remap = nullptr;
-  us->A.pairs_by_feature = use_cells ? 1 : 0;
-  us->A.cell_offset = 0;
-  us->d_call = d_call;
-  us->d_tot = d_tot;
-  us->n_pairs = n_pairs;
-  us->rec_feat = ids.feat;
-  us->feat_replayed = d_feat_replayed;
-  us->n_records = n;
-  us->n_features = n_feat;
-  c->umi_state = us;
-  // names and cells in id order
-  {
-    int rc;
-    if ((rc = ensure(c, c->umi_names, (size_t)std::max<uint64_t>(n_feat, 1) * kFeatIdMaxLen))) return rc;
-    if ((rc = ensure(c, c->umi_cells, (size_t)std::max<uint64_t>(n_cells, 1) * 8))) return rc;
-    ProfScope ps(c, "k_umi_export");
-    hipLaunchKernelGGL(k_umi_export_features, dim3(blocks_for(cap)), dim3(kBlock), 0, st, d_buf, cap, F, pf,
-                       (const UmiRec*)d_rec, (char*)c->umi_names.p);
-    hipLaunchKernelGGL(k_umi_export_cells, dim3(blocks_for(cap)), dim3(kBlock), 0, st, cap, C, pc,
-                       (unsigned long long*)c->umi_cells.p);
-  }
-  HIP_TRY(c, hipMemcpyAsync(&h_call, d_call, sizeof(h_call), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  HIP_TRY(c, hipGetLastError());
-  if (h_call.table_full) return fail(c, FQG_ERR_STATE, "fqg_umi_count: hash table full");
-  for (int k = 0; k < 64; ++k) {
-    h_call.n_counted += h_call.spread[1][k];
-    h_call.n_new += h_call.spread[2][k];
-  }
-  out->n_counted = h_call.n_counted;
-  out->n_new = h_call.n_new;
-  out->unit_increments = unit ? 1 : 0;
-  if (unit) {
-    out->tot_reads = h_call.n_counted > 16777216ull ? 16777216.0f : (float)h_call.n_counted;
-    out->tot_umi = h_call.n_new > 16777216ull ? 16777216.0f : (float)h_call.n_new;
-  } else {
-    out->tot_reads = h_call.db_reads;
-    out->tot_umi = h_call.db_umi;
-  }
-  c->umi_n_features = n_feat;
-  c->umi_n_cells = n_cells;
-  if (prm->defer_output) return 0;
-  const int rc_emit = fqg_umi_emit(c, nullptr, 0, 0, out);
-  umi_drop_state(c);
-  return rc_emit;
+  UmiCount u{nbytes, (uint32_t)n_records, prm, out, std::unique_ptr<Scratch>(new Scratch(c)), c->stream};
+  NEED(umi_inputs(c, u, stream, mem, offsets));
+  NEED(umi_parameters(c, u));
+  NEED(umi_parse_and_insert(c, u));
+  NEED(umi_dense_ids(c, u));
+  NEED(umi_first_results(c, u));
+  if (u.stopped) return 0;
+  // counting: (cell, feature) pairs, new UMIs, the reference's tree where it is not a set, pairs by cell
+  NEED(u.by_cells ? umi_count_cells(c, u) : umi_count_tables(c, u));
+  NEED(umi_keep_state(c, u));
+  return umi_finish(c, u);
 }
 
 int fqg_umi_emit(fqg_ctx* c, const uint32_t* feat_remap, uint64_t n_remap, uint32_t cell_offset, fqg_umi_result* out) {

@@ -3,8 +3,10 @@ every comparable golden invocation of the reference binary (tests/golden/umi_cou
 fqg_umi_count through the C-ABI against the oracle (oracle/umi_oracle.py) on seeded BAMs with
 re-used UMIs, NH weights, multi-gene tags, whitelists, in both output modes.  Integer / byte work
 and float32 counters added in record order: the bar is bit-exact."""
+import json
 import os
 import subprocess
+import sys
 import tempfile
 import zlib
 
@@ -166,10 +168,8 @@ def test_fixed_geometry_batch_against_the_tree_replay(ctx):
     assert got["rl_replayed"] >= 1 and stats[2] >= 1   # the input does exercise the defect
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_dense_umi_reuse_against_the_tree_replay(ctx, seed):
-    """Few UMI values, many reads per (cell, gene): most sets hit the overwrite, many read slots that only an
-    earlier cell of the same gene wrote (the look-back), some read memory the reference never wrote."""
+def dense_umi_reuse_input(seed):
+    """Few UMI values, many reads per (cell, gene): the stream and its (cell, gene, UMI) columns."""
     rng = np.random.default_rng(900 + seed)
     n = int(rng.integers(2000, 60000))
     n_cells, n_genes = int(rng.integers(2, 80)), int(rng.integers(1, 30))
@@ -179,10 +179,45 @@ def test_dense_umi_reuse_against_the_tree_replay(ctx, seed):
     umi = (rng.integers(0, space, n) * int(rng.choice([1, 7, 64]))) % (4 ** 10)
     cells_code = rng.choice(np.uint64(1) << np.uint64(32), size=n_cells, replace=False).astype(np.uint64)
     rec = bamgen.fixed_records(cells_code[cell], gene, umi.astype(np.uint64))
-    got = ctx.umi_count(bamgen.header() + rec.tobytes())
+    return bamgen.header() + rec.tobytes(), cell, gene, umi
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_dense_umi_reuse_against_the_tree_replay(ctx, seed):
+    """Few UMI values, many reads per (cell, gene): most sets hit the overwrite, many read slots that only an
+    earlier cell of the same gene wrote (the look-back), some read memory the reference never wrote."""
+    stream, cell, gene, umi = dense_umi_reuse_input(seed)
+    got = ctx.umi_count(stream)
     lu, lr, tu, tr, nc, ng, stats = bamgen.expected_matrix_reference(cell, gene, umi)
     assert got["code"] == 0 and got["rl_unresolved"] == 0
     assert got["entries"][0] == lu and got["entries"][1] == lr and got["total"] == [tu, tr]
+
+
+def test_dense_umi_reuse_on_the_table_path():
+    """The same input (seeds 900, 901) through the hash tables, which input grouped by cell with unit increments
+    does not reach by itself: FQGPU_UMI_HASH_PATH is read once per process, so a child process with it set runs
+    every stream twice on one context - buffers from hipMalloc the first time, from the arena the second
+    (tests/umi_table_path_worker.py).  All four results: what the test above requires."""
+    inputs = [dense_umi_reuse_input(seed) for seed in (0, 1)]
+    env = dict(os.environ, FQGPU_UMI_HASH_PATH="1", FQGPU_RL_DEBUG="1")
+    with tempfile.TemporaryDirectory() as tmp:
+        np.savez(os.path.join(tmp, "in.npz"), **{"seed%d" % (900 + k): np.frombuffer(s[0], dtype=np.uint8)
+                                                  for k, s in enumerate(inputs)})
+        out = os.path.join(tmp, "out.json")
+        p = subprocess.run([sys.executable, os.path.join(REPO, "tests", "umi_table_path_worker.py"),
+                            os.path.join(tmp, "in.npz"), out], env=env, cwd=REPO, capture_output=True, timeout=120)
+        err = p.stderr.decode("latin-1")
+        assert p.returncode == 0, err[-3000:]
+        runs = json.load(open(out))
+    # (the replay's debug line names the path that ran: "[rl] ..." the tables, "[rl/cells] ..." one workgroup per cell)
+    assert err.count("[rl] runs ") == 4 and "[rl/cells]" not in err, err[-3000:]
+    assert [r["input"] for r in runs] == ["seed900", "seed900", "seed901", "seed901"]
+    for k, (stream, cell, gene, umi) in enumerate(inputs):
+        lu, lr, tu, tr, nc, ng, stats = bamgen.expected_matrix_reference(cell, gene, umi)
+        for r in runs[2 * k: 2 * k + 2]:
+            assert r["code"] == 0 and r["rl_unresolved"] == 0
+            assert [tuple(e) for e in r["entries"][0]] == lu and [tuple(e) for e in r["entries"][1]] == lr
+            assert r["total"] == [tu, tr]
 
 
 def test_strict_set_extra_against_numpy(ctx):
