@@ -33,6 +33,7 @@
 #include "fqg_deflate_kernels.hip"
 #include "fqg_inflate_kernels.hip"
 #include "fqg_bam_index_kernels.hip"
+#include "fqg_names_build_plan.h"
 
 using namespace fqg;
 
@@ -1588,515 +1589,6 @@ void fqg_frame_release(fqg_frame* f) {
 
 uint64_t fqg_frame_n_records(const fqg_frame* f) { return f ? f->fv.n_records : 0; }
 
-// ---- read-name index ------------------------------------------------------------------------
-struct fqg_index {
-  fqg_ctx* ctx = nullptr;
-  DevBuf slots, names, claims, segs_dev, found, match;
-  uint64_t capacity = 0;
-  uint64_t rec_cap = 0;          // records names[] / claims[] have room for
-  bool keep_names = true;        // false: nobody will look names up in this index (fqg_index_expect_lookups)
-  std::vector<fqg_frame*> frames;
-  std::vector<IndexSeg> segs;
-  uint64_t n_records_total = 0;  // records fed so far = global index of the next frame's first record
-  uint64_t n_askers_total = 0;   // records of the asking file(s) matched against the index so far
-  uint64_t inserted = 0, matched = 0, name_bytes = 0;
-  int fmt = FQG_NAME_UNDEF, is_pe = 0;
-  uint32_t flags = 0;
-  bool names_once = true;        // no insert has reported a repeated name or a header without '@' (IndexView::n_positional)
-};
-
-namespace {
-
-int index_alloc_table(fqg_index* ix, uint64_t capacity) {
-  fqg_ctx* c = ix->ctx;
-  int rc;
-  if ((rc = ensure(c, ix->slots, (size_t)capacity * 8))) return rc;
-  HIP_TRY(c, hipMemsetAsync(ix->slots.p, 0xFF, (size_t)capacity * 8, c->stream));
-  ix->capacity = capacity;
-  return 0;
-}
-
-IndexView index_view(fqg_index* ix) {
-  IndexView v;
-  v.slots = (unsigned long long*)ix->slots.p;
-  v.names = ix->keep_names ? (NameRec*)ix->names.p : nullptr;
-  v.claims = (unsigned long long*)ix->claims.p;
-  v.mask = ix->capacity - 1;
-  static const bool no_positional = getenv("FQGPU_NO_POSITIONAL_MATCH") != nullptr;  // (measurement, tests)
-  v.n_positional = ix->keep_names && ix->names.p && ix->names_once && !no_positional ? ix->n_records_total : 0;
-  v.segs = (const IndexSeg*)ix->segs_dev.p;
-  v.n_segs = (int)ix->segs.size();
-  v.fmt = ix->fmt;
-  v.is_pe = ix->is_pe;
-  v.may_have_nul = (ix->flags & kFlagNul) ? 1 : 0;
-  return v;
-}
-
-// room in names[] / claims[] for `total` inserted records (kept across growth: record-ordered arrays)
-int index_reserve_records(fqg_index* ix, uint64_t total) {
-  fqg_ctx* c = ix->ctx;
-  if (total <= ix->rec_cap) return 0;
-  const uint64_t cap = std::max<uint64_t>(total + total / 8 + 1024, 2 * ix->rec_cap);
-  DevBuf names, claims;
-  hipError_t e = hipSuccess;
-  if (ix->keep_names) e = hipMalloc(&names.p, (size_t)cap * sizeof(NameRec));
-  if (e == hipSuccess) e = hipMalloc(&claims.p, (size_t)cap * 8);
-  if (e != hipSuccess) {
-    if (names.p) (void)hipFree(names.p);
-    return fail(c, FQG_ERR_NOMEM, "name index: hipMalloc", e);
-  }
-  names.cap = (size_t)cap * sizeof(NameRec);
-  claims.cap = (size_t)cap * 8;
-  const uint64_t used = ix->n_records_total;
-  if (used && ix->names.p && names.p)
-    (void)hipMemcpyAsync(names.p, ix->names.p, (size_t)used * sizeof(NameRec), hipMemcpyDeviceToDevice, c->stream);
-  if (used && ix->claims.p) (void)hipMemcpyAsync(claims.p, ix->claims.p, (size_t)used * 8, hipMemcpyDeviceToDevice, c->stream);
-  (void)hipMemsetAsync((char*)claims.p + (size_t)used * 8, 0xFF, (size_t)(cap - used) * 8, c->stream);  // nobody has asked yet
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  release(ix->names);
-  release(ix->claims);
-  ix->names = names;
-  ix->claims = claims;
-  ix->rec_cap = cap;
-  return 0;
-}
-
-int index_upload_segs(fqg_index* ix) {
-  fqg_ctx* c = ix->ctx;
-  int rc;
-  if ((rc = ensure(c, ix->segs_dev, std::max<size_t>(1, ix->segs.size()) * sizeof(IndexSeg)))) return rc;
-  if (!ix->segs.empty())
-    HIP_TRY(c, hipMemcpyAsync(ix->segs_dev.p, ix->segs.data(), ix->segs.size() * sizeof(IndexSeg),
-                              hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-
-int index_reset_call(fqg_ctx* c) {
-  IndexCall z;
-  memset(&z, 0, sizeof(z));
-  z.first_dup = z.first_wrong = z.first_missing = kNoRecord;
-  *c->h_icall = z;
-  HIP_TRY(c, hipMemcpyAsync(c->d_icall, c->h_icall, sizeof(IndexCall), hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-
-int index_fetch_call(fqg_ctx* c) {
-  HIP_TRY(c, hipMemcpyAsync(c->h_icall, c->d_icall, sizeof(IndexCall), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-unsigned index_grid(fqg_ctx* c, uint64_t n) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 16));
-}
-
-// the capture records of the last fqg_validate belong to this frame (FQG_VALIDATE_NAMES, streamed)
-// (digests hold no name bytes and are made under one file state: they serve the insert into an index that keeps no name
-// records, for that very state - everybody else reads the names through the line index)
-bool names_usable(const fqg_ctx* c, const FrameView& fv, const fqg_file_state* st, bool bytes_needed) {
-  static const bool off = getenv("FQGPU_NO_NAME_CAPTURE") != nullptr;  // (A/B: always go through the line index)
-  if (off || !c->names_img || c->names_img != fv.img || c->names_nbytes != fv.nbytes) return false;
-  if (c->names.digests) return !bytes_needed && st->readname_format == c->names.fmt && st->is_pe == c->names.is_pe;
-  return true;
-}
-// the lists k_names_pass fills for k_names_rest
-int env_int(const char* name, int dflt);
-int names_prepare(fqg_ctx* c, const FrameView& fv) {
-  int rc;
-  (void)fv;
-  const uint64_t n_slots = (uint64_t)c->names.cr.n_chunks << c->names.k_shift;
-  if ((rc = ensure(c, c->name_redo, ((n_slots + 63) / 64 + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->name_redo_chunks, (((size_t)std::max<uint32_t>(c->names.cr.n_chunks, 1) + 15) & ~(size_t)15) + 16))) return rc;
-  c->names.redo_bits = (unsigned long long*)c->name_redo.p;
-  c->names.chunk_redo = (uint8_t*)c->name_redo_chunks.p;
-  static const int abl = measure_int("FQGPU_NAMES_ABL");
-  c->names.ablate = abl;
-  return 0;
-}
-// (measurement knobs: FQGPU_NAMES_BLOCKS_PER_CU, FQGPU_NAMES_DYN_LDS - bytes of unused LDS per workgroup, which caps the
-// workgroups a CU holds -, FQGPU_NAMES_NT=0 for plain instead of non-temporal loads of the capture records)
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-unsigned names_grid(fqg_ctx* c) {
-  static const int per_cu = std::max(1, env_int("FQGPU_NAMES_BLOCKS_PER_CU", 16));
-  const uint64_t n_slots = (uint64_t)c->names.cr.n_chunks << c->names.k_shift;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_slots + kBlock - 1) / kBlock, (uint64_t)c->cu_count * per_cu));
-}
-void launch_names_pass(fqg_ctx* c, bool match, const FrameView& fv, const IndexView& iv, const fqg_file_state* st,
-                       uint64_t base, unsigned long long* found) {
-  static const unsigned dyn_lds = (unsigned)std::max(0, env_int("FQGPU_NAMES_DYN_LDS", 0));
-  static const bool nt = env_int("FQGPU_NAMES_NT", 1) != 0;
-#define FQG_NAMES_PASS(M, N)                                                                                             \
-  hipLaunchKernelGGL((k_names_pass<M, N>), dim3(names_grid(c)), dim3(kBlock), dyn_lds, c->stream, fv, c->names, iv,       \
-                     st->readname_format, st->is_pe, base, found, c->d_icall)
-  if (match) {
-    if (nt) FQG_NAMES_PASS(true, true);
-    else FQG_NAMES_PASS(true, false);
-  } else if (c->names.digests) {
-    hipLaunchKernelGGL((k_names_pass<false, true, true>), dim3(names_grid(c)), dim3(kBlock), dyn_lds, c->stream, fv, c->names, iv,
-                       st->readname_format, st->is_pe, base, found, c->d_icall);
-  } else {
-    if (nt) FQG_NAMES_PASS(false, true);
-    else FQG_NAMES_PASS(false, false);
-  }
-#undef FQG_NAMES_PASS
-}
-
-// The table built part by part in LDS from the name digests of the current frame (fqg_names_build_kernels.hip) instead of
-// one CAS per name.  Returns 0 when it ran (the call's scalars hold its counts and findings), 1 when it does not apply
-// or a bucket overflowed (nothing has touched the table: the caller takes k_names_pass), < 0 on errors.
-constexpr unsigned long long kBuildSpillCap = 1ull << 20;
-int names_build(fqg_ctx* c, fqg_index* ix, const FrameView& fv, const fqg_file_state* st, uint64_t record_base) {
-  const int mode = env_int("FQGPU_NAMES_BUILD", -1);  // 0: never, 1: whenever the table allows it (tests), -1: by size
-  if (mode == 0) return 1;
-  const bool from_records = !c->names.digests;  // (an index that keeps name records: keys and names[] from the capture records)
-  uint32_t k = 0;
-  while ((1ull << k) < ix->capacity) ++k;
-  if (k < kPartLogMin + 1) return 1;
-  uint32_t part_log = std::min(std::max(k > 16 ? k - 16 : 0u, kPartLogMin), kPartLogMax);
-  {
-    const int forced = env_int("FQGPU_BUILD_PART_LOG", 0);  // (A/B)
-    if (forced == 12 || forced == 13) part_log = std::max<uint32_t>(forced, k > 16 ? k - 16 : 0u);
-    if (part_log > kPartLogMax || k < part_log + 1) return 1;
-  }
-  const uint32_t part_bits = k - part_log;
-  const uint32_t bits0 = std::min<uint32_t>(part_bits, 8), bits1 = part_bits - bits0;
-  if (bits1 > 8) return 1;
-  // worth it when the frame brings a sizeable share of the table: the build writes (and, for an index that is not
-  // empty, first reads) every part - 8 bytes per SLOT -, the CAS pass costs by the name
-  const bool empty = ix->n_records_total == 0;
-  if (mode < 0 && fv.n_records < ix->capacity / (empty ? 16 : 8)) return 1;
-  const uint64_t n = fv.n_records;
-  auto room = [](double mean) { return (unsigned long long)(mean + 8.0 * std::sqrt(mean + 1.0) + 64.0); };
-  const unsigned long long cap0 = room((double)n / (double)(1u << bits0));
-  const unsigned long long cap1 = bits1 ? room((double)n / (double)(1u << part_bits)) : 0;
-  int rc;
-  if ((rc = ensure(c, c->build_keys[0], (size_t)(cap0 << bits0) * sizeof(BuildKey)))) return rc;
-  if (bits1 && (rc = ensure(c, c->build_keys[1], (size_t)(cap1 << part_bits) * sizeof(BuildKey)))) return rc;
-  const size_t n_cursors = (size_t)(1u << bits0) + (bits1 ? (size_t)(1u << part_bits) : 0);
-  if ((rc = ensure(c, c->build_cursor, n_cursors * 4))) return rc;
-  if ((rc = ensure(c, c->build_spill, (size_t)kBuildSpillCap * sizeof(BuildKey)))) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->build_cursor.p, 0, n_cursors * 4, c->stream));
-  unsigned int* cur0 = (unsigned int*)c->build_cursor.p;
-  unsigned int* cur1 = cur0 + (1u << bits0);
-  const uint64_t mask = ix->capacity - 1;
-  BuildLevel L0{(BuildKey*)c->build_keys[0].p, cur0, cap0, k - bits0, bits0};
-  const uint64_t n_slots = (uint64_t)c->names.cr.n_chunks << c->names.k_shift;
-  {
-    ProfScope ps(c, "k_names_build_scatter0");
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_slots + kBuildTile - 1) / kBuildTile, (uint64_t)c->cu_count * 8));
-    if (from_records)
-      hipLaunchKernelGGL(k_build_scatter<2>, dim3(grid), dim3(kBuildThreads), 0, c->stream, fv, c->names, record_base, mask, L0,
-                         (const BuildKey*)nullptr, (const unsigned int*)nullptr, 0ull, c->d_icall,
-                         ix->keep_names ? (NameRec*)ix->names.p : (NameRec*)nullptr, st->readname_format, st->is_pe);
-    else
-      hipLaunchKernelGGL(k_build_scatter<0>, dim3(grid), dim3(kBuildThreads), 0, c->stream, fv, c->names, record_base, mask, L0,
-                         (const BuildKey*)nullptr, (const unsigned int*)nullptr, 0ull, c->d_icall, (NameRec*)nullptr, 0, 0);
-  }
-  const BuildKey* part_keys = L0.out;
-  const unsigned int* part_count = cur0;
-  unsigned long long part_cap = cap0;
-  if (bits1) {
-    BuildLevel L1{(BuildKey*)c->build_keys[1].p, cur1, cap1, part_log, bits1};
-    ProfScope ps(c, "k_names_build_scatter1");
-    const unsigned tiles = (unsigned)((cap0 + kBuildTile - 1) / kBuildTile);
-    hipLaunchKernelGGL(k_build_scatter<1>, dim3(tiles, 1u << bits0), dim3(kBuildThreads), 0, c->stream, fv, c->names, record_base, mask, L1,
-                       (const BuildKey*)L0.out, (const unsigned int*)cur0, cap0, c->d_icall, (NameRec*)nullptr, 0, 0);
-    part_keys = L1.out;
-    part_count = cur1;
-    part_cap = cap1;
-  }
-  {
-    ProfScope ps(c, "k_names_build_parts");
-    if (part_log == 12)
-      hipLaunchKernelGGL(k_build_parts<12>, dim3(1u << part_bits), dim3(kBlock), 0, c->stream, fv, index_view(ix), record_base, part_keys,
-                         part_count, part_cap, empty ? 0 : 1, (BuildKey*)c->build_spill.p, kBuildSpillCap, c->d_icall);
-    else
-      hipLaunchKernelGGL(k_build_parts<13>, dim3(1u << part_bits), dim3(kBlock), 0, c->stream, fv, index_view(ix), record_base, part_keys,
-                         part_count, part_cap, empty ? 0 : 1, (BuildKey*)c->build_spill.p, kBuildSpillCap, c->d_icall);
-  }
-  {
-    ProfScope ps(c, "k_names_build_spill");
-    hipLaunchKernelGGL(k_build_spill, dim3(64), dim3(kBlock), 0, c->stream, fv, index_view(ix), record_base,
-                       (const BuildKey*)c->build_spill.p, kBuildSpillCap, c->d_icall);
-  }
-  if ((rc = index_fetch_call(c))) return rc;
-  // (gigabytes that only this call needs: a context that keeps them is what the next large allocation of the process
-  // fails on - the bench's 200 M-pair leg did, with 4 GB free of 288)
-  release(c->build_keys[0]);
-  release(c->build_keys[1]);
-  if (c->h_icall->build_overflow) return 1;
-  return 0;
-}
-
-// rebuild the table at a larger capacity from the retained segments
-int index_grow(fqg_index* ix, uint64_t need_names) {
-  fqg_ctx* c = ix->ctx;
-  uint64_t cap = ix->capacity ? ix->capacity : 1024;
-  while (cap < 2 * need_names) cap <<= 1;
-  if (cap == ix->capacity) return 0;
-  int rc;
-  if ((rc = index_alloc_table(ix, cap))) return rc;
-  if ((rc = index_upload_segs(ix))) return rc;
-  for (size_t s = 0; s < ix->segs.size(); ++s) {
-    if (!ix->segs[s].n_records) continue;  // (a frame whose insert failed: kept for ownership only)
-    if ((rc = index_reset_call(c))) return rc;
-    FrameView fv = ix->frames[s]->fv;
-    ProfScope ps(c, "k_index_insert(regrow)");
-    IndexView v = index_view(ix);
-    v.names = nullptr;  // (the name records of these frames are in place)
-    hipLaunchKernelGGL(k_index_insert, dim3(index_grid(c, fv.n_records)), dim3(kBlock), 0, c->stream, fv, v,
-                       ix->segs[s].record_base, c->d_icall);
-  }
-  return 0;
-}
-
-}  // namespace
-
-int fqg_index_create(fqg_ctx* c, uint64_t expected_names, fqg_index** out) {
-  if (!c || !out) return FQG_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  fqg_index* ix = new fqg_index();
-  ix->ctx = c;
-  uint64_t cap = 1024;
-  while (cap < 2 * expected_names) cap <<= 1;
-  int rc = index_alloc_table(ix, cap);
-  if (rc) {
-    fqg_index_destroy(ix);
-    return rc;
-  }
-  *out = ix;
-  return 0;
-}
-
-int fqg_index_expect_lookups(fqg_index* ix, int yes) {
-  if (!ix) return FQG_ERR_ARG;
-  if (ix->n_records_total) return fail(ix->ctx, FQG_ERR_STATE, "fqg_index_expect_lookups: the index is not empty");
-  ix->keep_names = yes != 0;
-  return 0;
-}
-
-void fqg_index_destroy(fqg_index* ix) {
-  if (!ix) return;
-  (void)hipStreamSynchronize(ix->ctx->stream);
-  for (auto* f : ix->frames) fqg_frame_release(f);
-  release(ix->slots);
-  release(ix->names);
-  release(ix->claims);
-  release(ix->segs_dev);
-  release(ix->found);
-  release(ix->match);
-  delete ix;
-}
-
-int fqg_index_insert_unique(fqg_ctx* c, fqg_index* ix, const fqg_file_state* st, fqg_index_result* out) {
-  if (!c || !ix || !st || !out || ix->ctx != c) return FQG_ERR_ARG;
-  if (!c->frame_valid) return fail(c, FQG_ERR_STATE, "no frame: call fqg_validate first");
-  if (const int irc = index_now(c)) return irc;
-  memset(out, 0, sizeof(*out));
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  fqg_frame* fr = nullptr;
-  if ((rc = fqg_frame_retain(c, &fr))) return rc;
-  if (ix->frames.empty()) {
-    ix->fmt = st->readname_format;
-    ix->is_pe = st->is_pe;
-  }
-  ix->flags |= fr->flags;
-  IndexSeg sg;
-  sg.img = fr->fv.img;
-  sg.line_end = fr->fv.line_end;
-  sg.nbytes = fr->fv.nbytes;
-  sg.n_records = fr->fv.n_records;
-  sg.record_base = ix->n_records_total;
-  ix->frames.push_back(fr);
-  ix->segs.push_back(sg);
-  // on any failure below the frame stays registered with the index (freed by fqg_index_destroy), but its records do
-  // not count: n_records_total / inserted only move once the insert has succeeded
-  if (2 * (ix->inserted + sg.n_records) > ix->capacity) {
-    // grow first (re-inserting the earlier segments), then insert this one
-    ix->segs.pop_back();
-    ix->frames.pop_back();
-    rc = index_grow(ix, ix->inserted + sg.n_records);
-    ix->frames.push_back(fr);
-    ix->segs.push_back(sg);
-    if (rc) {
-      ix->segs.back().n_records = 0;
-      return rc;
-    }
-  }
-  auto drop = [&](int code) {
-    ix->segs.back().n_records = 0;  // (kept for ownership only)
-    return code;
-  };
-  if ((rc = index_reserve_records(ix, ix->n_records_total + sg.n_records))) return drop(rc);
-  if ((rc = index_upload_segs(ix))) return drop(rc);
-  if ((rc = index_reset_call(c))) return drop(rc);
-  const bool captured = names_usable(c, fr->fv, st, ix->keep_names);
-  if (sg.n_records && captured) {
-    if ((rc = names_prepare(c, fr->fv))) return drop(rc);
-    const int built = names_build(c, ix, fr->fv, st, sg.record_base);
-    if (built < 0) return drop(built);
-    if (built == 1) {
-      if ((rc = index_reset_call(c))) return drop(rc);
-      ProfScope ps(c, "k_names_insert");
-      launch_names_pass(c, false, fr->fv, index_view(ix), st, sg.record_base, nullptr);
-    }
-    ProfScope ps(c, "k_names_rest");
-    hipLaunchKernelGGL(k_names_rest<false>, dim3(c->cu_count * 4), dim3(kBlock), 0, c->stream, fr->fv, c->names, index_view(ix),
-                       st->readname_format, st->is_pe, sg.record_base, (unsigned long long*)nullptr, c->d_icall);
-  } else if (sg.n_records) {
-    ProfScope ps(c, "k_index_insert");
-    hipLaunchKernelGGL(k_index_insert, dim3(index_grid(c, sg.n_records)), dim3(kBlock), 0, c->stream, fr->fv,
-                       index_view(ix), sg.record_base, c->d_icall);
-  }
-  if ((rc = index_fetch_call(c))) return drop(rc);
-  if (hipGetLastError() != hipSuccess) return drop(fail(c, FQG_ERR_HIP, "k_index_insert"));
-  if (c->h_icall->table_full) return drop(fail(c, FQG_ERR_STATE, "name index full"));
-  if (sg.n_records && c->h_icall->seen != sg.n_records && !measured_wrong(captured && c->names.ablate)) return drop(fail(c, FQG_ERR_STATE, "name index: the pass did not meet every record once"));
-  c->last_names_captured = c->h_icall->captured;
-  ix->n_records_total += sg.n_records;
-  ix->inserted += c->h_icall->inserted;
-  ix->name_bytes += c->h_icall->name_bytes;
-  const uint64_t w = c->h_icall->first_wrong;
-  const uint64_t d = c->h_icall->first_dup == kNoRecord ? kNoRecord : c->h_icall->first_dup - sg.record_base;
-  if (w != kNoRecord && w < d) {
-    out->code = FQG_E_WRONG_HEADER;
-    out->record = w;
-  } else if (d != kNoRecord) {
-    out->code = FQG_E_DUP_NAME;
-    out->record = d;
-  }
-  if (w != kNoRecord || d != kNoRecord) ix->names_once = false;
-  out->n_entries = ix->inserted;
-  // sizeof(hashtable) + per entry sizeof(INDEX_ENTRY) + len + 1 + sizeof(hashnode)
-  out->index_mem = 8 + ix->inserted * (16 + 1 + 24) + ix->name_bytes;
-  return 0;
-}
-
-static int index_match_impl(fqg_ctx* c, fqg_index* ix, const fqg_file_state* st, uint64_t* match, fqg_index_result* out) {
-  if (!c || !ix || !st || !out || ix->ctx != c) return FQG_ERR_ARG;
-  if (!c->frame_valid) return fail(c, FQG_ERR_STATE, "no frame: call fqg_validate first");
-  if (const int irc = index_now(c)) return irc;
-  memset(out, 0, sizeof(*out));
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  if (!ix->claims.p && (rc = index_reserve_records(ix, std::max<uint64_t>(ix->n_records_total, 1)))) return rc;
-  if ((rc = index_upload_segs(ix))) return rc;
-  if ((rc = index_reset_call(c))) return rc;
-  const FrameView fv = c->frame;
-  unsigned long long *d_slot = nullptr, *d_match = nullptr;
-  if (match && fv.n_records) {
-    if ((rc = ensure(c, ix->found, fv.n_records * 8))) return rc;
-    if ((rc = ensure(c, ix->match, fv.n_records * 8))) return rc;
-    d_slot = (unsigned long long*)ix->found.p;
-    d_match = (unsigned long long*)ix->match.p;
-  }
-  if (fv.n_records) {
-    if (names_usable(c, fv, st, true)) {
-      if ((rc = names_prepare(c, fv))) return rc;
-      {
-        ProfScope ps(c, "k_names_match");
-        launch_names_pass(c, true, fv, index_view(ix), st, ix->n_askers_total, d_slot);
-      }
-      ProfScope ps(c, "k_names_rest");
-      hipLaunchKernelGGL(k_names_rest<true>, dim3(c->cu_count * 4), dim3(kBlock), 0, c->stream, fv, c->names, index_view(ix),
-                         st->readname_format, st->is_pe, ix->n_askers_total, d_slot, c->d_icall);
-    } else {
-      ProfScope ps(c, "k_index_match_delete");
-      hipLaunchKernelGGL(k_index_match_delete, dim3(index_grid(c, fv.n_records)), dim3(kBlock), 0, c->stream, fv,
-                         index_view(ix), st->readname_format, st->is_pe, (c->frame_flags & kFlagNul) ? 1 : 0,
-                         ix->n_askers_total, d_slot, c->d_icall);
-    }
-    if (match) {
-      {
-        ProfScope ps(c, "k_index_probe_resolve");
-        hipLaunchKernelGGL(k_index_probe_resolve, dim3((unsigned)((fv.n_records + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           c->stream, fv.n_records, (const unsigned long long*)d_slot, index_view(ix), ix->n_askers_total,
-                           d_match);
-      }
-      HIP_TRY(c, hipMemcpyAsync(match, d_match, fv.n_records * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-  }
-  if ((rc = index_fetch_call(c))) return rc;
-  HIP_TRY(c, hipGetLastError());
-  if (fv.n_records && c->h_icall->seen != fv.n_records && !measured_wrong(c->names.ablate)) return fail(c, FQG_ERR_STATE, "name index: the pass did not meet every record once");
-  c->last_names_captured = c->h_icall->captured;
-  ix->matched += c->h_icall->matched;
-  ix->n_askers_total += fv.n_records;
-  const uint64_t w = c->h_icall->first_wrong, m = c->h_icall->first_missing;
-  if (w != kNoRecord && w < m) {
-    out->code = FQG_E_WRONG_HEADER;
-    out->record = w;
-  } else if (m != kNoRecord) {
-    out->code = FQG_E_UNPAIRED;
-    out->record = m;
-  }
-  out->n_entries = ix->inserted - ix->matched;
-  out->index_mem = 8 + ix->inserted * (16 + 1 + 24) + ix->name_bytes;
-  return 0;
-}
-
-int fqg_index_match_delete(fqg_ctx* c, fqg_index* ix, const fqg_file_state* st, fqg_index_result* out) {
-  return index_match_impl(c, ix, st, nullptr, out);
-}
-
-int fqg_index_probe_delete(fqg_ctx* c, fqg_index* ix, const fqg_file_state* st, uint64_t* match, fqg_index_result* out) {
-  if (!match && c && c->frame_valid && c->frame.n_records) return FQG_ERR_ARG;
-  return index_match_impl(c, ix, st, match, out);
-}
-
-int fqg_index_alive(fqg_ctx* c, fqg_index* ix, uint8_t* alive, uint64_t cap) {
-  if (!c || !ix || ix->ctx != c || (!alive && cap)) return FQG_ERR_ARG;
-  if (cap < ix->n_records_total) return fail(c, FQG_ERR_ARG, "fqg_index_alive: buffer too small");
-  if (!ix->n_records_total) return 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = index_upload_segs(ix))) return rc;
-  uint8_t* d = nullptr;
-  if (hipMalloc((void**)&d, ix->n_records_total) != hipSuccess) return fail(c, FQG_ERR_NOMEM, "fqg_index_alive: device allocation failed");
-  (void)hipMemsetAsync(d, 0, ix->n_records_total, c->stream);
-  IndexView v = index_view(ix);
-  hipLaunchKernelGGL(k_index_alive, dim3((unsigned)((ix->capacity + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, v,
-                     ix->n_records_total, d);
-  hipError_t e = hipMemcpyAsync(alive, d, ix->n_records_total, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(c, FQG_ERR_HIP, "fqg_index_alive", e);
-  return 0;
-}
-
-int fqg_names_compare(fqg_ctx* c, const fqg_frame* a, const fqg_file_state* sa, const fqg_frame* b,
-                      const fqg_file_state* sb, fqg_index_result* out) {
-  if (!c || !a || !sa || !out || (b && !sb)) return FQG_ERR_ARG;
-  memset(out, 0, sizeof(*out));
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = index_reset_call(c))) return rc;
-  const int interleaved = b ? 0 : 1;
-  const uint64_t n_pairs = interleaved ? a->fv.n_records / 2 : std::min(a->fv.n_records, b->fv.n_records);
-  if (n_pairs) {
-    ProfScope ps(c, "k_names_compare");
-    const uint32_t fl = a->flags | (b ? b->flags : 0u);
-    hipLaunchKernelGGL(k_names_compare, dim3(index_grid(c, n_pairs)), dim3(kBlock), 0, c->stream, a->fv,
-                       sa->readname_format, sa->is_pe, b ? b->fv : a->fv, b ? sb->readname_format : sa->readname_format,
-                       b ? sb->is_pe : sa->is_pe, interleaved, (fl & kFlagNul) ? 1 : 0, n_pairs, c->d_icall);
-  }
-  if ((rc = index_fetch_call(c))) return rc;
-  HIP_TRY(c, hipGetLastError());
-  const uint64_t w = c->h_icall->first_wrong, m = c->h_icall->first_missing;
-  if (w != kNoRecord && w <= m) {
-    out->code = FQG_E_WRONG_HEADER;
-    out->record = interleaved ? 2 * w : w;
-  } else if (m != kNoRecord) {
-    out->code = interleaved ? FQG_E_UNPAIRED : FQG_E_NAME_MISMATCH;
-    out->record = interleaved ? 2 * m : m;
-  }
-  return 0;
-}
-
 // ---- barcode extraction ----------------------------------------------------------------------
 // Tile geometry for one call: T iterations whose records and output text fit `budget` bytes of LDS
 // per wavefront, from the mean record sizes (a tile that does not fit anyway takes the direct path).
@@ -2790,12 +2282,6 @@ int fqg_records_gather(fqg_ctx* c, const fqg_frame* frame, const uint64_t* recor
 }
 int fqg_records_gather_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) { return fqg_barcodes_output(c, 1, host_dst, nbytes); }
 
-uint64_t fqg_index_names_captured(const fqg_ctx* c) { return c ? c->last_names_captured : 0; }
-const fqg_frame* fqg_index_frame(const fqg_index* ix, uint64_t k) {
-  return (ix && k < ix->frames.size()) ? ix->frames[k] : nullptr;
-}
-uint64_t fqg_index_n_frames(const fqg_index* ix) { return ix ? ix->frames.size() : 0; }
-
 // ---- measurement ----------------------------------------------------------------------------
 int fqg_profile_enable(fqg_ctx* c, int on) {
   if (!c) return FQG_ERR_ARG;
@@ -2853,6 +2339,7 @@ int fqg_synth_fastq(fqg_ctx* c, void* device_out, uint64_t n_records, uint32_t r
 }
 
 #include "fqg_umi_abi.inc"
+#include "fqg_index_abi.inc"
 #include "fqg_fp_abi.inc"
 #include "fqg_bamtags_abi.inc"
 #include "fqg_bam2fastq_abi.inc"
