@@ -38,7 +38,8 @@ EXPORTS = [
     "fqg_records_gather_output", "fqg_records_split", "fqg_records_split_output", "fqg_records_split_info", "fqg_names_compare",
     "fqg_bam_header", "fqg_barcodes_transform", "fqg_barcodes_output", "fqg_barcodes_output_begin", "fqg_barcodes_output_wait", "fqg_records_filter", "fqg_records_filter_output",
     "fqg_records_filter_info",
-    "fqg_whitelist_create", "fqg_whitelist_destroy", "fqg_barcodes_whitelist",
+    "fqg_whitelist_create", "fqg_whitelist_destroy", "fqg_barcodes_whitelist", "fqg_barcodes_whitelist_correct",
+    "fqg_census_set_whitelist", "fqg_census_whitelist_info",
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
@@ -55,6 +56,7 @@ EXPORTS = [
 
 
 GZ_MEMBER_TEXT = 65280  # FQG_GZ_MEMBER_TEXT
+WL_MISS, WL_EXACT, WL_RESCUED, WL_AMBIGUOUS, WL_SHORT = 0, 1, 2, 3, 4  # FQG_WL_*: fqg_barcodes_whitelist_correct's status
 TEXT_RECORDS, TEXT_BAM2FASTQ, TEXT_BAM_TAGS = 0, 1, 2  # FQG_TEXT_*: the store fqg_text_deflate reads
 
 
@@ -297,6 +299,8 @@ def load():
     L.fqg_census_pairs.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64), u64]
     L.fqg_census_device_pairs.argtypes = [vp, C.c_int]
     L.fqg_census_device_pairs.restype = vp
+    L.fqg_census_set_whitelist.argtypes = [vp, vp, vp, C.c_int]
+    L.fqg_census_whitelist_info.argtypes = [vp, C.POINTER(u64)]
     L.fqg_barcodes_output_begin.argtypes = [vp, C.c_int, vp, u64]
     L.fqg_barcodes_output_wait.argtypes = [vp]
     L.fqg_records_filter.argtypes = [vp, vp, u64, u64, C.POINTER(FilterParams), C.POINTER(FilterResult)]
@@ -328,6 +332,8 @@ def load():
     L.fqg_whitelist_destroy.restype = None
     L.fqg_barcodes_whitelist.argtypes = [vp, vp, u64, u64, u64, C.c_int64, C.c_int64, vp, C.POINTER(C.c_uint8),
                                          C.POINTER(WhitelistResult)]
+    L.fqg_barcodes_whitelist_correct.argtypes = [vp, vp, u64, u64, u64, C.c_int64, C.c_int64, vp, C.c_int, C.POINTER(C.c_uint8),
+                                                 C.POINTER(u64), C.POINTER(WhitelistCorrectResult)]
     L.fqg_pack_barcode.argtypes = [C.c_char_p]
     L.fqg_pack_barcode.restype = u64
     L.fqg_unpack_barcode.argtypes = [u64, C.c_char_p]
@@ -436,6 +442,11 @@ class WhitelistResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_valid", C.c_uint64), ("n_short", C.c_uint64)]
 
 
+class WhitelistCorrectResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_exact", C.c_uint64), ("n_rescued", C.c_uint64), ("n_ambiguous", C.c_uint64),
+                ("n_short", C.c_uint64)]
+
+
 class Whitelist:
     """Device set of packed barcodes (fqg_whitelist): what load_whitelist builds from a --known_cells file."""
 
@@ -491,6 +502,18 @@ class Census:
 
     def device_pairs(self, which):
         return load().fqg_census_device_pairs(self.h, which)
+
+    def set_whitelist(self, wl, max_mismatch=0):
+        """from here on a pair is kept only when its cell is in the whitelist (max_mismatch 0: what bam_umi_count
+        --known_cells keeps) or, with max_mismatch 1, one substitution away from exactly one member, which then is the
+        pair's cell.  Only while the census holds no pair; None detaches.  Keep `wl` open while it is attached."""
+        self.ctx._check(load().fqg_census_set_whitelist(self.ctx.h, self.h, wl.h if wl is not None else None, max_mismatch))
+
+    def whitelist_info(self):
+        """pairs that were exact, rescued, ambiguous and dropped (the ambiguous ones among them) since the census was created"""
+        v = (C.c_uint64 * 4)()
+        self.ctx._check(load().fqg_census_whitelist_info(self.h, v))
+        return dict(zip(("exact", "rescued", "ambiguous", "dropped"), (int(x) for x in v)))
 
     def close(self):
         if self.h:
@@ -798,6 +821,27 @@ class Context:
         d = {k: int(getattr(r, k)) for k, _ in WhitelistResult._fields_}
         if want_flags:
             d["valid"] = flags[:n]
+        return d
+
+    def barcodes_whitelist_correct(self, frame, whitelist, offset, size, max_mismatch=0, n_records=None, first_record=0, step=1,
+                                   want_status=False, want_cells=False):
+        """fqg_barcodes_whitelist_correct: per record WL_EXACT / WL_RESCUED (max_mismatch 1: exactly one member of the
+        whitelist at Hamming distance 1) / WL_AMBIGUOUS / WL_MISS / WL_SHORT; returns the counts and, on request, one
+        status byte ("status") and one packed value ("cells": the member, 0 where there is none) per record"""
+        import numpy as np
+        n = frame.n_records if n_records is None else n_records
+        r = WhitelistCorrectResult()
+        status = np.zeros(max(1, n), dtype=np.uint8) if want_status else None
+        cells = np.zeros(max(1, n), dtype=np.uint64) if want_cells else None
+        self._check(load().fqg_barcodes_whitelist_correct(
+            self.h, frame.h, first_record, step, n, offset, size, whitelist.h, max_mismatch,
+            status.ctypes.data_as(C.POINTER(C.c_uint8)) if want_status else None,
+            cells.ctypes.data_as(C.POINTER(C.c_uint64)) if want_cells else None, C.byref(r)))
+        d = {k: int(getattr(r, k)) for k, _ in WhitelistCorrectResult._fields_}
+        if want_status:
+            d["status"] = status[:n]
+        if want_cells:
+            d["cells"] = cells[:n]
         return d
 
     def barcodes_output(self, which, nbytes, beside_next_call=False):

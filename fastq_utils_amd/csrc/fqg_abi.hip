@@ -160,6 +160,7 @@ struct fqg_ctx {
   bool frame_borrowed = false;   // the current frame is a retained frame made current again (fqg_frame_make_current)
   uint32_t frame_flags = 0;      // kFlagNul / kFlagCr of the framed image
   DevBuf bc_status, bc_len[3], bc_off[3], bc_sum[3], bc_tile_big;
+  DevBuf wl_cells;  // fqg_barcodes_whitelist_correct: one 8-byte value per record
   BcCall* d_bcall = nullptr;
   BcCall* h_bcall = nullptr;  // pinned
   // the text of the last transform (streams 0..2), filter or gather (1), split (1, 2); of the last fqg_bam_add_tags;
@@ -504,6 +505,7 @@ void fqg_close(fqg_ctx* c) {
   release(c->umi_entries[0]);
   release(c->umi_entries[1]);
   release(c->bc_status);
+  release(c->wl_cells);
   release(c->bc_tile_big);
   for (DevBuf* b : {&c->bam_in, &c->bam_off, &c->bam_size, &c->bam_local, &c->bam_sums, &c->bt_tables, &c->bt_call,
                     &c->b2f_call, &c->bc_text.buf, &c->bt_text.buf, &c->b2f_text.buf, &c->gz_text.buf, &c->gz_in, &c->gz_carry,
@@ -573,7 +575,7 @@ int fqg_release_scratch(fqg_ctx* c) {
   for (DevBuf* b : {&c->image, &c->tile_counts, &c->tile_local, &c->span_sums, &c->line_end, &c->records, &c->suspect, &c->list,
                     &c->stage, &c->cinfo, &c->queue, &c->redo, &c->lines_slow, &c->build_keys[0], &c->build_keys[1],
                     &c->build_cursor, &c->build_spill, &c->name_recs, &c->name_hcount, &c->name_redo, &c->name_redo_chunks,
-                    &c->bc_status, &c->bc_tile_big, &c->inf_out, &c->inf_raw, &c->inf_rows, &c->inf_status, &c->inf_first,
+                    &c->bc_status, &c->wl_cells, &c->bc_tile_big, &c->inf_out, &c->inf_raw, &c->inf_rows, &c->inf_status, &c->inf_first,
                     &c->bx_offsets, &c->bx_entries, &c->bx_counts, &c->bx_stretch, &c->bx_state})
     release(*b);
   c->inf_valid = false;  // (fqg_inflate_device: valid until here)
@@ -1871,6 +1873,12 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
 }
 
 // ---- census of what the transform kept (fqg_census_kernels.hip) -------------------------------------
+struct fqg_whitelist {
+  fqg_ctx* ctx = nullptr;
+  DevBuf set;
+  uint64_t capacity = 0;
+};
+
 struct fqg_census {
   fqg_ctx* ctx = nullptr;
   DevBuf cells, umis;     // the pairs, in arrival order until fqg_census_finish sorts them
@@ -1879,6 +1887,8 @@ struct fqg_census {
   uint64_t n_pairs = 0, n_cells = 0;
   unsigned umi_bits = 1, cell_bits = 1;  // bits the packed values of the batches so far can need (census_bits)
   bool finished = false;
+  const struct fqg_whitelist* wl = nullptr;  // fqg_census_set_whitelist: the caller's, alive while it is attached
+  int max_mismatch = 0;
 };
 
 // char2uint_64 of at most `size` characters is below 10^size: the sorts of fqg_census_finish need not look at more bits
@@ -1898,8 +1908,9 @@ int fqg_census_create(fqg_ctx* c, fqg_census** out) {
   HIP_TRY(c, hipSetDevice(c->device));
   std::unique_ptr<fqg_census> z(new fqg_census());
   z->ctx = c;
-  if (hipMalloc((void**)&z->d_count, 8) != hipSuccess) return fail(c, FQG_ERR_NOMEM, "fqg_census_create");
-  HIP_TRY(c, hipMemsetAsync(z->d_count, 0, 8, c->stream));
+  // the count of a call, and behind it the whitelist's four: pairs by status (kWlMiss .. kWlAmbiguous) since the census was created
+  if (hipMalloc((void**)&z->d_count, 5 * 8) != hipSuccess) return fail(c, FQG_ERR_NOMEM, "fqg_census_create");
+  HIP_TRY(c, hipMemsetAsync(z->d_count, 0, 5 * 8, c->stream));
   *out = z.release();
   return 0;
 }
@@ -1948,6 +1959,8 @@ int fqg_barcodes_census(fqg_ctx* c, fqg_census* z, const fqg_frame* const frames
   bool inter;
   int rc;
   if ((rc = bc_make_params(c, frames, states, first_record, bp, n_done, 0, P, inter))) return rc;
+  if (z->wl && z->max_mismatch && P.cell_read > 0 && (P.cell_size < 1 || P.cell_size > kWlMaxRescueSize))
+    return fail(c, FQG_ERR_ARG, "fqg_barcodes_census: a whitelist with max_mismatch 1 takes a cell_size of 1..19");
   if ((rc = census_reserve(c, z, z->n_pairs + n_done))) return rc;
   z->umi_bits = std::max(z->umi_bits, census_bits((long)P.umi_size));
   z->cell_bits = std::max(z->cell_bits, P.cell_read > 0 ? census_bits((long)P.cell_size) : 1u);
@@ -1956,9 +1969,15 @@ int fqg_barcodes_census(fqg_ctx* c, fqg_census* z, const fqg_frame* const frames
     ProfScope ps(c, "k_bc_census");
     const uint64_t tile = (uint64_t)kBlock * kCensusPer;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_done + tile - 1) / tile, (uint64_t)c->cu_count * 16));
-    hipLaunchKernelGGL(k_bc_census, dim3(grid), dim3(kBlock), 0, c->stream, P, n_done, (const uint8_t*)c->bc_status.p,
-                       (unsigned long long*)z->cells.p, (unsigned long long*)z->umis.p, (unsigned long long)z->n_pairs,
-                       (unsigned long long)(z->cells.cap / 8), z->d_count);
+    CensusWl W{nullptr, 0, z->d_count + 1, 0};
+    if (z->wl) W = CensusWl{(const WlSlot*)z->wl->set.p, z->wl->capacity - 1, z->d_count + 1, (uint32_t)z->max_mismatch};
+#define FQG_CENSUS(WL)                                                                                                          \
+  hipLaunchKernelGGL(k_bc_census<WL>, dim3(grid), dim3(kBlock), 0, c->stream, P, n_done, (const uint8_t*)c->bc_status.p,        \
+                     (unsigned long long*)z->cells.p, (unsigned long long*)z->umis.p, (unsigned long long)z->n_pairs,          \
+                     (unsigned long long)(z->cells.cap / 8), z->d_count, W)
+    if (z->wl) FQG_CENSUS(true);
+    else FQG_CENSUS(false);
+#undef FQG_CENSUS
   }
   unsigned long long added = 0;
   HIP_TRY(c, hipMemcpyAsync(&added, z->d_count, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2038,13 +2057,29 @@ const void* fqg_census_device_pairs(const fqg_census* z, int which) {
   return z ? (which ? z->umis.p : z->cells.p) : nullptr;
 }
 
-// ---- whitelist membership ---------------------------------------------------------------------
-struct fqg_whitelist {
-  fqg_ctx* ctx = nullptr;
-  DevBuf set;
-  uint64_t capacity = 0;
-};
+int fqg_census_set_whitelist(fqg_ctx* c, fqg_census* z, const fqg_whitelist* wl, int max_mismatch) {
+  if (!c || !z || z->ctx != c) return FQG_ERR_ARG;
+  if (wl && wl->ctx != c) return fail(c, FQG_ERR_ARG, "fqg_census_set_whitelist: a whitelist of another context");
+  if (max_mismatch != 0 && max_mismatch != 1) return fail(c, FQG_ERR_ARG, "fqg_census_set_whitelist: max_mismatch is 0 or 1");
+  if (z->n_pairs || z->finished)
+    return fail(c, FQG_ERR_ARG, "fqg_census_set_whitelist: the census holds pairs already");
+  z->wl = wl;
+  z->max_mismatch = wl ? max_mismatch : 0;
+  return 0;
+}
 
+int fqg_census_whitelist_info(const fqg_census* z, uint64_t info[4]) {
+  if (!z || !info) return FQG_ERR_ARG;
+  unsigned long long v[4] = {0, 0, 0, 0};
+  if (hipSetDevice(z->ctx->device) != hipSuccess || hipStreamSynchronize(z->ctx->stream) != hipSuccess ||
+      hipMemcpy(v, z->d_count + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+    return FQG_ERR_HIP;
+  info[0] = v[kWlExact], info[1] = v[kWlRescued], info[2] = v[kWlAmbiguous];
+  info[3] = v[kWlAmbiguous] + v[kWlMiss];  // dropped: what the look-up took away, the ambiguous ones among them
+  return 0;
+}
+
+// ---- whitelist membership (struct fqg_whitelist: above, in front of the census that may hold one) ----
 int fqg_whitelist_create(fqg_ctx* c, const uint64_t* packed, uint64_t n, fqg_whitelist** out) {
   if (!c || !out || (!packed && n)) return FQG_ERR_ARG;
   *out = nullptr;
@@ -2110,6 +2145,64 @@ int fqg_barcodes_whitelist(fqg_ctx* c, const fqg_frame* frame, uint64_t first, u
   HIP_TRY(c, hipGetLastError());
   out->n_valid = h_call->n_valid;
   out->n_short = h_call->n_short;
+  return 0;
+}
+
+int fqg_barcodes_whitelist_correct(fqg_ctx* c, const fqg_frame* frame, uint64_t first, uint64_t step, uint64_t n, int64_t offset,
+                                   int64_t size, const fqg_whitelist* wl, int max_mismatch, uint8_t* status, uint64_t* cells,
+                                   fqg_whitelist_correct_result* out) {
+  if (!c || !frame || !wl || !out || wl->ctx != c || frame->ctx != c) return FQG_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  if (offset < 0 || size < 1 || size > kWlMaxSize)
+    return fail(c, FQG_ERR_ARG, "fqg_barcodes_whitelist_correct: offset >= 0 and 1 <= size <= 56");
+  if (max_mismatch != 0 && max_mismatch != 1) return fail(c, FQG_ERR_ARG, "fqg_barcodes_whitelist_correct: max_mismatch is 0 or 1");
+  if (max_mismatch && size > kWlMaxRescueSize) return fail(c, FQG_ERR_ARG, "fqg_barcodes_whitelist_correct: max_mismatch 1 takes a size of 1..19");
+  if (frame->flags & kFlagNul) return fail(c, FQG_ERR_ARG, "fqg_barcodes_whitelist_correct: input holds NUL bytes");
+  if (step < 1 || (n && first + (n - 1) * step >= frame->fv.n_records))
+    return fail(c, FQG_ERR_ARG, "fqg_barcodes_whitelist_correct: records beyond the frame");
+  out->n_records = n;
+  if (!n) return 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  uint8_t* d_status = nullptr;
+  unsigned long long* d_cells = nullptr;
+  if (status) {
+    if ((rc = ensure(c, c->bc_status, n))) return rc;
+    d_status = (uint8_t*)c->bc_status.p;
+    c->bc_status_valid = 0;  // (the status bytes of the last transform are gone)
+  }
+  if (cells) {
+    if ((rc = ensure(c, c->wl_cells, n * 8))) return rc;
+    d_cells = (unsigned long long*)c->wl_cells.p;
+  }
+  static_assert(sizeof(WlCorrectCall) <= sizeof(BcCall), "the call's counters live in the context's BcCall");
+  static_assert(kWlMiss == FQG_WL_MISS && kWlExact == FQG_WL_EXACT && kWlRescued == FQG_WL_RESCUED &&
+                    kWlAmbiguous == FQG_WL_AMBIGUOUS && kWlShort == FQG_WL_SHORT,
+                "the kernels' status bytes are the header's");
+  WlCorrectCall* d_call = reinterpret_cast<WlCorrectCall*>(c->d_bcall);
+  HIP_TRY(c, hipMemsetAsync(d_call, 0, sizeof(WlCorrectCall), c->stream));
+  {
+    ProfScope ps(c, "k_bc_whitelist_correct");
+    // (8 workgroups of 4 wavefronts fill a CU; more of them only add to the counters more often)
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 8));
+#define FQG_WL(W)                                                                                                                 \
+  hipLaunchKernelGGL(k_bc_whitelist_correct<W>, dim3(grid), dim3(kBlock), 0, c->stream, frame->fv, first, step, n, (uint32_t)offset, \
+                     (uint32_t)size, (const WlSlot*)wl->set.p, wl->capacity - 1, (uint32_t)max_mismatch, d_status, d_cells, d_call)
+    if (size <= 16) FQG_WL(2);
+    else if (size <= 32) FQG_WL(4);
+    else FQG_WL(7);
+#undef FQG_WL
+  }
+  WlCorrectCall* h_call = reinterpret_cast<WlCorrectCall*>(c->h_bcall);
+  HIP_TRY(c, hipMemcpyAsync(h_call, d_call, sizeof(WlCorrectCall), hipMemcpyDeviceToHost, c->stream));
+  if (status) HIP_TRY(c, hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
+  if (cells) HIP_TRY(c, hipMemcpyAsync(cells, d_cells, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  out->n_exact = h_call->by_status[kWlExact];
+  out->n_rescued = h_call->by_status[kWlRescued];
+  out->n_ambiguous = h_call->by_status[kWlAmbiguous];
+  out->n_short = h_call->by_status[kWlShort];
   return 0;
 }
 

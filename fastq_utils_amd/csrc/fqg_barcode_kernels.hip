@@ -1747,4 +1747,184 @@ __global__ __launch_bounds__(kBlock) void k_bc_whitelist(FrameView f, uint64_t f
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// whitelist rescue (include/fqg.h: fqg_barcodes_whitelist_correct): a barcode that is no member, but has exactly one
+// member at Hamming distance 1, becomes that member.  On the packed value a substitution at string position p is one
+// decimal digit replaced: v + (o - d) * 10^p, d the digit there and o one of the four other digits of 1..5 (the first
+// character of the string is the LAST digit char2uint_64 adds: position p weighs 10^p).  4 * size neighbours - 64 for
+// the 16 bases of a 10x cell barcode: one probe per lane of a wavefront.
+//
+// Phase one is k_bc_whitelist's, lane by lane.  Phase two belongs to the wavefront (wl_rescue_wave): the lanes that
+// missed are found by ballot and served one after the other; the served lane's value and length are read by all
+// (readlane), lane i takes neighbour i (position i / 4, i & 3 of the other digits) - a second pass for 17..19
+// characters - and the number of hits and the one hit come back by ballot, popcount and readlane.  The neighbours of
+// one value are distinct values and the table holds every key once: the number of hits is |C|.  A member of another
+// length than the barcode has another number of digits than any neighbour (no digit of a neighbour is 0): never a hit.
+// ------------------------------------------------------------------------------------------
+enum : uint32_t { kWlMiss = 0, kWlExact = 1, kWlRescued = 2, kWlAmbiguous = 3, kWlShort = 4 };  // FQG_WL_*
+constexpr int kWlMaxRescueSize = 19;  // digits that cannot wrap in 64 bits
+struct WlCorrectCall {
+  unsigned long long by_status[5];  // records by kWl* status
+};
+__device__ const unsigned long long kWlPow10[kWlMaxRescueSize + 1] = {1ull,
+                                                                      10ull,
+                                                                      100ull,
+                                                                      1000ull,
+                                                                      10000ull,
+                                                                      100000ull,
+                                                                      1000000ull,
+                                                                      10000000ull,
+                                                                      100000000ull,
+                                                                      1000000000ull,
+                                                                      10000000000ull,
+                                                                      100000000000ull,
+                                                                      1000000000000ull,
+                                                                      10000000000000ull,
+                                                                      100000000000000ull,
+                                                                      1000000000000000ull,
+                                                                      10000000000000000ull,
+                                                                      100000000000000000ull,
+                                                                      1000000000000000000ull,
+                                                                      10000000000000000000ull};
+
+__device__ __forceinline__ bool wl_member(const WlSlot* __restrict__ set, uint64_t mask, uint64_t v) {
+  for (uint64_t at = wl_hash(v) & mask;; at = (at + 1) & mask) {  // (load <= 1/4: an empty slot ends every chain)
+    const WlSlot s = set[at];
+    if (!s.used) return false;
+    if (s.key == v) return true;
+  }
+}
+__device__ __forceinline__ uint64_t wl_readlane64(uint64_t v, int src) {  // src: the same in every lane
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+// the digits of a packed value of n <= 19 characters, 3 bits each, the digit of 10^p at bit 3p
+__device__ __forceinline__ uint64_t wl_digits(uint64_t v, uint32_t n) {
+  uint64_t dig = 0;
+  for (uint32_t p = 0; p < n; ++p) {
+    const uint64_t q = v / 10ull;
+    dig |= (v - q * 10ull) << (3u * p);
+    v = q;
+  }
+  return dig;
+}
+// Every lane of the wavefront calls this together (no lane may have left: the probes of one lane's barcode are made by
+// all 64).  need: this lane's barcode v of n characters (1..19, all of them bases) is no member.  Returns the lane's
+// status (kWlMiss where !need) and, for kWlRescued, the member in *out.
+__device__ __forceinline__ uint32_t wl_rescue_wave(const WlSlot* __restrict__ set, uint64_t mask, bool need, uint64_t v, uint32_t n,
+                                                   int lane, uint64_t* out) {
+  uint32_t st = kWlMiss;
+  const uint64_t dig = need ? wl_digits(v, n) : 0ull;
+  unsigned long long todo = __ballot(need);
+  while (todo) {
+    const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
+    todo &= todo - 1ull;
+    const uint64_t sv = wl_readlane64(v, src), sdig = wl_readlane64(dig, src);
+    const uint32_t total = 4u * (uint32_t)__builtin_amdgcn_readlane((int)n, src);
+    uint32_t hits = 0;
+    uint64_t hit = 0;
+    for (uint32_t i0 = 0; i0 < total; i0 += 64u) {  // one pass up to 16 characters, two for 17..19
+      const uint32_t i = i0 + (uint32_t)lane;
+      bool found = false;
+      uint64_t cand = 0;
+      if (i < total) {
+        const uint32_t p = i >> 2;
+        const uint32_t d = (uint32_t)(sdig >> (3u * p)) & 7u;  // 1..5
+        const uint32_t o = (d + (i & 3u)) % 5u + 1u;           // the four others
+        cand = sv + (uint64_t)(int64_t)((int)o - (int)d) * kWlPow10[p];
+        found = wl_member(set, mask, cand);
+      }
+      const unsigned long long m = __ballot(found);
+      hits += (uint32_t)__builtin_popcountll(m);
+      if (m) hit = wl_readlane64(cand, __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m)));
+    }
+    if (lane == src) {
+      st = hits == 1u ? kWlRescued : hits ? kWlAmbiguous : kWlMiss;
+      *out = hit;
+    }
+  }
+  return st;
+}
+
+template <int WORDS>  // 8-byte words that hold the barcode
+__global__ __launch_bounds__(kBlock) void k_bc_whitelist_correct(FrameView f, uint64_t first, uint64_t step, uint64_t n, uint32_t offset,
+                                                                 uint32_t size, const WlSlot* __restrict__ set, uint64_t mask,
+                                                                 uint32_t max_mismatch, uint8_t* __restrict__ status,
+                                                                 unsigned long long* __restrict__ cells,
+                                                                 WlCorrectCall* __restrict__ call) {
+  unsigned long long cnt[5] = {0, 0, 0, 0, 0};  // by status
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  const int lane = lane_id();
+  // (the wavefront stays together: its lanes beyond n idle through the round, they do not leave it)
+  for (uint64_t k0 = (uint64_t)blockIdx.x * kBlock + (threadIdx.x & ~63u); k0 < n; k0 += stride) {
+    const uint64_t k = k0 + (uint64_t)lane;
+    const bool in = k < n;
+    uint32_t st = kWlShort;
+    uint64_t v = 0;
+    bool stopped = false;
+    if (in) {
+      const uint64_t r = first + k * step;
+      const uint64_t b = f.line_end[4 * r] + 1, e = f.line_end[4 * r + 1];  // the sequence line
+      if ((uint64_t)offset + size <= e - b) {
+        const uint8_t* p = f.img + b + offset;
+        uint64_t w[WORDS];
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) {
+          w[i] = 0;
+          if (8u * i < size) {
+            if (b + offset + 8u * i + 8u <= f.nbytes) __builtin_memcpy(&w[i], p + 8 * i, 8);
+            else
+              for (uint32_t q = 0; q < 8 && 8u * i + q < size; ++q) w[i] |= (uint64_t)p[8 * i + q] << (8 * q);
+          }
+        }
+#pragma unroll
+        for (int pos = 8 * WORDS - 1; pos >= 0; --pos) {
+          const uint32_t u = (uint32_t)(w[pos >> 3] >> (8 * (pos & 7))) & 0xDFu;
+          const uint32_t base = u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
+          if ((uint32_t)pos < size && !stopped) {
+            if (!base) stopped = true;
+            else v = v * 10 + base;
+          }
+        }
+        st = wl_member(set, mask, v) ? kWlExact : kWlMiss;
+      }
+    }
+    if (max_mismatch) {  // (the same in every lane; size <= 19 - the host has checked)
+      uint64_t to = 0;
+      const uint32_t r = wl_rescue_wave(set, mask, in && st == kWlMiss && !stopped, v, size, lane, &to);
+      if (r != kWlMiss) {
+        st = r;
+        v = to;
+      }
+    }
+    if (in) {
+      if (status) status[k] = (uint8_t)st;
+      if (cells) cells[k] = st == kWlExact || st == kWlRescued ? v : 0ull;
+#pragma unroll
+      for (int s = 0; s < 5; ++s) cnt[s] += st == (uint32_t)s ? 1ull : 0ull;
+    }
+  }
+  // Shuffle, then one add per WORKGROUP and counter: the adds of a launch go to one cache line and are served one
+  // after the other (~90 per microsecond).  One per wavefront and counter, as k_bc_whitelist does it, was most of this
+  // kernel's time as soon as a second counter was not zero (0.50 ms -> 0.87 ms for 8 M reads).
+  __shared__ unsigned long long s_cnt[kBlock / 64][5];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) cnt[s] += __shfl_down(cnt[s], d, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) s_cnt[threadIdx.x >> 6][s] = cnt[s];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) sum += s_cnt[w][threadIdx.x];
+    if (sum) atomicAdd(&call->by_status[threadIdx.x], sum);
+  }
+}
+
 }  // namespace fqg

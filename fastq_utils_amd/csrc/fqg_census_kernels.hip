@@ -107,14 +107,26 @@ __device__ __forceinline__ uint32_t census_value(const uint8_t* __restrict__ s, 
 // wavefront adds to once per 64 reads is the whole kernel's clock: ~90 adds per microsecond to one address).  The order of
 // the pairs in the arrays is of no consequence - fqg_census_finish sorts them.
 constexpr int kCensusPer = 4;
+// WL: a whitelist is attached (fqg_census_set_whitelist).  The cell is looked up where it is packed: the pair is kept
+// for a member (kWlExact) or, with max_mismatch 1, for a cell one substitution away from exactly one member
+// (kWlRescued, wl_rescue_wave: the pair then carries that member).  The census's own rules come first - a read without
+// a pair is never looked up.  <false> is the kernel as it was: nothing of the look-up is compiled into it.
+struct CensusWl {
+  const WlSlot* set;
+  unsigned long long mask;
+  unsigned long long* info;  // pairs by kWl* status (miss, exact, rescued, ambiguous): added to, never cleared
+  uint32_t max_mismatch;
+};
+template <bool WL>
 __global__ __launch_bounds__(kBlock) void k_bc_census(BcParams P, uint64_t n_done, const uint8_t* __restrict__ status,
                                                       unsigned long long* __restrict__ cells, unsigned long long* __restrict__ umis,
                                                       unsigned long long base, unsigned long long cap,
-                                                      unsigned long long* __restrict__ count) {
+                                                      unsigned long long* __restrict__ count, CensusWl W) {
   __shared__ uint32_t s_wave[kBlock / 64];
   __shared__ unsigned long long s_base;
   const uint64_t tile = (uint64_t)kBlock * kCensusPer;
   const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+  unsigned long long wl_cnt[4] = {0, 0, 0, 0};  // (WL) this lane's pairs by kWl* status
   for (uint64_t t0 = (uint64_t)blockIdx.x * tile; t0 < n_done; t0 += (uint64_t)gridDim.x * tile) {
     unsigned long long cell[kCensusPer], umi[kCensusPer];
     uint32_t at[kCensusPer];  // my slot among the wavefront's pairs of this round; ~0u: no pair
@@ -124,6 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_bc_census(BcParams P, uint64_t n_don
       const uint64_t k = t0 + (uint64_t)j * kBlock + threadIdx.x;
       bool have = k < n_done && status[k] == kBcKeep;
       cell[j] = umi[j] = 0;
+      uint32_t wl_n = 0;  // (WL) characters of the cell value
       if (have) {
         uint32_t n = 0, cn = 0, qn = 0;
         const uint8_t *s = nullptr, *cs = nullptr, *q = nullptr;
@@ -142,6 +155,23 @@ __global__ __launch_bounds__(kBlock) void k_bc_census(BcParams P, uint64_t n_don
         }
         // no UMI tag: bam_umi_count does not count the alignment (src/bam_umi_count.c:960); a value with a '_': no tags
         if (!n || n == ~0u || cn == ~0u) have = false;
+        if (WL) wl_n = cn;
+      }
+      if (WL) {
+        uint32_t st = kWlMiss;
+        if (have && wl_member(W.set, W.mask, cell[j])) st = kWlExact;
+        if (W.max_mismatch) {  // (cell_size <= 19 - the host has checked; all wl_n characters are bases: wl_n digits)
+          uint64_t to = 0;
+          const bool need = have && st == kWlMiss && wl_n >= 1u && wl_n <= (uint32_t)kWlMaxRescueSize && cell[j] >= kWlPow10[wl_n - 1u];
+          const uint32_t r = wl_rescue_wave(W.set, W.mask, need, cell[j], wl_n, lane, &to);
+          if (r != kWlMiss) {
+            st = r;
+            cell[j] = to;
+          }
+        }
+#pragma unroll
+        for (uint32_t s = 0; s < 4; ++s) wl_cnt[s] += have && st == s ? 1ull : 0ull;
+        have = have && (st == kWlExact || st == kWlRescued);
       }
       const unsigned long long m = __ballot(have);
       at[j] = have ? mine + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull)) : ~0u;
@@ -170,6 +200,22 @@ __global__ __launch_bounds__(kBlock) void k_bc_census(BcParams P, uint64_t n_don
       }
     }
     __syncthreads();  // (s_wave and s_base are written again in the next round)
+  }
+  if constexpr (WL) {  // one add per workgroup and counter (k_bc_whitelist_correct: why not one per wavefront)
+    __shared__ unsigned long long s_cnt[kBlock / 64][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) wl_cnt[s] += __shfl_down(wl_cnt[s], d, 64);
+      if (lane == 0) s_cnt[wave][s] = wl_cnt[s];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      unsigned long long sum = 0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) sum += s_cnt[w][threadIdx.x];
+      if (sum) atomicAdd(&W.info[threadIdx.x], sum);
+    }
   }
 }
 

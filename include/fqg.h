@@ -436,6 +436,40 @@ int fqg_barcodes_whitelist(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_
                            int64_t offset, int64_t size, const fqg_whitelist *wl, uint8_t *valid,
                            fqg_whitelist_result *out);
 
+/* ---- whitelist rescue: a barcode one mismatch away from a known cell ------------------------------------
+ * Not a reference result: bam_umi_count drops a cell that is not on the list (its README points to `umis count`,
+ * "which will try to correct the barcodes").  This is the rule single-cell pipelines apply, and its definition here
+ * is the contract.  s: the `size` bytes at `offset` of the sequence line (bounds as above); P: char2uint_64; W: the
+ * values given to fqg_whitelist_create.  Per record one status (FQG_WL_*, fqg_codes.h) and one value:
+ *   FQG_WL_EXACT      P(s) is in W - exactly fqg_barcodes_whitelist's `valid`, quirks included (a string that packs
+ *                     to 0 is a member if 0 is; a byte that is no base cuts the packing).  The value is P(s).
+ *   FQG_WL_RESCUED    not exact, max_mismatch == 1, every byte of s is one of ACGTNacgtn, and exactly one member of
+ *                     W is P(s') for an s' over ACGTN that differs from s in exactly one position (on the packed
+ *                     value: one decimal digit replaced by another digit of 1..5).  The value is that member.
+ *   FQG_WL_AMBIGUOUS  as above, with two or more such members.  No value (0).
+ *   FQG_WL_MISS       everything else - a non-exact s that holds a byte that is no base among them.  No value.
+ *   FQG_WL_SHORT      the read is too short: no barcode.
+ * An exact hit is never examined for neighbours.  max_mismatch is 0 or 1; with 1, size must be <= 19 (the digits
+ * that cannot wrap in 64 bits), with 0 sizes up to 56 work as in fqg_barcodes_whitelist; anything else is
+ * FQG_ERR_ARG.  status (one byte per record) and cells (one value per record) are host memory; either may be NULL. */
+typedef struct {
+  uint64_t n_records, n_exact, n_rescued, n_ambiguous, n_short;
+} fqg_whitelist_correct_result;
+int fqg_barcodes_whitelist_correct(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_record, uint64_t step,
+                                   uint64_t n_records, int64_t offset, int64_t size, const fqg_whitelist *wl,
+                                   int max_mismatch, uint8_t *status, uint64_t *cells, fqg_whitelist_correct_result *out);
+/* The census with a whitelist: fqg_barcodes_census looks the cell up where it packs it and appends the pair only for
+ * FQG_WL_EXACT or FQG_WL_RESCUED, with the value above as the cell (s: the cell value as the census packs it).  With
+ * max_mismatch 0 that is what bam_umi_count --known_cells keeps (valid_barcode, src/bam_umi_count.c:523-535).  The
+ * census's own rules run first and are unchanged: no UMI - no pair, a '_' in a value - no pair, a missing cell is cell
+ * 0, which is then kept if and only if 0 is in W.  Allowed only while the census holds no pair (FQG_ERR_ARG
+ * otherwise); NULL detaches.  The whitelist is the caller's and has to live while it is attached.  A cell_size beyond
+ * 19 with max_mismatch 1 is refused by the next fqg_barcodes_census.
+ * fqg_census_whitelist_info: pairs that were exact, rescued, ambiguous, and dropped (every pair the look-up took away,
+ * the ambiguous ones among them) since the census was created. */
+int fqg_census_set_whitelist(fqg_ctx *ctx, fqg_census *census, const fqg_whitelist *wl, int max_mismatch);
+int fqg_census_whitelist_info(const fqg_census *census, uint64_t info[4]);
+
 /* ---- per-record filters (fastq_filter_n, fastq_trim_poly_at) ------------------------------------
  * Replaces the record loops of fastq_filter_n (src/fastq_filter_n.c:75-91: count N/n in the sequence,
  * drop the record when there are more than read_len * max_n / 100) and of fastq_trim_poly_at

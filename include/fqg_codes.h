@@ -113,6 +113,13 @@ enum fqg_code {
 #define FQG_NAME_NOP 2
 #define FQG_NAME_UNDEF (-1)
 
+/* Not reference outcomes.  fqg_barcodes_whitelist_correct: what a record's barcode is to the whitelist (fqg.h) */
+#define FQG_WL_MISS 0
+#define FQG_WL_EXACT 1
+#define FQG_WL_RESCUED 2
+#define FQG_WL_AMBIGUOUS 3
+#define FQG_WL_SHORT 4
+
 /* src/fastq.h:48 */
 #define FQG_SPACE_SEQ 0
 #define FQG_SPACE_COLOUR 1
