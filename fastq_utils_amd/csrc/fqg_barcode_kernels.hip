@@ -1687,7 +1687,48 @@ __host__ __device__ inline uint64_t wl_hash(uint64_t x) {
 }
 constexpr int kWlMaxSize = 56;  // barcode characters (the reference's arrays hold 49)
 
+// char2uint_64's digit of a character: A C G T N (either case - & 0xDF folds it) -> 1..5, every other character 0
+__device__ __forceinline__ uint32_t wl_base(uint32_t c) {
+  const uint32_t u = c & 0xDFu;
+  return u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
+}
+// The `size` characters at byte `at` of the image, packed; *stopped: a character that is no base ended the value early.
+// Whole words while they lie inside the image; the last bytes of an image one by one.
 template <int WORDS>  // 8-byte words that hold the barcode
+__device__ __forceinline__ uint64_t wl_pack_at(const FrameView& f, uint64_t at, uint32_t size, bool* stopped) {
+  const uint8_t* p = f.img + at;
+  uint64_t w[WORDS];
+#pragma unroll
+  for (int i = 0; i < WORDS; ++i) {
+    w[i] = 0;
+    if (8u * i < size) {
+      if (at + 8u * i + 8u <= f.nbytes) __builtin_memcpy(&w[i], p + 8 * i, 8);
+      else
+        for (uint32_t q = 0; q < 8 && 8u * i + q < size; ++q) w[i] |= (uint64_t)p[8 * i + q] << (8 * q);
+    }
+  }
+  uint64_t v = 0;
+  bool stop = false;
+#pragma unroll
+  for (int pos = 8 * WORDS - 1; pos >= 0; --pos) {
+    const uint32_t base = wl_base((uint32_t)(w[pos >> 3] >> (8 * (pos & 7))));
+    if ((uint32_t)pos < size && !stop) {
+      if (!base) stop = true;
+      else v = v * 10 + base;
+    }
+  }
+  *stopped = stop;
+  return v;
+}
+__device__ __forceinline__ bool wl_member(const WlSlot* __restrict__ set, uint64_t mask, uint64_t v) {
+  for (uint64_t at = wl_hash(v) & mask;; at = (at + 1) & mask) {  // (load <= 1/4: an empty slot ends every chain)
+    const WlSlot s = set[at];
+    if (!s.used) return false;
+    if (s.key == v) return true;
+  }
+}
+
+template <int WORDS>
 __global__ __launch_bounds__(kBlock) void k_bc_whitelist(FrameView f, uint64_t first, uint64_t step, uint64_t n, uint32_t offset,
                                                          uint32_t size, const WlSlot* __restrict__ set, uint64_t mask,
                                                          uint8_t* __restrict__ valid, WlCall* __restrict__ call) {
@@ -1699,39 +1740,8 @@ __global__ __launch_bounds__(kBlock) void k_bc_whitelist(FrameView f, uint64_t f
     bool ok = false;
     if ((uint64_t)offset + size > e - b) ++n_short;  // (offset + size > read_len - 1, read_len = strlen(seq) with its '\n')
     else {
-      const uint8_t* p = f.img + b + offset;
-      uint64_t w[WORDS];
-#pragma unroll
-      for (int i = 0; i < WORDS; ++i) {
-        w[i] = 0;
-        // (whole words while they lie inside the image; the last bytes of an image one by one)
-        if (8u * i < size) {
-          if (b + offset + 8u * i + 8u <= f.nbytes) __builtin_memcpy(&w[i], p + 8 * i, 8);
-          else
-            for (uint32_t q = 0; q < 8 && 8u * i + q < size; ++q) w[i] |= (uint64_t)p[8 * i + q] << (8 * q);
-        }
-      }
-      uint64_t v = 0;
-      bool stopped = false;
-#pragma unroll
-      for (int pos = 8 * WORDS - 1; pos >= 0; --pos) {
-        const uint32_t c = (uint32_t)(w[pos >> 3] >> (8 * (pos & 7))) & 0xFFu;
-        // A C G T N (either case) -> 1 2 3 4 5: c & 0xDF folds the case
-        const uint32_t u = c & 0xDFu;
-        const uint32_t base = u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
-        if ((uint32_t)pos < size && !stopped) {
-          if (!base) stopped = true;
-          else v = v * 10 + base;
-        }
-      }
-      for (uint64_t at = wl_hash(v) & mask;; at = (at + 1) & mask) {
-        const WlSlot s = set[at];
-        if (!s.used) break;
-        if (s.key == v) {
-          ok = true;
-          break;
-        }
-      }
+      bool stopped;
+      ok = wl_member(set, mask, wl_pack_at<WORDS>(f, b + offset, size, &stopped));
     }
     if (valid) valid[k] = ok ? 1 : 0;
     n_valid += ok ? 1 : 0;
@@ -1787,13 +1797,6 @@ __device__ const unsigned long long kWlPow10[kWlMaxRescueSize + 1] = {1ull,
                                                                       1000000000000000000ull,
                                                                       10000000000000000000ull};
 
-__device__ __forceinline__ bool wl_member(const WlSlot* __restrict__ set, uint64_t mask, uint64_t v) {
-  for (uint64_t at = wl_hash(v) & mask;; at = (at + 1) & mask) {  // (load <= 1/4: an empty slot ends every chain)
-    const WlSlot s = set[at];
-    if (!s.used) return false;
-    if (s.key == v) return true;
-  }
-}
 __device__ __forceinline__ uint64_t wl_readlane64(uint64_t v, int src) {  // src: the same in every lane
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
@@ -1847,6 +1850,28 @@ __device__ __forceinline__ uint32_t wl_rescue_wave(const WlSlot* __restrict__ se
   return st;
 }
 
+// N counters of every lane summed over the workgroup and added to dst[0 .. N).  Shuffle, then one add per WORKGROUP
+// and counter: the adds of a launch go to one cache line and are served one after the other (~90 per microsecond).
+// One per wavefront and counter, as k_bc_whitelist does it, was most of k_bc_whitelist_correct's time as soon as a
+// second counter was not zero (0.50 ms -> 0.87 ms for 8 M reads).
+template <int N>
+__device__ __forceinline__ void wl_add_counters(unsigned long long (&cnt)[N], unsigned long long* __restrict__ dst) {
+  __shared__ unsigned long long s_cnt[kBlock / 64][N];
+#pragma unroll
+  for (int s = 0; s < N; ++s) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt[s] += __shfl_down(cnt[s], d, 64);
+    if (lane_id() == 0) s_cnt[threadIdx.x >> 6][s] = cnt[s];
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) sum += s_cnt[w][threadIdx.x];
+    if (sum) atomicAdd(&dst[threadIdx.x], sum);
+  }
+}
+
 template <int WORDS>  // 8-byte words that hold the barcode
 __global__ __launch_bounds__(kBlock) void k_bc_whitelist_correct(FrameView f, uint64_t first, uint64_t step, uint64_t n, uint32_t offset,
                                                                  uint32_t size, const WlSlot* __restrict__ set, uint64_t mask,
@@ -1867,26 +1892,7 @@ __global__ __launch_bounds__(kBlock) void k_bc_whitelist_correct(FrameView f, ui
       const uint64_t r = first + k * step;
       const uint64_t b = f.line_end[4 * r] + 1, e = f.line_end[4 * r + 1];  // the sequence line
       if ((uint64_t)offset + size <= e - b) {
-        const uint8_t* p = f.img + b + offset;
-        uint64_t w[WORDS];
-#pragma unroll
-        for (int i = 0; i < WORDS; ++i) {
-          w[i] = 0;
-          if (8u * i < size) {
-            if (b + offset + 8u * i + 8u <= f.nbytes) __builtin_memcpy(&w[i], p + 8 * i, 8);
-            else
-              for (uint32_t q = 0; q < 8 && 8u * i + q < size; ++q) w[i] |= (uint64_t)p[8 * i + q] << (8 * q);
-          }
-        }
-#pragma unroll
-        for (int pos = 8 * WORDS - 1; pos >= 0; --pos) {
-          const uint32_t u = (uint32_t)(w[pos >> 3] >> (8 * (pos & 7))) & 0xDFu;
-          const uint32_t base = u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
-          if ((uint32_t)pos < size && !stopped) {
-            if (!base) stopped = true;
-            else v = v * 10 + base;
-          }
-        }
+        v = wl_pack_at<WORDS>(f, b + offset, size, &stopped);
         st = wl_member(set, mask, v) ? kWlExact : kWlMiss;
       }
     }
@@ -1905,26 +1911,7 @@ __global__ __launch_bounds__(kBlock) void k_bc_whitelist_correct(FrameView f, ui
       for (int s = 0; s < 5; ++s) cnt[s] += st == (uint32_t)s ? 1ull : 0ull;
     }
   }
-  // Shuffle, then one add per WORKGROUP and counter: the adds of a launch go to one cache line and are served one
-  // after the other (~90 per microsecond).  One per wavefront and counter, as k_bc_whitelist does it, was most of this
-  // kernel's time as soon as a second counter was not zero (0.50 ms -> 0.87 ms for 8 M reads).
-  __shared__ unsigned long long s_cnt[kBlock / 64][5];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int s = 0; s < 5; ++s) cnt[s] += __shfl_down(cnt[s], d, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int s = 0; s < 5; ++s) s_cnt[threadIdx.x >> 6][s] = cnt[s];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) sum += s_cnt[w][threadIdx.x];
-    if (sum) atomicAdd(&call->by_status[threadIdx.x], sum);
-  }
+  wl_add_counters(cnt, call->by_status);
 }
 
 }  // namespace fqg

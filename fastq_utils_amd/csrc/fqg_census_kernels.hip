@@ -9,7 +9,7 @@
 // bytes), cuts the same characters get_barcode cut (bc_get), and packs them as char2uint_64 packs the tag values - a
 // (cell, UMI) pair of two 64-bit words per kept read that has a UMI (bam_umi_count skips an alignment without one,
 // :960; a read without a cell barcode has the cell 0, as char2uint_64 of a missing tag gives).  The pairs are sorted by
-// (cell, UMI) (rocPRIM radix sort, fqg_abi.hip) and k_census_* turn the sorted pairs into one line per cell: reads and
+// (cell, UMI) (rocPRIM radix sort, fqg_barcode_abi.inc) and k_census_* turn the sorted pairs into one line per cell: reads and
 // distinct UMIs - bam_umi_count's per-cell totals before a gene tag exists.
 #include "fqg_device.h"
 #include "fqg_tile.h"
@@ -21,12 +21,11 @@ struct CensusCell {
 };
 
 // char2uint_64 (src/bam_umi_count.c:364-382) on the n characters at s: from the last character backwards, base 10
-// digits A C G T N = 1..5 (either case), stopping at the first character that is none of them
+// digits A C G T N = 1..5 (either case: wl_base), stopping at the first character that is none of them
 __device__ __forceinline__ unsigned long long census_pack(const uint8_t* __restrict__ s, uint32_t n) {
   unsigned long long v = 0;
   for (uint32_t i = n; i-- > 0;) {
-    const uint32_t u = (uint32_t)s[i] & 0xDFu;
-    const uint32_t base = u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
+    const uint32_t base = wl_base(s[i]);
     if (!base) break;
     v = v * 10ull + base;
   }
@@ -72,8 +71,7 @@ __device__ __forceinline__ unsigned long long census_pack_w(const uint64_t (&w)[
   bool go = true;
 #pragma unroll
   for (int i = 31; i >= 0; --i) {
-    const uint32_t u = (uint32_t)(w[i >> 3] >> (8 * (i & 7))) & 0xDFu;
-    const uint32_t base = u == 'A' ? 1u : u == 'C' ? 2u : u == 'G' ? 3u : u == 'T' ? 4u : u == 'N' ? 5u : 0u;
+    const uint32_t base = wl_base((uint32_t)(w[i >> 3] >> (8 * (i & 7))));
     const bool in = (uint32_t)i < n;
     go = go && (!in || base != 0u);
     if (in && go) v = v * 10ull + base;
@@ -201,22 +199,7 @@ __global__ __launch_bounds__(kBlock) void k_bc_census(BcParams P, uint64_t n_don
     }
     __syncthreads();  // (s_wave and s_base are written again in the next round)
   }
-  if constexpr (WL) {  // one add per workgroup and counter (k_bc_whitelist_correct: why not one per wavefront)
-    __shared__ unsigned long long s_cnt[kBlock / 64][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) wl_cnt[s] += __shfl_down(wl_cnt[s], d, 64);
-      if (lane == 0) s_cnt[wave][s] = wl_cnt[s];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      unsigned long long sum = 0;
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w) sum += s_cnt[w][threadIdx.x];
-      if (sum) atomicAdd(&W.info[threadIdx.x], sum);
-    }
-  }
+  if constexpr (WL) wl_add_counters(wl_cnt, W.info);  // (one add per workgroup and counter)
 }
 
 // sorted by (cell, UMI): flag[i] = 1 where a new cell begins

@@ -425,7 +425,9 @@ const void *fqg_census_device_pairs(const fqg_census *census, int which);
  * on every line that fgets returns non-empty, in any order; repeats are fine); fqg_barcodes_whitelist answers, for
  * records first_record, first_record + step, ... of a retained frame, whether the `size` characters at `offset` of
  * the sequence line are a member.  A read too short for them (get_barcode's bounds, src/fastq_pre_barcodes.c:232)
- * has no barcode: not valid, counted in n_short.  valid (host memory, one byte per record) may be NULL. */
+ * has no barcode: not valid, counted in n_short.  valid (host memory, one byte per record) may be NULL.  With valid
+ * the call overwrites the status bytes of the context's last fqg_barcodes_transform: a fqg_barcodes_census behind
+ * it is FQG_ERR_STATE until the next transform. */
 typedef struct fqg_whitelist fqg_whitelist;
 typedef struct {
   uint64_t n_records, n_valid, n_short;
@@ -451,7 +453,8 @@ int fqg_barcodes_whitelist(fqg_ctx *ctx, const fqg_frame *frame, uint64_t first_
  *   FQG_WL_SHORT      the read is too short: no barcode.
  * An exact hit is never examined for neighbours.  max_mismatch is 0 or 1; with 1, size must be <= 19 (the digits
  * that cannot wrap in 64 bits), with 0 sizes up to 56 work as in fqg_barcodes_whitelist; anything else is
- * FQG_ERR_ARG.  status (one byte per record) and cells (one value per record) are host memory; either may be NULL. */
+ * FQG_ERR_ARG.  status (one byte per record) and cells (one value per record) are host memory; either may be NULL.
+ * With status, as fqg_barcodes_whitelist with valid: a fqg_barcodes_census behind it is FQG_ERR_STATE. */
 typedef struct {
   uint64_t n_records, n_exact, n_rescued, n_ambiguous, n_short;
 } fqg_whitelist_correct_result;

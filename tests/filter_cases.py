@@ -78,7 +78,7 @@ def budget_of(env=os.environ):
 
 
 def tile_for(nbytes, n_records, budget):
-    """bc_tile_for (fqg_abi.hip) for one FASTQ input that is printed as FASTQ -> (T, in_cap, out_cap)"""
+    """bc_tile_for (fqg_barcode_abi.inc) for one FASTQ input that is printed as FASTQ -> (T, in_cap, out_cap)"""
     r = nbytes / n_records
     t = (budget - (48.0 + 96.0)) / (1.06 * (r + (r + 100)) + 1.0)
     T = int(max(1.0, min(t, 64.0)))

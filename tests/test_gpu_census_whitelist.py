@@ -192,6 +192,86 @@ def test_10x_synthetic_exact_then_rescue():
         assert r["n_discarded"] > 0
 
 
+@pytest.mark.parametrize("n", [1, 64, 65])
+def test_a_cell_value_in_the_last_bytes_of_the_image(n):
+    """One file, the UMI its first base and the cell its second.  The last record is `@r\\nCA\\n+\\nII\\n`: 7 bytes lie
+    between its cell value and the image's end, so census_fetch leaves it to the byte-wise packer - plain, under a
+    whitelist that holds it, and under one that holds its neighbour `C` only (rescued)."""
+    rng = np.random.default_rng(n)
+    recs = []
+    for i in range(n - 1):
+        s = bytes(rng.choice(list(b"ACGTNacgt"), int(rng.integers(1, 9))).astype(np.uint8))   # (one base: too short, discarded)
+        recs.append(b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)))
+    img = b"".join(recs) + b"@r\nCA\n+\nII\n"
+    specs = {"umi": (A.READ1, 0, 1), "cell": (A.READ1, 1, 1), "sample": None}
+    args = ["--read1", "r.fastq", "--phred_encoding", "33", "--min_qual", "10", "--outfile1", "o.fastq.gz", "--umi_read", "read1",
+            "--umi_offset", "0", "--umi_size", "1", "--cell_read", "read1", "--cell_offset", "1", "--cell_size", "1"]
+    want = pbo.run_pre_barcodes(args, lambda name: img)
+    assert want["exit"] == 0
+    pairs = string_pairs(want["files"][1])
+    assert pairs[-1] == (b"A", wro.pack(b"C"))
+    with fq.Context(0) as ctx:
+        for lines in ([b"A"], [b"C"]):
+            compare(ctx, {A.READ1: img}, specs, {"phred": 33, "min_qual": 10}, pairs, lines)
+            kept, info = wro.census_filter(pairs[-1:], wro.members(lines), 1)
+            assert kept == [(wro.pack(lines[0]), wro.pack(b"C"))] and info["rescued"] == (lines == [b"C"])
+
+
+def frames_of(ctx, s):
+    frames, states = {}, {}
+    for x, img in ((A.READ1, s["r2"]), (A.INDEX1, s["r1"])):
+        st = A.probe_first_record(img, True)
+        ctx.validate(img, None, st, final=True, flags=A.VALIDATE_FRAME_ONLY)
+        frames[x], states[x] = ctx.retain_frame(), st
+    return frames, states
+
+
+KW_10X = dict(umi=(A.INDEX1, 16, 10), cell=(A.INDEX1, 0, 16), min_qual=10, sam=False)
+
+
+def test_a_whitelist_call_without_its_bytes_leaves_the_census_its_status_bytes():
+    s = synthetic()
+    with fq.Context(0) as ctx:
+        frames, states = frames_of(ctx, s)
+        w = A.Whitelist.from_lines(ctx, b"\n".join(s["pool"]) + b"\n")
+        z = ctx.census()
+        r = ctx.barcodes_transform(frames, states, s["n"], **KW_10X)
+        assert ctx.barcodes_whitelist(frames[A.INDEX1], w, 0, 16)["n_valid"] > 0
+        assert ctx.barcodes_whitelist_correct(frames[A.INDEX1], w, 0, 16, 1, want_cells=True)["n_rescued"] > 0
+        added = ctx.barcodes_census(z, frames, states, r["n_done"], **KW_10X)
+        n_pairs, _ = z.finish()
+        ce, um = z.pairs(n_pairs)
+        assert added == n_pairs and list(zip(ce.tolist(), um.tolist())) == sorted((wro.pack(c), u) for c, u in s["pairs"])
+        z.close()
+        w.close()
+        for f in frames.values():
+            f.release()
+
+
+@pytest.mark.parametrize("call", ["whitelist", "whitelist_correct"])
+def test_a_whitelist_call_that_writes_its_bytes_ends_the_transform_for_the_census(call):
+    """Both calls write their per-record bytes where the transform wrote its status bytes: a census behind them would
+    read 0 / 1 validity as keep / discard.  It is refused instead (FQG_ERR_STATE) until the next transform."""
+    s = synthetic()
+    with fq.Context(0) as ctx:
+        frames, states = frames_of(ctx, s)
+        w = A.Whitelist.from_lines(ctx, b"\n".join(s["pool"]) + b"\n")
+        z = ctx.census()
+        r = ctx.barcodes_transform(frames, states, s["n"], **KW_10X)
+        if call == "whitelist":
+            ctx.barcodes_whitelist(frames[A.INDEX1], w, 0, 16, want_flags=True)
+        else:
+            ctx.barcodes_whitelist_correct(frames[A.INDEX1], w, 0, 16, 1, want_status=True)
+        with pytest.raises(A.FqgError):
+            ctx.barcodes_census(z, frames, states, r["n_done"], **KW_10X)
+        r = ctx.barcodes_transform(frames, states, s["n"], **KW_10X)
+        assert ctx.barcodes_census(z, frames, states, r["n_done"], **KW_10X) == len(s["pairs"])
+        z.close()
+        w.close()
+        for f in frames.values():
+            f.release()
+
+
 def test_set_whitelist_is_refused_where_it_cannot_hold():
     s = synthetic()
     with fq.Context(0) as ctx:

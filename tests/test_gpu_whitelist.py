@@ -67,6 +67,42 @@ def test_membership_matches_the_reference_semantics(size, offset):
         frame.release()
 
 
+# The last record of a well-formed image whose barcode (one character at `offset`) has fewer than 8 bytes between its
+# first byte and the image's end - 6 and 7: the kernels' fetch (wl_pack_at) takes such a word byte by byte
+TAILS = {0: b"@r\nA\n+\nI\n", 1: b"@r\nCA\n+\nII\n"}
+
+
+def ends_at_the_image_end(rng, n, wl, offset):
+    """n records, the last of them TAILS[offset]"""
+    return make(rng, n - 1, wl, 1, offset)[0] + TAILS[offset]
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("n", [1, 64, 65])
+def test_a_barcode_in_the_last_bytes_of_the_image(n, offset):
+    rng = np.random.default_rng(10 * n + offset)
+    with fq.Context(0) as ctx:
+        for wl in ([b"A"], [b"C"]):
+            img = ends_at_the_image_end(rng, n, wl, offset)
+            assert len(img) - (img.rindex(b"@r\n") + 3 + offset) == 6 + offset
+            members = {uo.char2uint_64(x + b"\n") for x in wl}
+            seqs = img.split(b"\n")[1::4]
+            want = np.array([0 if offset + 1 > len(s) else int(uo.char2uint_64(s[offset:offset + 1] + b"\n") in members) for s in seqs],
+                            dtype=np.uint8)
+            assert len(seqs) == n and want[-1] == (wl == [b"A"])
+            st = fq.abi.probe_first_record(img, False)
+            assert ctx.validate(img, None, st, flags=fq.abi.VALIDATE_FRAME_ONLY)["n_records"] == n
+            frame = ctx.retain_frame()
+            w = fq.abi.Whitelist.from_lines(ctx, b"".join(x + b"\n" for x in wl))
+            got = ctx.barcodes_whitelist(frame, w, offset, 1, want_flags=True)
+            assert (got["valid"] == want).all(), np.nonzero(got["valid"] != want)[0][:10]
+            assert (got["n_records"], got["n_valid"]) == (n, int(want.sum()))
+            assert got["n_short"] == sum(1 for s in seqs if offset + 1 > len(s))
+            assert ctx.barcodes_whitelist(frame, w, offset, 1)["n_valid"] == int(want.sum())   # ... without the bytes
+            w.close()
+            frame.release()
+
+
 def test_the_reference_fixture_whitelist():
     """tests/golden/data_umi's known_cells file as load_whitelist reads it, against the oracle's packing"""
     import os

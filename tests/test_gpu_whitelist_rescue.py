@@ -7,7 +7,7 @@ import pytest
 
 import fastq_utils_amd as fq
 from tests import whitelist_rescue_oracle as wro
-from tests.test_gpu_whitelist import ALPHA, make
+from tests.test_gpu_whitelist import ALPHA, ends_at_the_image_end, make
 
 pytestmark = pytest.mark.gpu
 M64 = (1 << 64) - 1
@@ -84,6 +84,19 @@ def test_record_counts_around_one_wavefront(n):
     img, _ = make(rng, n, wl, 16, 0)
     with fq.Context(0) as ctx:
         check(ctx, img, wl, 0, 16)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("n", [1, 64, 65])
+def test_a_barcode_in_the_last_bytes_of_the_image(n, offset):
+    """the last record's barcode is fetched byte by byte (tests/test_gpu_whitelist.py: TAILS): a member, and an `A`
+    beside the only member `C`; both modes, and max_mismatch 0 against fqg_barcodes_whitelist (check)"""
+    rng = np.random.default_rng(10 * n + offset)
+    with fq.Context(0) as ctx:
+        for wl, last in (([b"A"], wro.EXACT), ([b"C"], wro.RESCUED)):
+            img = ends_at_the_image_end(rng, n, wl, offset)
+            assert check(ctx, img, wl, offset, 1, modes=(0,))[-1] == (wro.EXACT if last == wro.EXACT else wro.MISS)
+            assert check(ctx, img, wl, offset, 1)[-1] == last
 
 
 @pytest.mark.parametrize("size", [20, 56])
