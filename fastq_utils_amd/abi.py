@@ -42,6 +42,7 @@ EXPORTS = [
     "fqg_census_set_whitelist", "fqg_census_whitelist_info",
     "fqg_census_create", "fqg_census_destroy", "fqg_barcodes_census", "fqg_census_finish", "fqg_census_cells",
     "fqg_census_pairs", "fqg_census_device_pairs",
+    "fqg_census_collapse_umis", "fqg_census_umis", "fqg_census_cells_collapsed", "fqg_census_append",
     "fqg_pack_barcode", "fqg_unpack_barcode", "fqg_bam_index_records", "fqg_bam_add_tags", "fqg_bam_add_tags_output",
     "fqg_bam2fastq", "fqg_bam2fastq_output", "fqg_deflate", "fqg_text_deflate", "fqg_deflate_output",
     "fqg_bgzf_deflate", "fqg_text_bgzf_deflate", "fqg_deflate_output_begin", "fqg_deflate_output_wait",
@@ -301,6 +302,10 @@ def load():
     L.fqg_census_device_pairs.restype = vp
     L.fqg_census_set_whitelist.argtypes = [vp, vp, vp, C.c_int]
     L.fqg_census_whitelist_info.argtypes = [vp, C.POINTER(u64)]
+    L.fqg_census_collapse_umis.argtypes = [vp, vp, C.c_int, C.POINTER(u64)]
+    L.fqg_census_umis.argtypes = [vp, vp, vp, u64]
+    L.fqg_census_cells_collapsed.argtypes = [vp, vp, C.POINTER(u64), u64]
+    L.fqg_census_append.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64), u64, C.c_int, C.c_int]
     L.fqg_barcodes_output_begin.argtypes = [vp, C.c_int, vp, u64]
     L.fqg_barcodes_output_wait.argtypes = [vp]
     L.fqg_records_filter.argtypes = [vp, vp, u64, u64, C.POINTER(FilterParams), C.POINTER(FilterResult)]
@@ -514,6 +519,40 @@ class Census:
         v = (C.c_uint64 * 4)()
         self.ctx._check(load().fqg_census_whitelist_info(self.h, v))
         return dict(zip(("exact", "rescued", "ambiguous", "dropped"), (int(x) for x in v)))
+
+    def append(self, cells, umis, cell_size, umi_size):
+        """pairs of packed values from host memory, taken as given (no whitelist look-up); until finish().  The sizes
+        bound the values as a batch's parameters do (<= 0: not known)."""
+        import numpy as np
+        ce = np.ascontiguousarray(cells, dtype=np.uint64)
+        um = np.ascontiguousarray(umis, dtype=np.uint64)
+        if ce.ndim != 1 or ce.shape != um.shape:
+            raise ValueError("cells and umis: two one-dimensional arrays of one length")
+        self.ctx._check(load().fqg_census_append(self.ctx.h, self.h, ce.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 um.ctypes.data_as(C.POINTER(C.c_uint64)), ce.size, cell_size, umi_size))
+
+    def collapse_umis(self, max_mismatch=1):
+        """behind finish(): the table of distinct (cell, UMI) with reads and, with max_mismatch 1, every UMI folded into the
+        strongest neighbour of its cell with strictly more reads (include/fqg.h).  -> n_umis, n_absorbed, n_roots, longest_chain"""
+        v = (C.c_uint64 * 4)()
+        self.ctx._check(load().fqg_census_collapse_umis(self.ctx.h, self.h, max_mismatch, v))
+        return dict(zip(("n_umis", "n_absorbed", "n_roots", "longest_chain"), (int(x) for x in v)))
+
+    UMI_ROW = [("cell", "<u8"), ("umi", "<u8"), ("reads", "<u8"), ("root", "<u8")]
+
+    def umis(self, n):
+        """structured numpy array of the first n table rows (cell, umi, reads, root), sorted by (cell, umi)"""
+        import numpy as np
+        out = np.zeros(max(1, n), dtype=self.UMI_ROW)
+        self.ctx._check(load().fqg_census_umis(self.ctx.h, self.h, out.ctypes.data_as(C.c_void_p), n))
+        return out[:n]
+
+    def cells_collapsed(self, n_cells):
+        """per line of cells(), in its order: the UMIs of the cell that are their own root"""
+        import numpy as np
+        out = np.zeros(max(1, n_cells), dtype=np.uint64)
+        self.ctx._check(load().fqg_census_cells_collapsed(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n_cells))
+        return out[:n_cells]
 
     def close(self):
         if self.h:

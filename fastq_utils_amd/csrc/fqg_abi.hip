@@ -23,6 +23,7 @@
 #include "fqg_names_build_kernels.hip"
 #include "fqg_barcode_kernels.hip"
 #include "fqg_census_kernels.hip"
+#include "fqg_census_umi_kernels.hip"
 #include "fqg_filter_kernels.hip"
 #include "fqg_split_kernels.hip"
 #include "fqg_umi_kernels.hip"

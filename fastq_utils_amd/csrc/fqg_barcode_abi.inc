@@ -341,6 +341,12 @@ struct fqg_census {
   bool finished = false;
   const struct fqg_whitelist* wl = nullptr;  // fqg_census_set_whitelist: the caller's, alive while it is attached
   int max_mismatch = 0;
+  // fqg_census_collapse_umis (fqg_census_umi_kernels.hip): the table of distinct (cell, UMI) rows and what led to it
+  bool umi_wide = false;   // a umi_size outside 1..19 was seen: the values may have twenty digits
+  bool collapsed = false;  // the last collapse call's results stand in u_table / u_cell_roots
+  uint64_t n_umis = 0;
+  DevBuf u_flag, u_local, u_sums, u_tot, u_umi, u_cid, u_head, u_reads, u_first, u_word, u_table, u_cell_roots, u_part;
+  DevBuf u_rot[2], u_perm[2], u_key[2], u_pos[2];  // the second order: in / out of its two sorts
 };
 
 // char2uint_64 of at most `size` characters is below 10^size: the sorts of fqg_census_finish need not look at more bits
@@ -371,6 +377,10 @@ void fqg_census_destroy(fqg_census* z) {
   if (!z) return;
   (void)hipStreamSynchronize(z->ctx->stream);
   for (DevBuf* b : {&z->cells, &z->umis, &z->cells2, &z->umis2, &z->tmp, &z->flag, &z->local, &z->sums, &z->lines}) release(*b);
+  for (DevBuf* b : {&z->u_flag, &z->u_local, &z->u_sums, &z->u_tot, &z->u_umi, &z->u_cid, &z->u_head, &z->u_reads, &z->u_first,
+                    &z->u_word, &z->u_table, &z->u_cell_roots, &z->u_part, &z->u_rot[0], &z->u_rot[1], &z->u_perm[0], &z->u_perm[1],
+                    &z->u_key[0], &z->u_key[1], &z->u_pos[0], &z->u_pos[1]})
+    release(*b);
   if (z->d_count) (void)hipFree(z->d_count);
   delete z;
 }
@@ -416,6 +426,7 @@ int fqg_barcodes_census(fqg_ctx* c, fqg_census* z, const fqg_frame* const frames
   if ((rc = census_reserve(c, z, z->n_pairs + n_done))) return rc;
   z->umi_bits = std::max(z->umi_bits, census_bits((long)P.umi_size));
   z->cell_bits = std::max(z->cell_bits, P.cell_read > 0 ? census_bits((long)P.cell_size) : 1u);
+  if (P.umi_read > 0 && (P.umi_size < 1 || P.umi_size > kWlMaxRescueSize)) z->umi_wide = true;
   HIP_TRY(c, hipMemsetAsync(z->d_count, 0, 8, c->stream));
   {
     ProfScope ps(c, "k_bc_census");
@@ -507,6 +518,175 @@ int fqg_census_pairs(fqg_ctx* c, fqg_census* z, uint64_t* cells, uint64_t* umis,
 
 const void* fqg_census_device_pairs(const fqg_census* z, int which) {
   return z ? (which ? z->umis.p : z->cells.p) : nullptr;
+}
+
+// pairs from host memory, taken as given (no whitelist look-up)
+int fqg_census_append(fqg_ctx* c, fqg_census* z, const uint64_t* cells, const uint64_t* umis, uint64_t n, int cell_size,
+                      int umi_size) {
+  if (!c || !z || z->ctx != c || ((!cells || !umis) && n)) return FQG_ERR_ARG;
+  if (z->finished) return fail(c, FQG_ERR_STATE, "fqg_census_append: the census is finished");
+  if (!n) return 0;
+  const int sizes[2] = {cell_size, umi_size};
+  const uint64_t* vals[2] = {cells, umis};
+  for (int k = 0; k < 2; ++k) {
+    if (sizes[k] < 1 || sizes[k] > kWlMaxRescueSize) continue;  // (unknown, or twenty digits and more: any value)
+    unsigned long long lim = 1;
+    for (int i = 0; i < sizes[k]; ++i) lim *= 10ull;
+    for (uint64_t i = 0; i < n; ++i)
+      if (vals[k][i] >= lim) return fail(c, FQG_ERR_ARG, "fqg_census_append: a value of more digits than its size");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = census_reserve(c, z, z->n_pairs + n))) return rc;
+  HIP_TRY(c, hipMemcpyAsync((unsigned long long*)z->cells.p + z->n_pairs, cells, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((unsigned long long*)z->umis.p + z->n_pairs, umis, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  z->umi_bits = std::max(z->umi_bits, census_bits(umi_size > 0 ? (long)umi_size : -1l));
+  z->cell_bits = std::max(z->cell_bits, census_bits(cell_size > 0 ? (long)cell_size : -1l));
+  if (umi_size < 1 || umi_size > kWlMaxRescueSize) z->umi_wide = true;
+  z->n_pairs += n;
+  return 0;
+}
+
+// ---- the census with UMI collapse (fqg_census_umi_kernels.hip) ---------------------------------------
+// bits a radix sort has to look at for keys below `count`
+static unsigned bits_below(uint64_t count) {
+  unsigned bits = 1;
+  while (bits < 64 && (1ull << bits) < count) ++bits;
+  return bits;
+}
+
+int fqg_census_collapse_umis(fqg_ctx* c, fqg_census* z, int max_mismatch, fqg_census_collapse_result* out) {
+  if (!c || !z || z->ctx != c || !out) return FQG_ERR_ARG;
+  *out = fqg_census_collapse_result{};
+  if (!z->finished) return fail(c, FQG_ERR_STATE, "fqg_census_collapse_umis: fqg_census_finish first");
+  if (max_mismatch != 0 && max_mismatch != 1) return fail(c, FQG_ERR_ARG, "fqg_census_collapse_umis: max_mismatch is 0 or 1");
+  if (max_mismatch && z->umi_wide) return fail(c, FQG_ERR_ARG, "fqg_census_collapse_umis: max_mismatch 1 takes a umi_size of 1..19");
+  HIP_TRY(c, hipSetDevice(c->device));
+  z->collapsed = false;
+  z->n_umis = 0;
+  const uint64_t n = z->n_pairs, n_cells = z->n_cells;
+  if (!n) {
+    z->collapsed = true;
+    return 0;
+  }
+  typedef unsigned long long u64;
+  int rc;
+  const uint64_t nb = scan64_spans(n);
+  if ((rc = ensure(c, z->u_flag, n * 4)) || (rc = ensure(c, z->u_local, n * 8)) || (rc = ensure(c, z->u_sums, nb * 8 + 8)) ||
+      (rc = ensure(c, z->u_tot, 3 * 8)))
+    return rc;
+  u64* d_tot = (u64*)z->u_tot.p;  // distinct pairs; rows with a parent, the longest chain (k_cu_roots)
+  HIP_TRY(c, hipMemsetAsync(d_tot, 0, 3 * 8, c->stream));
+  const unsigned grid_n = (unsigned)((n + kBlock - 1) / kBlock);
+  {
+    ProfScope ps(c, "k_cu_flags");
+    hipLaunchKernelGGL(k_cu_flags, dim3(grid_n), dim3(kBlock), 0, c->stream, (const u64*)z->cells.p, (const u64*)z->umis.p, n,
+                       (uint32_t*)z->u_flag.p);
+    scan64(c, z->u_flag.p, z->u_local.p, z->u_sums.p, d_tot, n);
+  }
+  u64 m64 = 0;
+  HIP_TRY(c, hipMemcpyAsync(&m64, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  const uint64_t m = m64;
+  if (!m || m > n || !n_cells) return fail(c, FQG_ERR_HIP, "fqg_census_collapse_umis: the count of distinct pairs");
+  if ((rc = ensure(c, z->u_umi, m * 8)) || (rc = ensure(c, z->u_cid, m * 4)) || (rc = ensure(c, z->u_head, (m + 1) * 4)) ||
+      (rc = ensure(c, z->u_reads, m * 4)) || (rc = ensure(c, z->u_first, (n_cells + 1) * 4)) || (rc = ensure(c, z->u_word, m * 8)) ||
+      (rc = ensure(c, z->u_table, m * sizeof(CensusUmi))) || (rc = ensure(c, z->u_cell_roots, n_cells * 8)) ||
+      (rc = ensure(c, z->u_part, ((m + kBlock - 1) / kBlock) * 16)))
+    return rc;
+  const unsigned ub = std::min(64u, z->umi_bits), cb = bits_below(n_cells);
+  size_t tmp_bytes = 0;
+  if (max_mismatch) {
+    for (int k = 0; k < 2; ++k)
+      if ((rc = ensure(c, z->u_rot[k], m * 8)) || (rc = ensure(c, z->u_perm[k], m * 4)) || (rc = ensure(c, z->u_key[k], m * 4)) ||
+          (rc = ensure(c, z->u_pos[k], m * 4)))
+        return rc;
+    size_t t1 = 0, t2 = 0;
+    if (rocprim::radix_sort_pairs(nullptr, t1, (u64*)z->u_rot[0].p, (u64*)z->u_rot[1].p, (uint32_t*)z->u_perm[0].p,
+                                  (uint32_t*)z->u_perm[1].p, m, 0, ub, c->stream) != hipSuccess ||
+        rocprim::radix_sort_pairs(nullptr, t2, (uint32_t*)z->u_key[0].p, (uint32_t*)z->u_key[1].p, (uint32_t*)z->u_pos[0].p,
+                                  (uint32_t*)z->u_pos[1].p, m, 0, cb, c->stream) != hipSuccess)
+      return fail(c, FQG_ERR_HIP, "fqg_census_collapse_umis: sort");
+    tmp_bytes = std::max(t1, t2);
+    if ((rc = ensure(c, z->tmp, tmp_bytes + 16))) return rc;
+  }
+  const unsigned grid_m = (unsigned)((m + kBlock - 1) / kBlock);
+  const u64* r_umi = (const u64*)z->u_umi.p;
+  const uint32_t *r_cid = (const uint32_t*)z->u_cid.p, *r_reads = (const uint32_t*)z->u_reads.p, *first = (const uint32_t*)z->u_first.p;
+  {
+    ProfScope ps(c, "k_cu_rows");
+    hipLaunchKernelGGL(k_cu_rows, dim3(grid_n), dim3(kBlock), 0, c->stream, (const u64*)z->umis.p, n, (const uint32_t*)z->u_flag.p,
+                       (const u64*)z->u_local.p, (const u64*)z->u_sums.p, (const uint32_t*)z->flag.p, (const u64*)z->local.p,
+                       (const u64*)z->sums.p, m, n_cells, (u64*)z->u_umi.p, (uint32_t*)z->u_cid.p, (uint32_t*)z->u_head.p,
+                       (uint32_t*)z->u_first.p);
+    hipLaunchKernelGGL(k_cu_prep, dim3(grid_m), dim3(kBlock), 0, c->stream, r_umi, (const uint32_t*)z->u_head.p, m,
+                       (uint32_t*)z->u_reads.p, max_mismatch ? (u64*)z->u_rot[0].p : nullptr, (uint32_t*)z->u_perm[0].p);
+  }
+  if (max_mismatch) {
+    {
+      ProfScope ps(c, "k_cu_run_a");
+      hipLaunchKernelGGL(k_cu_run<false>, dim3(grid_m), dim3(kBlock), 0, c->stream, r_umi, (const uint32_t*)nullptr, r_cid, first,
+                         r_reads, m, (u64*)z->u_word.p);
+    }
+    {
+      // the second order: by the rotated value, then (stable) by cell id; keys and rows gathered into that order
+      ProfScope ps(c, "k_cu_order");
+      if (rocprim::radix_sort_pairs(z->tmp.p, tmp_bytes, (u64*)z->u_rot[0].p, (u64*)z->u_rot[1].p, (uint32_t*)z->u_perm[0].p,
+                                    (uint32_t*)z->u_perm[1].p, m, 0, ub, c->stream) != hipSuccess)
+        return fail(c, FQG_ERR_HIP, "fqg_census_collapse_umis: sort");
+      hipLaunchKernelGGL(k_cu_gather_cid, dim3(grid_m), dim3(kBlock), 0, c->stream, (const uint32_t*)z->u_perm[1].p, r_cid, m,
+                         (uint32_t*)z->u_key[0].p, (uint32_t*)z->u_pos[0].p);
+      if (rocprim::radix_sort_pairs(z->tmp.p, tmp_bytes, (uint32_t*)z->u_key[0].p, (uint32_t*)z->u_key[1].p, (uint32_t*)z->u_pos[0].p,
+                                    (uint32_t*)z->u_pos[1].p, m, 0, cb, c->stream) != hipSuccess)
+        return fail(c, FQG_ERR_HIP, "fqg_census_collapse_umis: sort");
+      hipLaunchKernelGGL(k_cu_gather_rot, dim3(grid_m), dim3(kBlock), 0, c->stream, (const uint32_t*)z->u_pos[1].p,
+                         (const u64*)z->u_rot[1].p, (const uint32_t*)z->u_perm[1].p, m, (u64*)z->u_rot[0].p, (uint32_t*)z->u_perm[0].p);
+    }
+    {
+      ProfScope ps(c, "k_cu_run_b");
+      hipLaunchKernelGGL(k_cu_run<true>, dim3(grid_m), dim3(kBlock), 0, c->stream, (const u64*)z->u_rot[0].p,
+                         (const uint32_t*)z->u_perm[0].p, r_cid, first, r_reads, m, (u64*)z->u_word.p);
+    }
+  } else {
+    HIP_TRY(c, hipMemsetAsync(z->u_word.p, 0, m * 8, c->stream));
+  }
+  HIP_TRY(c, hipMemsetAsync(z->u_cell_roots.p, 0, n_cells * 8, c->stream));
+  {
+    ProfScope ps(c, "k_cu_roots");
+    hipLaunchKernelGGL(k_cu_roots, dim3(grid_m), dim3(kBlock), 0, c->stream, (const u64*)z->u_word.p, r_umi, r_cid, r_reads,
+                       (const CensusCell*)z->lines.p, m, (CensusUmi*)z->u_table.p, (u64*)z->u_cell_roots.p, (u64*)z->u_part.p);
+    hipLaunchKernelGGL(k_cu_totals, dim3(1), dim3(kBlock), 0, c->stream, (const u64*)z->u_part.p, (uint64_t)grid_m, d_tot + 1);
+  }
+  u64 tot[3] = {0, 0, 0};
+  HIP_TRY(c, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  z->n_umis = m;
+  z->collapsed = true;
+  out->n_umis = m;
+  out->n_absorbed = tot[1];
+  out->n_roots = m - tot[1];
+  out->longest_chain = tot[2];
+  return 0;
+}
+
+int fqg_census_umis(fqg_ctx* c, fqg_census* z, fqg_census_umi* out, uint64_t cap) {
+  if (!c || !z || z->ctx != c || (!out && cap)) return FQG_ERR_ARG;
+  if (!z->collapsed) return fail(c, FQG_ERR_STATE, "fqg_census_umis: fqg_census_collapse_umis first");
+  static_assert(sizeof(fqg_census_umi) == sizeof(CensusUmi), "the C-ABI row is the device row");
+  const uint64_t n = std::min<uint64_t>(cap, z->n_umis);
+  if (n) HIP_TRY(c, hipMemcpy(out, z->u_table.p, n * sizeof(CensusUmi), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int fqg_census_cells_collapsed(fqg_ctx* c, fqg_census* z, uint64_t* umis, uint64_t cap) {
+  if (!c || !z || z->ctx != c || (!umis && cap)) return FQG_ERR_ARG;
+  if (!z->collapsed) return fail(c, FQG_ERR_STATE, "fqg_census_cells_collapsed: fqg_census_collapse_umis first");
+  const uint64_t n = std::min<uint64_t>(cap, z->n_cells);
+  if (n) HIP_TRY(c, hipMemcpy(umis, z->u_cell_roots.p, n * 8, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int fqg_census_set_whitelist(fqg_ctx* c, fqg_census* z, const fqg_whitelist* wl, int max_mismatch) {

@@ -473,6 +473,43 @@ int fqg_barcodes_whitelist_correct(fqg_ctx *ctx, const fqg_frame *frame, uint64_
 int fqg_census_set_whitelist(fqg_ctx *ctx, fqg_census *census, const fqg_whitelist *wl, int max_mismatch);
 int fqg_census_whitelist_info(const fqg_census *census, uint64_t info[4]);
 
+/* ---- the census with UMI collapse: UMIs one mismatch away from a stronger UMI of the cell ----------------
+ * Not a reference result: bam_umi_count counts every distinct UMI, so a substitution inside a UMI is one more
+ * "distinct UMI" of its cell.  This is the fold single-cell pipelines apply before they count, and its definition here
+ * is the contract.  The census is finished.  Per cell c: U(c) the distinct packed UMI values of its pairs, r(c,u) the
+ * number of pairs with that value.  A packed value is what char2uint_64 made: decimal digits 1..5, the least
+ * significant digit the first base; the digit count d of a value is the length of the UMI.
+ *   neighbours  two values of the same digit count that differ in exactly one decimal digit.  The value 0 has none;
+ *               neither has a value with a digit that is not 1..5 (no UMI packs to one - fqg_census_append can bring it).
+ *   parent      parent(c,u): the neighbour v in U(c) with r(c,v) > r(c,u), strictly, that has the most reads; among
+ *               equally strong ones the smallest packed value.  None: u has no parent.  Equal reads never absorb.
+ *   root        follows parent until a value has none (reads grow strictly on the way); such a value is its own root.
+ *   scope       a cell never looks into another cell.
+ * fqg_census_collapse_umis makes the table of distinct (cell, UMI) rows with their reads and roots, all on the device.
+ * max_mismatch 0: every value is its own root (the table alone); 1: the rule above; anything else FQG_ERR_ARG.  With 1
+ * a census that ever saw a umi_size outside 1..19 (the digits that cannot wrap in 64 bits) is FQG_ERR_ARG.  Before
+ * fqg_census_finish: FQG_ERR_STATE.  The call may be repeated, with either value; the accessors return the last call's
+ * results.  n_absorbed: values with a parent; n_roots = n_umis - n_absorbed; longest_chain: the most parent steps any
+ * value took.  An empty census: all zeros.  fqg_census_cells / _pairs / _device_pairs are what they were.
+ * fqg_census_umis: the table, sorted by (cell, umi); per cell its rows are fqg_census_cell.umis many and their reads
+ * sum to fqg_census_cell.reads.  fqg_census_cells_collapsed: per line of fqg_census_cells, in its order, the values of
+ * the cell that are their own root.  Both: at most cap entries; FQG_ERR_STATE before a collapse call. */
+typedef struct {
+  uint64_t cell, umi, reads, root;
+} fqg_census_umi;
+typedef struct {
+  uint64_t n_umis, n_absorbed, n_roots, longest_chain;
+} fqg_census_collapse_result;
+int fqg_census_collapse_umis(fqg_ctx *ctx, fqg_census *census, int max_mismatch, fqg_census_collapse_result *out);
+int fqg_census_umis(fqg_ctx *ctx, fqg_census *census, fqg_census_umi *out, uint64_t cap);
+int fqg_census_cells_collapsed(fqg_ctx *ctx, fqg_census *census, uint64_t *umis, uint64_t cap);
+/* n pairs of packed values from host memory, taken as given: no whitelist look-up runs and fqg_census_whitelist_info
+ * does not change.  Allowed until fqg_census_finish (FQG_ERR_STATE behind it).  cell_size / umi_size bound the values
+ * as a batch's parameters do (the sorts look at the bits of 10^size; <= 0: not known, all 64): a value >= 10^size for a
+ * size of 1..19 is FQG_ERR_ARG and nothing is appended.  Pairs of another context or another run merge into one census. */
+int fqg_census_append(fqg_ctx *ctx, fqg_census *census, const uint64_t *cells, const uint64_t *umis, uint64_t n,
+                      int cell_size, int umi_size);
+
 /* ---- per-record filters (fastq_filter_n, fastq_trim_poly_at) ------------------------------------
  * Replaces the record loops of fastq_filter_n (src/fastq_filter_n.c:75-91: count N/n in the sequence,
  * drop the record when there are more than read_len * max_n / 100) and of fastq_trim_poly_at
