@@ -33,6 +33,7 @@
 #include "fqg_type_spans.h"
 #include "fqg_mark_pack.h"
 #include "fqg_part_steps.h"
+#include "fqg_line_window.h"
 
 namespace fqg {
 
@@ -1088,9 +1089,26 @@ __global__ __launch_bounds__(kBlock) void k_stream_lines(LinesArgs A, const uint
 // first and the last records of an image, reads of kilobases whose ranks spread over more chunks than the window
 // holds, chunks with more than 64 newlines) are marked for the general kernel, which runs behind this one on the marks;
 // an image whose chunks hold more than 64 newlines on average (reads below 100 bases) goes to the general kernel alone.
+//
+// What a step costs is vector-ALU issue, the currency pass 1 is short of when the two share a launch, so
+// whatever is one fact per wavefront is kept in scalar registers: the step, the window's first chunk (fqg_line_window.h:
+// integer arithmetic), the covering chunks, the flags of the call, the decision to store the index, the read length of
+// a step whose records share one.  The wavefront's number within the workgroup is declared uniform (readfirstlane) for
+// that: from threadIdx.x the compiler takes the whole step loop for divergent.
 // ------------------------------------------------------------------------------------------
 constexpr int kFastSlots = 16;
 constexpr int kFastRanks = 4 * kWave * kLinesPer + 1;  // 513: the ranks of 128 records and the one in front of them
+// a piece holds at most 64 of the 513 ranks: a step that qualifies is covered by 9 chunks or more, so the slots below
+// this one are never tested against n_cov
+constexpr int kFastSlotsMin = (kFastRanks + kWave - 1) / kWave;
+constexpr uint32_t kFastRow = (uint32_t)((kFastRanks + 7) & ~3);  // words of s_ent per wavefront: the ranks, then 7 words nobody reads
+static_assert(kFastSlotsMin == 9 && kFastSlotsMin <= kFastSlots, "slots of a step");
+static_assert(kLineWindowChunks == (uint32_t)kWave, "a window chunk per lane");
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+}
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
   return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) |
@@ -1100,7 +1118,7 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
 struct LinesFastLds {
   uint32_t hist[kLinesHist];
   unsigned long long red[3][kBlock / kWave];
-  __attribute__((aligned(16))) uint32_t ent[kBlock / kWave][(kFastRanks + 7) & ~3];
+  __attribute__((aligned(16))) uint32_t ent[kBlock / kWave][kFastRow];
 };
 // worker / n_workers: which workgroup of the persistent grid this is; the steps it shares are [A.step_lo, A.step_hi)
 // (step_hi = 0: up to the last step of the image)
@@ -1111,42 +1129,87 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
   auto& s_ent = lds.ent;
   for (int i = threadIdx.x; i < kLinesHist; i += kBlock) s_hist[i] = 0;
   __syncthreads();
-  const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint32_t* const row = &s_ent[wv][0];
   const uint64_t n_groups = (A.n_lines + 4 * kWave - 1) / (4 * kWave);
   const uint64_t n_steps_all = (n_groups + kLinesPer - 1) / kLinesPer;
-  const uint64_t n_steps = A.step_hi && A.step_hi < n_steps_all ? A.step_hi : n_steps_all;
-  const uint64_t wave0 = A.step_lo + (uint64_t)worker * (kBlock / kWave) + (threadIdx.x >> 6);
+  const uint64_t n_steps = uniform64(A.step_hi && A.step_hi < n_steps_all ? A.step_hi : n_steps_all);
+  const uint64_t wave0 = uniform64(A.step_lo + (uint64_t)worker * (kBlock / kWave) + (uint64_t)wv);
   const uint64_t n_waves = (uint64_t)n_workers * (kBlock / kWave);
-  const double chunks_per_line = A.n_newlines ? (double)A.cr.n_chunks / (double)A.n_newlines : 0.0;
-  uint32_t n_ok32 = 0, min_rl32 = ~0u, max_rl32 = 0;  // (a wavefront's share of the records and a step's lengths fit)
-  // the window of the NEXT step is requested a step ahead and looked at when that step begins (see k_stream_lines)
+  const uint32_t n_chunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.cr.n_chunks);
+  LineWindow lw = line_window(n_chunks, A.n_newlines);
+  lw.ratio = uniform64(lw.ratio);
+  lw.round = uniform64(lw.round);
+  lw.frac_bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)lw.frac_bits);
+  lw.last = (uint32_t)__builtin_amdgcn_readfirstlane((int)lw.last);
+  // the steps [1, whole_steps) have all their ranks staged, their records complete, room in the line index and in the
+  // suspect bitmap: one comparison per step (Rhi = 512 step + 512 <= x is step < x / 512; 128 records a step)
+  uint64_t whole_steps = A.n_newlines < A.limit ? A.n_newlines : A.limit;
+  whole_steps = (whole_steps < A.line_cap ? whole_steps : A.line_cap) / kPartStepRanks;
+  whole_steps = uniform64(whole_steps < A.suspect_cap / (kWave * kLinesPer) ? whole_steps : A.suspect_cap / (kWave * kLinesPer));
+  // the flags of the call, once, as bits of a scalar word (a boolean the compiler keeps as a lane mask is tested with
+  // two vector instructions each time)
+  enum : uint32_t { kHasAcc = 1, kIndexOnly = 2, kNoIndex = 4, kStoreIndex = 8, kSusAll = 16 };
+  const uint32_t call_flags = (uint32_t)__builtin_amdgcn_readfirstlane(
+      (int)((A.acc ? kHasAcc : 0u) | (A.index_only ? kIndexOnly : 0u) | (A.no_index ? kNoIndex : 0u) |
+            ((A.ablate & 1) ? 0u : kStoreIndex) | (A.space != FQG_SPACE_SEQ ? kSusAll : 0u)));
+  const uint32_t lo12 = in_vgpr(0xFFFu);  // (a three-register v_bitop3 issues in 2 cycles, with a scalar operand in 4)
+  // the lane's byte offset into the staged entries of a chunk, and into those of the eighth chunk behind it
+  const uint32_t off0 = as_computed(2u * (uint32_t)lane), off8 = as_computed(2u * (uint32_t)lane + 8u * (kStageCap * 2));
+  // Statistics and the length histogram.  Records of ONE length are the usual file: the records that share the length of
+  // their group's first counted record are counted in a scalar register, a run of groups with the same length at a time
+  // (run_len, run_cnt); when the length changes, and once behind the last step, the run goes to the histogram and to the
+  // wavefront's count, minimum and maximum (u_*).  The other records of a group - none in the usual file - add
+  // themselves to the histogram and to three words of the wavefront's row of s_ent that no entry reaches: nothing of
+  // them lives in vector registers across the steps.  (A wavefront's share of the records and a step's lengths fit 32 bits.)
+  constexpr uint32_t kOddOk = kFastRanks + 1, kOddMin = kFastRanks + 2, kOddMax = kFastRanks + 3;
+  static_assert(kOddMax < kFastRow, "the words behind the dump word");
+  if (lane == 0) {
+    row[kOddOk] = 0;
+    row[kOddMin] = ~0u;
+    row[kOddMax] = 0;
+  }
+  uint32_t u_ok = 0, u_min = ~0u, u_max = 0;
+  uint32_t run_len = 0, run_cnt = 0;
+  auto run_flush = [&]() {
+    if (!run_cnt) return;
+    u_ok += run_cnt;
+    u_min = run_len < u_min ? run_len : u_min;
+    u_max = run_len > u_max ? run_len : u_max;
+    if (lane == 0) {
+      if (run_len < (uint32_t)kLinesHist) atomicAdd(&s_hist[run_len], run_cnt);
+      else atomicAdd(&A.hist[run_len], (unsigned long long)A.weight * (unsigned long long)run_cnt);
+    }
+  };
+  // the window of the NEXT step is requested a step ahead and looked at when that step begins (see k_stream_lines): lane
+  // j asks for chunk cw + j - a scalar base and the lane's own offset, the last chunk where the table is shorter
+  const bool whole = n_chunks >= (uint32_t)kWave;  // every window lies inside the chunk table
+  const uint32_t beyond = as_computed((uint32_t)lane < n_chunks ? 0u : ~0u);  // (a vector register, not a lane mask to select by)
   unsigned long long nx_se = 0;
   uint32_t nx_loc = 0, nx_cnt = 0, nx_win = 0;
-  bool nx_in = false;
   auto window_request = [&](uint64_t step) {
-    const uint64_t g = (step < n_steps ? step : n_steps - 1) * kLinesPer;
-    const uint64_t Rw = g ? 4 * g * kWave - 1 : 0;
-    const double est = (double)Rw * chunks_per_line;
-    uint32_t cw = est > 2.0 ? (uint32_t)(est - 2.0) : 0u;
-    if (cw + kWave > A.cr.n_chunks) cw = A.cr.n_chunks > (uint32_t)kWave ? A.cr.n_chunks - kWave : 0u;
-    const uint32_t cm = cw + (uint32_t)lane;
-    nx_in = cm < A.cr.n_chunks;
-    const uint32_t cl = nx_in ? cm : A.cr.n_chunks - 1;
-    nx_se = A.cr.span_excl[cl / kScanSpan];
-    nx_loc = A.cr.local[cl];
-    nx_cnt = A.cr.counts[cl];
+    const uint64_t s = step < n_steps ? step : n_steps - 1;
+    const uint32_t cw = line_window_start(lw, s ? s * kPartStepRanks - 1 : 0);
+    uint32_t j = (uint32_t)lane;
+    if (!whole) j = j < n_chunks ? j : n_chunks - 1;  // (cw = 0)
+    const uint32_t in_span = ((cw % (uint32_t)kScanSpan) + j) / (uint32_t)kScanSpan;  // 0, or 1 behind a span's end
+    nx_se = (A.cr.span_excl + cw / (uint32_t)kScanSpan)[in_span];
+    nx_loc = (A.cr.local + cw)[j];
+    nx_cnt = (A.cr.counts + cw)[j];
     nx_win = cw;
   };
   if (wave0 < n_steps) window_request(wave0);
   for (uint64_t step = wave0; step < n_steps; step += n_waves) {
     // lane j holds window chunk j: its first rank and its number of newlines
-    const uint64_t w0 = nx_in ? nx_se + nx_loc : ~0ull;
-    const uint32_t wc = nx_in ? nx_cnt : 0u;
+    uint64_t w0 = nx_se + nx_loc;
+    uint32_t wc = nx_cnt;
     const uint32_t win0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)nx_win);  // (the same in every lane: scalar arithmetic below)
+    w0 |= (uint64_t)beyond | ((uint64_t)beyond << 32);  // (lanes beyond a table of fewer than 64 chunks: ~0 and no newline)
+    wc &= ~beyond;
     const uint64_t rb = step * (uint64_t)(kWave * kLinesPer);   // the step's first record
     const uint64_t Rlo = 4 * rb - 1, Rhi = 4 * rb + 4 * kWave * kLinesPer;  // its ranks: [Rlo, Rhi)
-    bool fast = rb > 0 && Rhi <= A.n_newlines && Rhi <= A.limit && Rhi <= A.line_cap &&
-                (rb / kWave + kLinesPer) * kWave <= A.suspect_cap;
+    bool fast = step > 0 && step < whole_steps;
     // the chunks the ranks live in: from the last chunk whose first rank is <= Rlo to the last whose first rank is < Rhi
     // (first ranks do not decrease along the window; lanes beyond the image hold ~0)
     const unsigned long long b_lo = __ballot(w0 <= Rlo), b_hi = __ballot(w0 < Rhi);
@@ -1155,13 +1218,17 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
     const int jfirst = __builtin_amdgcn_readfirstlane(__builtin_popcountll(b_lo) - 1);
     const int jlast = __builtin_amdgcn_readfirstlane(__builtin_popcountll(b_hi) - 1);
     const uint32_t n_cov = (uint32_t)(jlast - jfirst + 1);
-    if (fast && b_lo != 0) {
+    // where chunk j's first entry goes in s_ent (32-bit, may be "negative": the chunk begins in front of the step's ranks)
+    const uint32_t rel0 = (uint32_t)(w0 - Rlo);
+    if (fast && b_lo != 0 && n_cov >= (uint32_t)kFastSlotsMin && n_cov <= (uint32_t)kFastSlots) {
       // every covering chunk in ONE piece of 64 entries (reads of 100 bases and more), and the window holds the step's
-      // last rank too
-      const unsigned long long many = __ballot(lane >= jfirst && lane <= jlast && wc > (uint32_t)kWave);
-      const uint64_t last_r0 = readlane64(w0, jlast);
+      // last rank too.  (Chunk jfirst holds rank Rlo - the chunk behind it begins beyond - so with pieces of at most 64
+      // its rel0 is -63 .. 0, and that of every covering chunk fits 32 bits.)
+      const unsigned long long cover = (~0ull >> (63 - jlast)) & (~0ull << jfirst);
+      const unsigned long long many = __ballot(wc > (uint32_t)kWave) & cover;
+      const uint32_t last_rel = (uint32_t)__builtin_amdgcn_readlane((int)rel0, jlast);
       const uint32_t last_cnt = (uint32_t)__builtin_amdgcn_readlane((int)wc, jlast);
-      fast = many == 0 && n_cov <= (uint32_t)kFastSlots && last_r0 + last_cnt >= Rhi;
+      fast = many == 0 && last_rel + last_cnt >= (uint32_t)kFastRanks;
     } else fast = false;
     if (!__builtin_amdgcn_readfirstlane((int)fast)) {
       if (lane == 0) todo[step] = 1;  // (its one owner writes it: no atomic - a counter all steps append to was 3.5 ms
@@ -1171,101 +1238,130 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
     }
     // ---- every request of the step: the next step's window, then the staged entries chunk by chunk ----
     window_request(step + n_waves);
-    // where chunk j's first entry goes in s_ent (32-bit, may be "negative": the chunk begins in front of the step's ranks)
-    const uint32_t rel0 = (uint32_t)(w0 - Rlo);
+    // Slot sl takes the first 64 staged entries of chunk jfirst + sl, lane i entry i: one scalar base and the lane's own
+    // offset, no test per lane.  A chunk with fewer newlines gives its last lanes whatever the stage holds behind its
+    // entries (inside the chunk's kStageCap slots); those land where the entries of the chunks behind it belong and are
+    // overwritten by them - the first ranks of consecutive chunks differ by the newlines of the chunk between them, and
+    // the slots are written in order - or beyond the step's ranks, in the dump word.  Slots at and beyond n_cov are
+    // skipped by scalar branches; the requests of the others are all issued before the first of them is used.
     constexpr uint32_t kDump = (uint32_t)kFastRanks;  // a word of s_ent nobody reads: where entries outside the step go
     const uint16_t* const base0 = A.stage + (uint64_t)(win0 + (uint32_t)jfirst) * kStageCap;  // (uniform: scalar arithmetic)
-    uint16_t raw[kFastSlots];
+    // (the lane's offset as a 32-bit value of its own - off0, off8: a load takes the scalar base, the offset register and
+    // a constant of up to 4 KiB, eight slots; left to itself the compiler adds base and lane to a 64-bit address per
+    // wavefront and the constant to that, slot by slot, from the ninth slot on)
+    const uint8_t* const base_b = reinterpret_cast<const uint8_t*>(base0);
+    uint32_t raw[kFastSlots];
 #pragma unroll
     for (int sl = 0; sl < kFastSlots; ++sl) {
-      // (a chunk that is not needed asks for the first one again: no branch around a request)
-      const uint32_t cj = (uint32_t)sl < n_cov ? (uint32_t)sl : 0u;
-      const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane((int)wc, jfirst + (int)cj);
-      raw[sl] = base0[cj * (uint32_t)kStageCap + ((uint32_t)lane < cnt ? (uint32_t)lane : 0u)];
+      if (sl < kFastSlotsMin || (uint32_t)sl < n_cov) {
+        const uint8_t* const mine = base_b + (sl < 8 ? off0 : off8);
+        raw[sl] = *reinterpret_cast<const uint16_t*>(mine + (sl & 7) * (kStageCap * 2));
+      }
+      else raw[sl] = lo12;  // (any 32-bit value the compiler cannot see through: without one it keeps the sixteen as a
+                            // tuple of registers it spills, with a constant it narrows them to 16 bits and widens each again)
     }
 #pragma unroll
     for (int sl = 0; sl < kFastSlots; ++sl) {
-      const uint32_t cj = (uint32_t)sl < n_cov ? (uint32_t)sl : 0u;
-      const uint32_t cnt = (uint32_t)sl < n_cov ? (uint32_t)__builtin_amdgcn_readlane((int)wc, jfirst + (int)cj) : 0u;
-      const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)rel0, jfirst + (int)cj) + (uint32_t)lane;  // >= 2^31 in front of the step
-      // no branch: an entry that is not wanted lands in the dump word
-      s_ent[wv][((uint32_t)lane < cnt && idx < (uint32_t)kFastRanks) ? idx : kDump] = ((uint32_t)(jfirst + (int)cj) << 16) | (uint32_t)raw[sl];
+      if (!(sl < kFastSlotsMin || (uint32_t)sl < n_cov)) continue;
+      const uint32_t rel = (uint32_t)__builtin_amdgcn_readlane((int)rel0, jfirst + sl);
+      uint32_t chunk_hi = (uint32_t)(jfirst + sl) << 16;
+      asm("" : "+s"(chunk_hi));  // (one OR: what the compiler knows of the two halves it joins with a mask and a shift)
+      const uint32_t val = chunk_hi | raw[sl];
+      // chunk jfirst + sl begins at rank -63 .. 0 of the step (sl = 0), at 1 .. 64 sl behind it: only the first slot can
+      // reach in front of the step's ranks, only those from 513 - 64 - 7 ranks on can reach beyond the row
+      if (sl > 0 && 64 * sl + kWave - 1 < (int)kFastRow) row[rel + (uint32_t)lane] = val;
+      else {
+        const uint32_t idx = rel + (uint32_t)lane;  // >= 2^31 in front of the step
+        row[idx < kDump ? idx : kDump] = val;
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // ---- the line index, the checks, the statistics: every record of the step is complete ----
 #pragma unroll
     for (int q = 0; q < kLinesPer; ++q) {
-      const uint64_t g = step * kLinesPer + q;
-      const uint64_t r = g * kWave + (uint64_t)lane;
-      const uint64_t L0 = 4 * r;
+      const uint64_t g = step * kLinesPer + q;  // (scalar, like everything made of it)
+      uint32_t call = call_flags;
+      asm volatile("" : "+s"(call));  // (tested where it is used: hoisted out of the loop the tests become lane masks)
       const uint32_t at = 4u * ((uint32_t)q * kWave + (uint32_t)lane);   // entry of rank 4r - 1
-      const uint4 e03 = *reinterpret_cast<const uint4*>(&s_ent[wv][at]);  // (16-byte aligned: at is a multiple of 4)
-      const uint32_t en[5] = {e03.x, e03.y, e03.z, e03.w, s_ent[wv][at + 4]};
+      const uint4 e03 = *reinterpret_cast<const uint4*>(&row[at]);  // (16-byte aligned: at is a multiple of 4)
+      const uint32_t en[5] = {e03.x, e03.y, e03.z, e03.w, row[at + 4]};
       // positions relative to the window's first chunk, 32 bits (a step's ranks live in at most 16 chunks): the lengths
-      // and the checks need no more; the 64-bit ends only where the index is stored
+      // and the checks need no more; the 64-bit ends only where the index is stored.  An entry is chunk << 16 | staged
+      // entry (offset 12 bits, class and look-ahead above them): the offset as it is under the chunk moved down by four
       uint32_t rel[5];
 #pragma unroll
-      for (int k = 0; k < 5; ++k) rel[k] = ((en[k] >> 16) << 12) | (en[k] & 0xFFFu);
-      if (!(A.ablate & 1) && !(A.no_index && L0 + 4 <= A.keep_from)) {
-        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-        const uint64_t wbase = (uint64_t)win0 * kChunkBytes;
-        u64x2 lo2, hi2;
-        lo2.x = wbase + rel[1]; lo2.y = wbase + rel[2]; hi2.x = wbase + rel[3]; hi2.y = wbase + rel[4];
-        __builtin_nontemporal_store(lo2, reinterpret_cast<u64x2*>(A.line_end + L0));
-        __builtin_nontemporal_store(hi2, reinterpret_cast<u64x2*>(A.line_end + L0 + 2));
+      for (int k = 0; k < 5; ++k) rel[k] = __builtin_amdgcn_bitop3_b32(en[k] >> 4, en[k], lo12, 0xD8);  // (A & ~C) | (B & C)
+      // the index: a group in front of keep_from stores nothing - its LAST record decides for all of them -, and the
+      // addresses are formed only where something is stored
+      if ((call & kStoreIndex) && !((call & kNoIndex) && 4 * (g * kWave + (kWave - 1)) + 4 <= A.keep_from)) {
+        const uint64_t L0 = 4 * (g * kWave + (uint64_t)lane);
+        if (!((call & kNoIndex) && L0 + 4 <= A.keep_from)) {
+          typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+          const uint64_t wbase = (uint64_t)win0 * kChunkBytes;
+          u64x2 lo2, hi2;
+          lo2.x = wbase + rel[1]; lo2.y = wbase + rel[2]; hi2.x = wbase + rel[3]; hi2.y = wbase + rel[4];
+          __builtin_nontemporal_store(lo2, reinterpret_cast<u64x2*>(A.line_end + L0));
+          __builtin_nontemporal_store(hi2, reinterpret_cast<u64x2*>(A.line_end + L0 + 2));
+        }
       }
-      if (A.index_only) continue;
+      if (call & kIndexOnly) continue;
       // header line: '@' and not empty; third line: exactly "+\n"  (what the entry BEFORE a line says about it)
       bool sus = !(((en[0] >> 12) & 3u) == kClsAt && !((en[0] >> 14) & 1u));
       sus |= !(((en[2] >> 12) & 3u) == kClsPlus && ((en[2] >> 14) & 1u));
       const uint32_t l0 = rel[1] - rel[0] - 1, l1 = rel[2] - rel[1] - 1, l2 = rel[3] - rel[2] - 1, l3 = rel[4] - rel[3] - 1;
-      sus |= l1 < 1 || l1 != l3 || A.space != FQG_SPACE_SEQ;
+      sus |= l1 < 1 || l1 != l3;
       sus |= l0 + 1 > FQG_MAX_LABEL_LENGTH - 1 || l2 + 1 > FQG_MAX_LABEL_LENGTH - 1 ||
              l1 + 1 > FQG_MAX_READ_LENGTH - 1 || l3 + 1 > FQG_MAX_READ_LENGTH - 1;
-      const bool counted = A.acc && l1 + 1 <= FQG_MAX_READ_LENGTH - 1;
       const uint32_t rl = l1 + 1;  // strlen(seq): the sequence line ends in '\n'
-      if (counted) {
-        ++n_ok32;
-        min_rl32 = rl < min_rl32 ? rl : min_rl32;
-        max_rl32 = rl > max_rl32 ? rl : max_rl32;
-      }
-      {  // the length histogram: the lanes that share the first counted lane's length add once, together (see k_stream_lines)
-        const unsigned long long cm = __ballot(counted);
-        if (cm) {
-          const int first = __builtin_ctzll(cm);
-          const uint32_t rl0 = (uint32_t)__builtin_amdgcn_readlane((int)rl, first);
-          const bool with_first = counted && rl == rl0;
-          const unsigned long long same = __ballot(with_first);
-          if (lane == first) {
-            if (rl < (uint32_t)kLinesHist) atomicAdd(&s_hist[rl], (uint32_t)__builtin_popcountll(same));
-            else atomicAdd(&A.hist[rl], (unsigned long long)A.weight * (unsigned long long)__builtin_popcountll(same));
-          }
-          if (counted && !with_first) {
+      // statistics and the length histogram (above; 64 lanes adding 1 to one LDS word are 64 serialised atomics, see
+      // k_stream_lines)
+      const unsigned long long cm = (call & kHasAcc) ? __ballot(rl <= FQG_MAX_READ_LENGTH - 1) : 0ull;
+      if (cm) {
+        const bool counted = rl <= FQG_MAX_READ_LENGTH - 1;
+        const uint32_t rl0 = (uint32_t)__builtin_amdgcn_readlane((int)rl, __builtin_ctzll(cm));
+        const unsigned long long same = __ballot(counted && rl == rl0);
+        const uint32_t n_same = (uint32_t)__builtin_popcountll(same);
+        if (rl0 != run_len) {
+          run_flush();
+          run_len = rl0;
+          run_cnt = 0;
+        }
+        run_cnt += n_same;
+        if (same != cm) {
+          if (counted && rl != rl0) {
+            atomicAdd(&row[kOddOk], 1u);
+            atomicMin(&row[kOddMin], rl);
+            atomicMax(&row[kOddMax], rl);
             if (rl < (uint32_t)kLinesHist) atomicAdd(&s_hist[rl], 1u);
             else atomicAdd(&A.hist[rl], (unsigned long long)A.weight);
           }
         }
       }
-      const unsigned long long sm = __ballot(sus);
-      if (lane == 0 && sm) {
-        const uint64_t w = g * 2;
-        if ((uint32_t)sm) A.suspect_bits[w] = (uint32_t)sm;
-        if ((uint32_t)(sm >> 32)) A.suspect_bits[w + 1] = (uint32_t)(sm >> 32);
+      // the wavefront owns records g*64 .. g*64+63 = two whole words of the bitmap
+      const unsigned long long sm = (call & kSusAll) ? ~0ull : __ballot(sus);
+      if (sm) {
+        if (lane == 0) {
+          const uint64_t w = g * 2;
+          if ((uint32_t)sm) A.suspect_bits[w] = (uint32_t)sm;
+          if ((uint32_t)(sm >> 32)) A.suspect_bits[w + 1] = (uint32_t)(sm >> 32);
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();  // (s_ent is rewritten by the next step)
   }
+  run_flush();
   if (!A.acc) return;
-  unsigned long long n_ok = n_ok32, min_rl = min_rl32 == ~0u ? ~0ull : (unsigned long long)min_rl32, max_rl = max_rl32;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    n_ok += __shfl_down(n_ok, d, 64);
-    const unsigned long long a = __shfl_down(min_rl, d, 64), b = __shfl_down(max_rl, d, 64);
-    min_rl = a < min_rl ? a : min_rl;
-    max_rl = b > max_rl ? b : max_rl;
-  }
+  // the wavefront's count, minimum and maximum: the scalar share and what the other records left in its row
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  unsigned long long n_ok = 0, min_rl = ~0ull, max_rl = 0;
   if (lane == 0) {
+    const uint32_t odd_min = row[kOddMin], odd_max = row[kOddMax];
+    const uint32_t lo = u_min < odd_min ? u_min : odd_min;
+    n_ok = (unsigned long long)u_ok + row[kOddOk];
+    min_rl = lo == ~0u ? ~0ull : (unsigned long long)lo;
+    max_rl = u_max > odd_max ? u_max : odd_max;
     s_red[0][threadIdx.x >> 6] = n_ok;
     s_red[1][threadIdx.x >> 6] = min_rl;
     s_red[2][threadIdx.x >> 6] = max_rl;
