@@ -10,7 +10,9 @@
 //                fastq_validate_entry (reference src/fastq.c:300-392) with ballots over 64-byte
 //                slices of each line; statistics kept in registers and flushed once per wave
 //
-// Everything here is byte / integer work bounded by HBM bandwidth; there is no MFMA use.
+// Everything here is byte / integer work bounded by HBM bandwidth; no kernel of this file uses the matrix pipe.  (The
+// streaming pass does, for one thing: its mark packs are v_mfma_i32_16x16x64_i8 with a constant block-diagonal of weights
+// as A - 128 dot products of 16 bytes in one instruction, no GEMM: fqg_mark_pack.h.)
 #include "fqg_device.h"
 
 namespace fqg {

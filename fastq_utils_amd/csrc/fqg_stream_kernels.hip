@@ -7,7 +7,8 @@
 //   k_stream_boot   quality range of the first records (line types are known at the image start)
 //   k_stream_pass1  one wavefront per 4 KiB chunk, no dependence on any other chunk:
 //                     - newline mask, NUL / CR / high-byte detection (SWAR on bytes < 0x80, byte
-//                       marks compacted to bit masks with v_dot4_u32_u8)
+//                       marks compacted to bit masks with v_dot4_u32_u8 - in the launches that also carry line
+//                       workers with v_mfma_i32_16x16x64_i8: fqg_mark_pack.h)
 //                     - the line type of the chunk's first byte is SPECULATED from the first
 //                       one-character line of the chunk (in FASTQ that is the "+" line, type 2)
 //                     - with that type: bases outside ACGTN on sequence lines -> suspect byte
@@ -239,6 +240,7 @@ __device__ __forceinline__ void stage_chunk(const uint8_t* __restrict__ img, uin
 
 // ABL: ablation mask for tools/kbench (product code instantiates 0): 1 = no byte-class checks,
 // 2 = no staging, 4 = no fetch of the byte after a newline, 8 = no base check, 16 = no quality test
+// WAVE_PACK: the six mark packs on the matrix pipe (pack_marks32_wave) instead of v_dot4 (pack_marks32)
 // NAMES: also capture the header lines that begin in the chunk (NameCapture, fqg_device.h)
 // NAMES: 0 = no capture, 1 = 64-byte records, 2 = 16-byte digests (fqg_device.h)
 // LDS of a pass-1 workgroup: the staging slots and the copies of its four chunks (static in k_stream_pass1, a piece of the
@@ -249,7 +251,7 @@ struct Pass1Lds {
   __attribute__((aligned(16))) uint8_t copy[kBlock / kWave][NAMES ? kCopyRow : (uint32_t)kChunkBytes];
 };
 // block: which workgroup of the pass this is (chunks 4 block .. 4 block + 3), n_chunks: the pass ends in front of it
-template <uint32_t ABL, int NAMES>
+template <uint32_t ABL, int NAMES, bool WAVE_PACK>
 __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ img, uint64_t n, uint32_t n_chunks, const StreamOut& o,
                                                   CallState* __restrict__ cs, const NameCapture& nc, uint32_t block,
                                                   Pass1Lds<NAMES>& lds) {
@@ -265,6 +267,16 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
   const uint64_t cb = (uint64_t)chunk * kChunkBytes;
   const uint64_t wb = cb + (uint64_t)lane * kLaneBytes;
   const bool interior = cb + kChunkBytes + 4 <= n;
+  // WAVE_PACK: the six mark packs of a chunk run on the matrix pipe (pack_marks32_wave, fqg_mark_pack.h): twelve MFMAs
+  // where 48 v_dot4 stand.  Every one of them stands where the whole wavefront goes or does not go - a wavefront that is
+  // here has all 64 lanes (the return above is by chunk), `interior` depends on the chunk alone, and `found && !dense` comes
+  // from ballots - so all 64 lanes supply their marks.  The weights depend on the lane alone: one 16-byte load per chunk.
+  pack_v4i wts = {0, 0, 0, 0};
+  if (WAVE_PACK) wts = pack_weights(lane);
+  auto pack = [&](uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3, uint32_t m4, uint32_t m5, uint32_t m6, uint32_t m7) {
+    if constexpr (WAVE_PACK) return pack_marks32_wave(wts, m0, m1, m2, m3, m4, m5, m6, m7);
+    else return pack_marks32(m0, m1, m2, m3, m4, m5, m6, m7);
+  };
   uint32_t nl[kHalves], ex[kHalves];
   Piece32 v[kHalves];
   uint32_t flags = 0;
@@ -291,8 +303,8 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
 #pragma unroll
     for (int k = 0; k < kHalves; ++k) {
       hiacc = or3(or3(or3(or3(hiacc, v[k].a.x, v[k].a.y), v[k].a.z, v[k].a.w), v[k].b.x, v[k].b.y), v[k].b.z, v[k].b.w);
-      nl[k] = pack_marks32(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc), nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc),
-                           nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc), nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
+      nl[k] = pack(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc), nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc),
+                   nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc), nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
     }
     const bool high = __ballot((hiacc & kH) != 0) != 0;
     const bool ctrl = __ballot((badacc & kH) != 0) != 0;
@@ -411,13 +423,13 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
 #pragma unroll
       for (int k = 0; k < kHalves; ++k) {
         const uint4 &a = v[k].a, &b = v[k].b;
-        const uint32_t inv = pack_marks32(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w), not_acgtn7(b.x), not_acgtn7(b.y),
-                                          not_acgtn7(b.z), not_acgtn7(b.w));
+        const uint32_t inv = pack(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w), not_acgtn7(b.x), not_acgtn7(b.y),
+                                  not_acgtn7(b.z), not_acgtn7(b.w));
         const uint32_t bad = (ABL & 8u) ? 0u : inv & M1[k];
         if (bad) queue_suspect(o, cs, wb + (uint64_t)k * kHalfBytes + (uint32_t)__builtin_ctz(bad));
-        const uint32_t okq = pack_marks32(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
-                                          in_range7a(a.w, lo_add, hihb, khv), in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv),
-                                          in_range7a(b.z, lo_add, hihb, khv), in_range7a(b.w, lo_add, hihb, khv));
+        const uint32_t okq = pack(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
+                                  in_range7a(a.w, lo_add, hihb, khv), in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv),
+                                  in_range7a(b.z, lo_add, hihb, khv), in_range7a(b.w, lo_add, hihb, khv));
         const uint32_t qm = (ABL & 16u) ? 0u : M3[k];
         if (__ballot((qm & ~okq) != 0)) {  // rare: exact range of this slice's quality bytes
           any_viol = true;
@@ -674,12 +686,16 @@ __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ im
   }
 }
 
-template <uint32_t ABL, int NAMES = 0>
-__global__ __launch_bounds__(kBlock) void k_stream_pass1(const uint8_t* __restrict__ img, uint64_t n,
+// WAVE_PACK: for tools/kbench - the launch of its own keeps the v_dot4 packs (alone on the GPU it is 1.7 - 1.9 % slower with the
+// MFMAs, docs/measurement_history.md); the launches that also carry line workers (k_stream_pass1_lines) gain by them.
+// (waves_per_eu: with a register budget of at most 256 the compiler keeps the MFMA results of the mark packs in vector
+// registers; without it they go to accumulation registers and come back through four v_accvgpr_read_b32 per pack)
+template <uint32_t ABL, int NAMES = 0, bool WAVE_PACK = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_stream_pass1(const uint8_t* __restrict__ img, uint64_t n,
                                                          uint32_t n_chunks, StreamOut o,
                                                          CallState* __restrict__ cs, NameCapture nc = NameCapture{}) {
   __shared__ Pass1Lds<NAMES> lds;
-  stream_pass1_body<ABL, NAMES>(img, n, n_chunks, o, cs, nc, blockIdx.x, lds);
+  stream_pass1_body<ABL, NAMES, WAVE_PACK>(img, n, n_chunks, o, cs, nc, blockIdx.x, lds);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1414,7 +1430,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   };
   __shared__ Lds lds;
   if (blockIdx.x >= line_workers) {
-    stream_pass1_body<0u, NAMES>(img, n, n_chunks, o, cs, nc, chunk_first / (kBlock / kWave) + (blockIdx.x - line_workers), lds.p1);
+    stream_pass1_body<0u, NAMES, true>(img, n, n_chunks, o, cs, nc, chunk_first / (kBlock / kWave) + (blockIdx.x - line_workers), lds.p1);
     return;
   }
   // ---- a line worker: the steps of part `part`, from what the scans have left in the call state ----

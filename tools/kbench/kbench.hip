@@ -86,6 +86,11 @@ int main(int argc, char** argv) {
     P1(8u, "  pass1 - no base check");
     P1(16u, "  pass1 - no quality test");
     P1(24u, "  pass1 - types only");
+    // the six mark packs on the matrix pipe (the form of k_stream_pass1_lines) against the v_dot4 packs, taking turns
+#define P1W(label) report(label, time_ms(reps, [&] { hipLaunchKernelGGL((k_stream_pass1<0u, 0, true>), dim3((n_tiles + 3) / 4), dim3(kBlock), 0, 0, img, n, n_tiles, so, cs); }))
+    P1W("  pass1 - MFMA packs");
+    P1(0u, "k_stream_pass1");
+    P1W("  pass1 - MFMA packs");
     P1(0u, "k_stream_pass1");
     hipLaunchKernelGGL(k_scan_a, dim3(n_spans), dim3(kBlock), 0, 0, counts, n_tiles, local, spans);
     hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, 0, spans, n_spans, img, n, cs);
