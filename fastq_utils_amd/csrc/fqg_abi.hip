@@ -1140,7 +1140,10 @@ int stream_lines(fqg_ctx* c, const StreamCall& s) {
         if ((rc = ensure(c, c->lines_slow, (size_t)n_steps + 4))) return rc;
         HIP_TRY(c, hipMemsetAsync(c->lines_slow.p, 0, (size_t)n_steps, c->stream));
       }
-      const uint64_t fast_per_gpu = (uint64_t)c->cu_count * resident_per_cu(c->lines_fast_per_cu, reinterpret_cast<const void*>(k_stream_lines_fast));
+      // (at most seven workgroups per CU: its LDS lets eight be resident, and with eight the kernel is slower - 0.148 ms
+      // against 0.129 ms for its launches of a step of 100 M reads, profiles/r18_ab_bench_waves.txt)
+      constexpr int kLinesFastPerCuMax = 7;
+      const uint64_t fast_per_gpu = (uint64_t)c->cu_count * std::min(kLinesFastPerCuMax, resident_per_cu(c->lines_fast_per_cu, reinterpret_cast<const void*>(k_stream_lines_fast)));
       auto grid_fast = [&](uint64_t steps) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((steps + 3) / 4, fast_per_gpu)); };
       if (done_steps && !lazy && (!s.early_line_cap || s.index_lost)) {
         // the index is wanted after all (pass 1 queued byte positions), or its room was too small: the stores of the

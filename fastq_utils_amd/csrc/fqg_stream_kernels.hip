@@ -1131,8 +1131,12 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
          ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32);
 }
 
+// The histogram of the kernel without a search has a size of its own, below that of the general kernel (kLinesHist): with
+// it LinesFastLds, and the union of k_stream_pass1_lines, fit an eighth of a CU's 160 KiB of LDS.  A length at or beyond it
+// goes to A.hist by a global atomic, as lengths beyond kLinesHist do in the general kernel.
+constexpr int kLinesFastHist = 3008;
 struct LinesFastLds {
-  uint32_t hist[kLinesHist];
+  uint32_t hist[kLinesFastHist];
   unsigned long long red[3][kBlock / kWave];
   __attribute__((aligned(16))) uint32_t ent[kBlock / kWave][kFastRow];
 };
@@ -1143,7 +1147,7 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
   auto& s_hist = lds.hist;
   auto& s_red = lds.red;
   auto& s_ent = lds.ent;
-  for (int i = threadIdx.x; i < kLinesHist; i += kBlock) s_hist[i] = 0;
+  for (int i = threadIdx.x; i < kLinesFastHist; i += kBlock) s_hist[i] = 0;
   __syncthreads();
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1194,7 +1198,7 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
     u_min = run_len < u_min ? run_len : u_min;
     u_max = run_len > u_max ? run_len : u_max;
     if (lane == 0) {
-      if (run_len < (uint32_t)kLinesHist) atomicAdd(&s_hist[run_len], run_cnt);
+      if (run_len < (uint32_t)kLinesFastHist) atomicAdd(&s_hist[run_len], run_cnt);
       else atomicAdd(&A.hist[run_len], (unsigned long long)A.weight * (unsigned long long)run_cnt);
     }
   };
@@ -1349,7 +1353,7 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
             atomicAdd(&row[kOddOk], 1u);
             atomicMin(&row[kOddMin], rl);
             atomicMax(&row[kOddMax], rl);
-            if (rl < (uint32_t)kLinesHist) atomicAdd(&s_hist[rl], 1u);
+            if (rl < (uint32_t)kLinesFastHist) atomicAdd(&s_hist[rl], 1u);
             else atomicAdd(&A.hist[rl], (unsigned long long)A.weight);
           }
         }
@@ -1395,7 +1399,7 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
       if (max_rl > A.acc->max_rl) atomicMax(&A.acc->max_rl, max_rl);
     }
   }
-  for (int i = threadIdx.x; i < kLinesHist; i += kBlock) {
+  for (int i = threadIdx.x; i < kLinesFastHist; i += kBlock) {
     const uint32_t cc = s_hist[i];
     if (cc) atomicAdd(&A.hist[i], (unsigned long long)cc * A.weight);
   }
@@ -1420,8 +1424,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
 // Their statistics go
 // to accumulators the caller merges once the whole image has passed (k_acc_merge): a later part can still raise a flag.
 // ------------------------------------------------------------------------------------------
+// the mark packs of the pass-1 workgroups in this kernel: on the matrix pipe (61 / 62 / 61 vector registers).  With v_dot4
+// (57 / 61 / 57) the three launches of a step are 4.96 ms against 4.88 ms at eight workgroups per CU
+// (profiles/r18_ab_bench_waves.txt).
+constexpr bool kFusedWavePack = true;
 template <int NAMES>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_stream_pass1_lines(
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_stream_pass1_lines(
     const uint8_t* __restrict__ img, uint64_t n, uint32_t chunk_first, uint32_t n_chunks, StreamOut o, CallState* __restrict__ cs,
     LinesArgs A, uint8_t* __restrict__ todo, uint32_t line_workers, uint32_t part /* whose lines: >= 0 */, NameCapture nc) {
   union Lds {
@@ -1429,8 +1437,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
     LinesFastLds lf;
   };
   __shared__ Lds lds;
+  // eight workgroups per CU, as k_stream_pass1 has alone: one is the line worker, seven are pass 1.  A byte more than an
+  // eighth of the CU's 160 KiB and the hardware holds seven - six for pass 1, which is bound by what the vector ALU issues
+  // and pays for every resident wavefront it loses.
+  static_assert(sizeof(Lds) <= (160u << 10) / 8, "the LDS of k_stream_pass1_lines: eight workgroups per CU");
   if (blockIdx.x >= line_workers) {
-    stream_pass1_body<0u, NAMES, true>(img, n, n_chunks, o, cs, nc, chunk_first / (kBlock / kWave) + (blockIdx.x - line_workers), lds.p1);
+    stream_pass1_body<0u, NAMES, kFusedWavePack>(img, n, n_chunks, o, cs, nc, chunk_first / (kBlock / kWave) + (blockIdx.x - line_workers), lds.p1);
     return;
   }
   // ---- a line worker: the steps of part `part`, from what the scans have left in the call state ----
@@ -1440,8 +1452,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   // this one, lines_done[part] for the next: nobody reads it in this launch)
   static_assert(kPartStepRanks == (uint64_t)(4 * kWave * kLinesPer), "a step of the line kernels");
   // (what is read here is the same in every lane, and every lane is active: saying so keeps it in scalar registers - as
-  // vector values the three counts cost two more vector registers than the 72 of seven wavefronts per SIMD, 12 bytes of
-  // scratch per lane in a kernel whose other workgroups are pass 1)
+  // vector values the three counts cost two vector registers more, and the kernel has 64 at eight wavefronts per SIMD: what
+  // does not fit is scratch in a kernel whose other workgroups are pass 1)
   const unsigned long long R = readlane64(cs->part_newlines[part], 0), R0 = part ? readlane64(cs->part_newlines[part - 1], 0) : 0ull;
   const PartSteps ps = part_steps(R0, R, chunk_first, part ? readlane64(cs->lines_done[part - 1], 0) : 0ull);
   if (blockIdx.x == 0 && threadIdx.x == 0) {

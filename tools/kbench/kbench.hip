@@ -92,6 +92,31 @@ int main(int argc, char** argv) {
     P1(0u, "k_stream_pass1");
     P1W("  pass1 - MFMA packs");
     P1(0u, "k_stream_pass1");
+    {
+      // Pass 1 at eight, seven and six resident wavefronts per SIMD (8, 7, 6 workgroups of four wavefronts per CU), both
+      // pack forms taking turns: the residency is limited by padding the launch's dynamic LDS and by nothing else (the
+      // kernel does not touch the padding).  What the occupancy query says of every padding is printed beside the times.
+      const void* const kd = reinterpret_cast<const void*>(k_stream_pass1<0u, 0, false>);
+      const void* const km = reinterpret_cast<const void*>(k_stream_pass1<0u, 0, true>);
+      const unsigned pads[3] = {0u, (160u << 10) / 8 - (unsigned)sizeof(Pass1Lds<0>) + 512u, (160u << 10) / 7 - (unsigned)sizeof(Pass1Lds<0>) + 512u};
+      for (int turn = 0; turn < 2; ++turn)
+        for (unsigned pad : pads) {
+          int nd = 0, nm = 0;
+          CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nd, kd, kBlock, pad));
+          CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nm, km, kBlock, pad));
+          char label[96];
+          snprintf(label, sizeof label, "  pass1 v_dot4 %d wg/CU pad %u", nd, pad);
+          report(label, time_ms(reps, [&] { hipLaunchKernelGGL((k_stream_pass1<0u, 0, false>), dim3((n_tiles + 3) / 4), dim3(kBlock), pad, 0, img, n, n_tiles, so, cs, NameCapture{}); }));
+          snprintf(label, sizeof label, "  pass1 MFMA   %d wg/CU pad %u", nm, pad);
+          report(label, time_ms(reps, [&] { hipLaunchKernelGGL((k_stream_pass1<0u, 0, true>), dim3((n_tiles + 3) / 4), dim3(kBlock), pad, 0, img, n, n_tiles, so, cs, NameCapture{}); }));
+        }
+      int nf = 0, n0 = 0, n1 = 0, n2 = 0;
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nf, reinterpret_cast<const void*>(k_stream_lines_fast), kBlock, 0));
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n0, reinterpret_cast<const void*>(k_stream_pass1_lines<0>), kBlock, 0));
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, reinterpret_cast<const void*>(k_stream_pass1_lines<1>), kBlock, 0));
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, reinterpret_cast<const void*>(k_stream_pass1_lines<2>), kBlock, 0));
+      printf("resident workgroups per CU: k_stream_lines_fast %d, k_stream_pass1_lines<0 / 1 / 2> %d / %d / %d\n", nf, n0, n1, n2);
+    }
     hipLaunchKernelGGL(k_scan_a, dim3(n_spans), dim3(kBlock), 0, 0, counts, n_tiles, local, spans);
     hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(kBlock), 0, 0, spans, n_spans, img, n, cs);
     {
