@@ -1595,176 +1595,8 @@ void fqg_frame_release(fqg_frame* f) {
 
 uint64_t fqg_frame_n_records(const fqg_frame* f) { return f ? f->fv.n_records : 0; }
 
-#include "fqg_barcode_abi.inc"  // (in front of the filters: bc_tile_for is theirs and fqg_split_abi.inc's too)
-
-// ---- per-record filters ---------------------------------------------------------------------
-int fqg_records_filter(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record, uint64_t n_rec,
-                       const fqg_filter_params* fp, fqg_filter_result* out) {
-  if (!c || !frame || !fp || !out) return FQG_ERR_ARG;
-  NEED(text_begin(c, c->bc_text));
-  memset(out, 0, sizeof(*out));
-  for (uint64_t& v : c->filter_info) v = 0;
-  if (fp->mode != FQG_FILTER_N && fp->mode != FQG_FILTER_POLY_AT) return fail(c, FQG_ERR_ARG, "fqg_records_filter: unknown mode");
-  if (first_record > frame->fv.n_records || n_rec > frame->fv.n_records - first_record)
-    return fail(c, FQG_ERR_ARG, "fqg_records_filter: records beyond the frame");
-  HIP_TRY(c, hipSetDevice(c->device));
-  out->n_records = n_rec;
-  if (!n_rec) return 0;
-  BcParams F;
-  memset(&F, 0, sizeof(F));
-  F.f[1].fv = frame->fv;
-  F.f[1].first = first_record;
-  F.f[1].step = 1;
-  F.f[1].present = 1;
-  F.f[1].has_nul = F.has_nul = (frame->flags & kFlagNul) ? 1 : 0;  // lines are C strings then (bc_clip_nul)
-  F.n_inputs = 1;
-  F.emit[1] = 1;
-  RfParams P;
-  P.mode = fp->mode;
-  P.max_n = fp->max_n_percent > 100 ? 100 : fp->max_n_percent;
-  P.min_poly = fp->min_poly_at_len;
-  P.min_len = (uint64_t)fp->min_len;
-  int rc;
-  if ((rc = ensure(c, c->bc_status, n_rec))) return rc;
-  if ((rc = ensure(c, c->bc_len[1], n_rec * 4))) return rc;
-  if ((rc = ensure(c, c->bc_off[1], n_rec * 8))) return rc;
-  if ((rc = ensure(c, c->bc_sum[1], scan64_spans(n_rec) * 8))) return rc;
-  NEED(bcall_reset(c, 0));
-  // (the tiles are the EMIT kernel's alone now - the plan works record by record - and that kernel likes 24 KiB per
-  // wavefront better than the 20 KiB it shared with a staging plan: tools/tiles_lds_sweep.sh)
-  BcTile tc = bc_tile_for(F, 24576u);
-  tc.plan_m = 1;
-  const uint64_t n_tiles = (n_rec + tc.T - 1) / tc.T;
-  if ((rc = ensure(c, c->bc_tile_big, n_tiles))) return rc;
-  unsigned long long *d_tot = bcall_totals(c->d_bcall), *h_tot = bcall_totals(c->h_bcall);
-  {
-    ProfScope ps(c, "k_rf_plan");
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + kBlock - 1) / kBlock, (uint64_t)c->cu_count * 32));
-    if (P.mode == FQG_FILTER_N) {
-      const unsigned grid_n = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 31) / 32, (uint64_t)c->cu_count * 32));
-      hipLaunchKernelGGL(k_rf_plan_n, dim3(grid_n), dim3(kBlock), 0, c->stream, F, P, n_rec, (uint8_t*)c->bc_status.p,
-                         (uint32_t*)c->bc_len[1].p, c->d_bcall);
-    } else {
-      hipLaunchKernelGGL(k_rf_plan_records, dim3(grid), dim3(kBlock), 0, c->stream, F, P, n_rec, (uint8_t*)c->bc_status.p,
-                         (uint32_t*)c->bc_len[1].p, c->d_bcall);
-    }
-  }
-  {
-    // (the plan kernels count what they drop and trim; the tile flags come behind the scan, whose offsets they use)
-    ProfScope ps(c, "k_rf_scan");
-    scan64(c, c->bc_len[1].p, c->bc_off[1].p, c->bc_sum[1].p, d_tot + 1, n_rec);
-    hipLaunchKernelGGL(k_rf_tile_flags, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, F, tc, n_rec,
-                       (const uint32_t*)c->bc_len[1].p, (const unsigned long long*)c->bc_off[1].p,
-                       (const unsigned long long*)c->bc_sum[1].p, (uint8_t*)c->bc_tile_big.p, c->d_bcall);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->h_bcall, c->d_bcall, sizeof(BcCall) + 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  out->n_discarded = c->h_bcall->discarded;
-  out->n_trimmed = c->h_bcall->short_warnings;
-  out->n_kept = n_rec - out->n_discarded;
-  out->out_bytes = h_tot[1];
-  const uint64_t totals[2] = {0, h_tot[1]};  // (stream 1, as the transform's read1)
-  uint8_t* text[2];
-  NEED(text_reserve(c, c->bc_text, totals, 2, text));
-  text_publish(c->bc_text, totals, 2);
-  unsigned grid_t = 0;
-  if (h_tot[1]) {
-    ProfScope ps(c, "k_rf_emit");
-    const EmitOut eo{(const uint32_t*)c->bc_len[1].p, (const unsigned long long*)c->bc_off[1].p,
-                     (const unsigned long long*)c->bc_sum[1].p, text[1]};
-    const unsigned lds = tc.in_cap + tc.out_cap;
-    const unsigned grid = grid_t = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_rf_emit_tile, lds));
-    hipLaunchKernelGGL(k_rf_emit_tile, dim3(grid), dim3(kWave), lds, c->stream, F, P, tc, n_rec,
-                       (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo);
-    if (c->h_bcall->big) {
-      const unsigned grid_e = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 3) / 4, (uint64_t)c->cu_count * 8));
-      hipLaunchKernelGGL(k_rf_emit_direct, dim3(grid_e), dim3(kBlock), 0, c->stream, F, P, tc, n_rec,
-                         (const uint8_t*)c->bc_status.p, (const uint8_t*)c->bc_tile_big.p, eo);
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  c->filter_info[0] = n_tiles;
-  c->filter_info[1] = c->h_bcall->big;
-  c->filter_info[2] = grid_t;  // (0: every record was dropped, nothing was emitted)
-  c->filter_info[3] = tc.T;
-  c->filter_info[4] = tc.in_cap;
-  c->filter_info[5] = tc.out_cap;
-  return 0;
-}
-
-int fqg_records_filter_info(const fqg_ctx* c, uint64_t info[6]) {
-  if (!c || !info) return FQG_ERR_ARG;
-  for (int i = 0; i < 6; ++i) info[i] = c->filter_info[i];
-  return 0;
-}
-
-int fqg_barcodes_output(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
-  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
-  return text_copy(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output: more than was produced");
-}
-
-int fqg_barcodes_output_wait(fqg_ctx* c) { return c ? text_wait(c, c->bc_text) : (int)FQG_ERR_ARG; }
-
-int fqg_barcodes_output_begin(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
-  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
-  return text_copy_begin(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output_begin: more than was produced");
-}
-
-int fqg_records_filter_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) { return fqg_barcodes_output(c, 1, host_dst, nbytes); }
-
-int fqg_records_gather(fqg_ctx* c, const fqg_frame* frame, const uint64_t* records, uint64_t n, uint64_t* out_bytes) {
-  if (!c || !frame || !out_bytes || (!records && n)) return FQG_ERR_ARG;
-  NEED(text_begin(c, c->bc_text));
-  *out_bytes = 0;
-  if (!n) return 0;
-  for (uint64_t k = 0; k < n; ++k)
-    if (records[k] >= frame->fv.n_records) return fail(c, FQG_ERR_ARG, "fqg_records_gather: record outside the frame");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  const bool nul = (frame->flags & kFlagNul) != 0;
-  const uint64_t nb = scan64_spans(n);
-  if ((rc = ensure(c, c->bc_off[1], n * 8))) return rc;     // the list
-  if ((rc = ensure(c, c->bc_len[1], n * 4))) return rc;
-  if ((rc = ensure(c, c->bc_off[2], n * 8))) return rc;     // local offsets
-  if ((rc = ensure(c, c->bc_sum[1], nb * 8 + 16))) return rc;
-  unsigned long long* d_tot = (unsigned long long*)c->bc_sum[1].p + nb;
-  HIP_TRY(c, hipMemcpyAsync(c->bc_off[1].p, records, n * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ProfScope ps(c, "k_gather_plan");
-    if (nul)
-      hipLaunchKernelGGL(k_gather_lens_nul, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, frame->fv,
-                         (const unsigned long long*)c->bc_off[1].p, n, (uint32_t*)c->bc_len[1].p);
-    else
-      hipLaunchKernelGGL(k_gather_lens, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, frame->fv,
-                         (const unsigned long long*)c->bc_off[1].p, n, (uint32_t*)c->bc_len[1].p);
-    scan64(c, c->bc_len[1].p, c->bc_off[2].p, c->bc_sum[1].p, d_tot, n);
-  }
-  HIP_TRY(c, hipMemcpyAsync(&c->h_scalar[2], d_tot, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint64_t total = c->h_scalar[2], totals[2] = {0, total};  // (stream 1, as the filter)
-  uint8_t* text[2];
-  NEED(text_reserve(c, c->bc_text, totals, 2, text));
-  {
-    ProfScope ps(c, "k_gather_copy");
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + 4 * kWave - 1) / (4 * kWave), (uint64_t)c->cu_count * 16);
-    if (nul)  // what gzputs writes of a line is the C string: four pieces per record
-      hipLaunchKernelGGL(k_gather_copy_nul, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)c->cu_count * 16)), dim3(kBlock), 0,
-                         c->stream, frame->fv, (const unsigned long long*)c->bc_off[1].p, n,
-                         (const unsigned long long*)c->bc_off[2].p, (const unsigned long long*)c->bc_sum[1].p,
-                         text[1]);
-    else
-      hipLaunchKernelGGL(k_gather_copy, dim3(grid), dim3(kBlock), 0, c->stream, frame->fv,
-                         (const unsigned long long*)c->bc_off[1].p, n, (const unsigned long long*)c->bc_off[2].p,
-                         (const unsigned long long*)c->bc_sum[1].p, (const uint32_t*)c->bc_len[1].p, text[1]);
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  text_publish(c->bc_text, totals, 2);
-  *out_bytes = total;
-  return 0;
-}
-int fqg_records_gather_output(fqg_ctx* c, void* host_dst, uint64_t nbytes) { return fqg_barcodes_output(c, 1, host_dst, nbytes); }
+#include "fqg_barcode_abi.inc"  // (in front of the filters and the split: bc_tile_one and the output calls are theirs too)
+#include "fqg_filter_abi.inc"
 
 // ---- measurement ----------------------------------------------------------------------------
 int fqg_profile_enable(fqg_ctx* c, int on) {

@@ -1,19 +1,37 @@
 // fqg_barcode_abi.inc - host side of the barcode kernels: fqg_barcodes_transform, the census of what it kept
 // (fqg_census_*, fqg_barcodes_census) and the whitelist (fqg_whitelist_*, fqg_barcodes_whitelist[_correct]).  Included by
-// fqg_abi.hip inside extern "C", in front of the per-record filters: bc_tile_for is theirs and fqg_split_abi.inc's too.
+// fqg_abi.hip inside extern "C", in front of the per-record filters: bc_tile_one is theirs and fqg_split_abi.inc's.
 // fqg_barcodes_transform is its phases in order (bc_prepare, bc_plan, bc_lay_out, bc_emit, bc_cut_at_finding) on one
 // BcBatch; the order of launches, memsets, copies and synchronisations on the stream is the order of the text.
 // ---- barcode extraction ----------------------------------------------------------------------
-// Tile geometry for one call: T iterations whose records and output text fit `budget` bytes of LDS
-// per wavefront, from the mean record sizes (a tile that does not fit anyway takes the direct path).
-// FQGPU_BC_LDS overrides the budget (bytes, 4096..65536).
-static BcTile bc_tile_for(const BcParams& P, unsigned default_budget = 20480u) {
+// Tile geometry: T iterations whose records (`in` bytes an iteration, of `files` files) and output text (`out` bytes) fit
+// the LDS budget of a wavefront, from mean sizes (a tile that does not fit takes the direct path).  FQGPU_BC_LDS: the budget.
+static BcTile bc_tile_budget(double in, double out, int files, unsigned lanes_per_iter, unsigned default_budget) {
   static const unsigned env_budget = [] {
     const char* e = getenv("FQGPU_BC_LDS");
     const long v = e ? atol(e) : 0;
     return (unsigned)(v >= 4096 && v <= 65536 ? v : 0);
   }();
   const unsigned budget = env_budget ? env_budget : default_budget;
+  const double fixed = 48.0 * files + 96.0;
+  double t = ((double)budget - fixed) / (1.06 * (in + out) + 1.0);
+  unsigned T = (unsigned)std::max(1.0, std::min(t, 64.0 / lanes_per_iter));
+  BcTile tc;
+  tc.T = T;
+  tc.in_cap = ((unsigned)(1.06 * in * T + 48.0 * files + 48.0) + 15u) & ~15u;
+  if (tc.in_cap + 1024u > budget) tc.in_cap = (budget / 2) & ~15u;
+  tc.out_cap = (budget - tc.in_cap) & ~15u;
+  tc.plan_m = 1;
+  tc.plan_cap = 64;
+  return tc;
+}
+// ... of the kernels that read one file and write its records as FASTQ text (the record filters, the split)
+static BcTile bc_tile_one(const FrameView& fv, unsigned default_budget) {
+  const double rec = fv.n_records ? (double)fv.nbytes / (double)fv.n_records : 0.0;
+  return bc_tile_budget(rec, rec + 100, 1, 1, default_budget);
+}
+// ... of the transform
+static BcTile bc_tile_for(const BcParams& P, unsigned default_budget = 20480u) {
   double in = 0, out_sam = 0, out_fq = 0;
   int files = 0;
   for (int x = 1; x < kBcFiles; ++x) {
@@ -26,16 +44,7 @@ static BcTile bc_tile_for(const BcParams& P, unsigned default_budget = 20480u) {
       if (P.emit[x]) out_fq = std::max(out_fq, rec + 100);
     }
   }
-  const double out = P.out_sam ? out_sam : out_fq;
-  const unsigned lanes_per_iter = P.out_sam && P.f[2].present ? 2 : 1;
-  const double fixed = 48.0 * files + 96.0;
-  double t = ((double)budget - fixed) / (1.06 * (in + out) + 1.0);
-  unsigned T = (unsigned)std::max(1.0, std::min(t, 64.0 / lanes_per_iter));
-  BcTile tc;
-  tc.T = T;
-  tc.in_cap = ((unsigned)(1.06 * in * T + 48.0 * files + 48.0) + 15u) & ~15u;
-  if (tc.in_cap + 1024u > budget) tc.in_cap = (budget / 2) & ~15u;
-  tc.out_cap = (budget - tc.in_cap) & ~15u;
+  BcTile tc = bc_tile_budget(in, P.out_sam ? out_sam : out_fq, files, P.out_sam && P.f[2].present ? 2 : 1, default_budget);
   // the plan kernel: several tiles at once while one lane per iteration allows it.  It stages only the files a
   // barcode is cut from, and only when a minimum quality makes it read their bytes (bc_staged<PLAN>)
   tc.plan_m = std::max(1u, std::min(64u / tc.T, 4u));
@@ -46,7 +55,7 @@ static BcTile bc_tile_for(const BcParams& P, unsigned default_budget = 20480u) {
       plan_in += (P.f[x].fv.n_records ? (double)P.f[x].fv.nbytes / (double)P.f[x].fv.n_records : 0.0) * P.f[x].step;
       ++plan_files;
     }
-  tc.plan_cap = ((unsigned)(1.06 * plan_in * T * tc.plan_m + 48.0 * plan_files + 64.0) + 15u) & ~15u;
+  tc.plan_cap = ((unsigned)(1.06 * plan_in * tc.T * tc.plan_m + 48.0 * plan_files + 64.0) + 15u) & ~15u;
   while (tc.plan_m > 1 && tc.plan_cap > 32768u) {  // (long reads in a barcode file)
     tc.plan_cap = (tc.plan_cap / tc.plan_m * (tc.plan_m - 1) + 15u) & ~15u;
     --tc.plan_m;
@@ -249,20 +258,13 @@ int bc_emit(fqg_ctx* c, const BcBatch& B, const uint64_t totals[3]) {
     bc_with_kind(B.P.out_sam, [&](auto kind) {
       unsigned grid_t = 1;
       bc_with_mask(B.file_mask, [&](auto mask) {
-        const auto kernel = k_bc_emit_tile<decltype(kind)::value, decltype(mask)::value>;
-        grid_t = (unsigned)std::min<uint64_t>(n_tiles_done, resident_waves(c, (const void*)kernel, lds));
-        hipLaunchKernelGGL(kernel, dim3(grid_t), dim3(kWave), lds, c->stream, B.P, tc, B.n_done, status, big, eo[0], eo[1], eo[2],
-                           c->d_bcall);
+        grid_t = launch_tile_pair(c, k_bc_emit_tile<decltype(kind)::value, decltype(mask)::value>, true, n_tiles_done, lds,
+                                  k_bc_emit_direct<decltype(kind)::value == kEmitBam>, n_big != 0, B.n_done, 8, B.P, tc, B.n_done,
+                                  status, big, eo[0], eo[1], eo[2], c->d_bcall);
       });
       if (getenv("FQGPU_BC_DEBUG"))
         fprintf(stderr, "fqgpu barcodes: T=%u in_cap=%u out_cap=%u emit grid=%u (%u/CU) big tiles=%llu\n", tc.T, tc.in_cap,
                 tc.out_cap, grid_t, grid_t / (unsigned)c->cu_count, (unsigned long long)n_big);
-      if (n_big) {
-        const unsigned grid_e =
-            (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((B.n_done + 3) / 4, (uint64_t)c->cu_count * 8));
-        hipLaunchKernelGGL(k_bc_emit_direct<decltype(kind)::value == kEmitBam>, dim3(grid_e), dim3(kBlock), 0, c->stream, B.P, tc,
-                           B.n_done, status, big, eo[0], eo[1], eo[2], c->d_bcall);
-      }
     });
   }
   NEED(bcall_fetch(c));
@@ -322,6 +324,19 @@ int fqg_barcodes_transform(fqg_ctx* c, const fqg_frame* const frames[6], const f
   NEED(bc_cut_at_finding(c, B, out, totals));
   c->bc_status_valid = out->n_done;  // (fqg_barcodes_census: the status bytes of the iterations this batch yielded)
   return 0;
+}
+
+// the text of the last call that left some (the transform, the record filters, the gather, the split)
+int fqg_barcodes_output(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
+  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
+  return text_copy(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output: more than was produced");
+}
+
+int fqg_barcodes_output_wait(fqg_ctx* c) { return c ? text_wait(c, c->bc_text) : (int)FQG_ERR_ARG; }
+
+int fqg_barcodes_output_begin(fqg_ctx* c, int which, void* host_dst, uint64_t nbytes) {
+  if (!c || which < 0 || which > 2) return FQG_ERR_ARG;
+  return text_copy_begin(c, c->bc_text, which, host_dst, nbytes, "fqg_barcodes_output_begin: more than was produced");
 }
 
 // ---- census of what the transform kept (fqg_census_kernels.hip) -------------------------------------

@@ -19,7 +19,7 @@
 // from the images, one wavefront per iteration in k_bc_emit_direct).
 // Inputs are framed images (line index from fqg_validate); nothing is re-parsed on the host.
 #include "fqg_device.h"
-#include "fqg_tile.h"
+#include "fqg_fastq_tile.h"
 
 namespace fqg {
 
@@ -67,12 +67,6 @@ struct BcCall {
   unsigned long long big;  // tiles that do not fit LDS
 };
 
-struct BcLine {
-  const uint8_t* p;
-  uint32_t len;  // bytes before '\n'
-  uint32_t nl;
-};
-
 // Which input files exist.  MASK = 0: ask the parameters at run time; otherwise bit x of MASK says
 // it at compile time, and the code and registers of absent files disappear from the kernel.
 template <int MASK>
@@ -80,48 +74,9 @@ __device__ __forceinline__ bool bc_has(const BcParams& P, int x) {
   return MASK ? ((MASK >> x) & 1) != 0 : P.f[x].present != 0;
 }
 
-// A line as the reference holds it: gzgets puts it into a buffer and everything after that is a C string function
-// (strlen, gzputs, printf("%s"), strncpy, the scans) - the line ENDS at its first NUL byte, and a line that ends there
-// has no '\n'.  This is also what a line cut at the gzgets limits is (host/fq_reframe.h: the piece is followed by
-// "\0\n").  Only images that hold a NUL byte come here (BcFile::has_nul); the line is in global memory.
-__device__ __forceinline__ void bc_clip_nul(BcLine& l) {
-  const uint32_t n = l.len;
-  uint32_t i = 0;
-  for (; i + 8 <= n; i += 8) {
-    uint64_t w;
-    __builtin_memcpy(&w, l.p + i, 8);
-    const uint64_t z = (w - 0x0101010101010101ull) & ~w & 0x8080808080808080ull;  // 0x80 in the lowest zero byte (and maybe above it)
-    if (z) {
-      l.len = i + ((uint32_t)__builtin_ctzll(z) >> 3);
-      l.nl = 0;
-      return;
-    }
-  }
-  for (; i < n; ++i)
-    if (l.p[i] == 0) {
-      l.len = i;
-      l.nl = 0;
-      return;
-    }
-}
-
+// the four lines of iteration k's record of a file, where they lie in the image
 __device__ __forceinline__ void bc_lines(const BcFile& f, uint64_t k, BcLine ln[4]) {
-  const uint64_t r = f.first + k * f.step + f.add;
-  uint64_t prev = r == 0 ? ~0ull : f.fv.line_end[4 * r - 1];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint64_t e = f.fv.line_end[4 * r + i];
-    ln[i].p = f.fv.img + prev + 1;
-    ln[i].len = (uint32_t)(e - prev - 1);
-    ln[i].nl = e < f.fv.nbytes ? 1u : 0u;
-    prev = e;
-  }
-  if (f.has_nul) {  // (four calls, not a loop over ln[i]: an index that is no constant puts the lines in scratch memory)
-    bc_clip_nul(ln[0]);
-    bc_clip_nul(ln[1]);
-    bc_clip_nul(ln[2]);
-    bc_clip_nul(ln[3]);
-  }
+  frame_lines(f.fv, f.first + k * f.step + f.add, f.has_nul != 0, ln);
 }
 
 // 8 bytes at any alignment (LDS: one ds_read_b64; gfx950 has unaligned DS access)
@@ -569,17 +524,8 @@ __device__ __forceinline__ void bc_out_lens_with(const BcParams& P, uint64_t k, 
 // ---- tiles: the records of T consecutive iterations of every file, copied into LDS ----------------
 // Two dependent round trips to memory per tile: the line index of the tile's records (what a lane
 // needs to know its iteration's lines, and lane 0 / the last lane to know the tile's byte span),
-// then the spans themselves.  The emit kernels and the record filters keep three tiles under way (index of the
-// tile after next and spans of the next tile in flight while the current one is written); the plan kernel of
-// fastq_pre_barcodes requests the next tile's index with the current tile's spans.  Units are aligned on the
-// image ADDRESS, so a unit always holds at least one byte of the image and never leaves its page.
-// (Nothing is computed from the loaded values where they are requested - no select, no addition: an instruction that
-// reads them there is a wait for the memory round trip there.  The requests of a tile are made one tile ahead.)
-struct BcGeo {
-  uint64_t praw, e[4];  // line ends of the lane's record, and of the line before it (record 0: its own first line end, unused)
-  uint32_t r0;          // the lane's record is record 0 of its file
-  __device__ __forceinline__ uint64_t start() const { return r0 ? 0ull : praw + 1; }  // first byte of the record
-};
+// then the spans themselves.  The emit kernel keeps three tiles under way (tile_walk, fqg_fastq_tile.h); the plan
+// kernel requests the next tile's index with the current tile's spans.
 struct TileGeo {
   BcGeo f[kBcFiles];
   // emit: the iteration's place in each output is off + sum (added where it is used: an addition inside the function
@@ -634,14 +580,11 @@ __device__ __forceinline__ void bc_span_plan(const BcParams& P, const TileGeo& t
     sp.skew[x] = (uint32_t)((uintptr_t)(f.fv.img + sp.s0[x]) & 15u);
     sp.first_unit[x] = sp.units;
     sp.gbase[x] = f.fv.img + sp.s0[x] - sp.skew[x] - 16ull * sp.units;
-    if (n > (uint64_t)in_cap) sp.fit = false;
-    else sp.units += (sp.skew[x] + (uint32_t)n + 15u) >> 4;
-    if ((uint64_t)sp.units * 16u + 32u > (uint64_t)in_cap) sp.fit = false;
+    if (!span_fits(sp.skew[x], n, in_cap, sp.units)) sp.fit = false;
   }
 }
-// unit u of a tile (clamped to the tile's last unit: no branch, every load of a round in flight)
-__device__ __forceinline__ bc_u32x4 bc_span_unit(const SpanPlan& sp, uint32_t u) {
-  u = u < sp.units ? u : (sp.units ? sp.units - 1 : 0u);  // (no unit at all: unit 0 of READ1's image, never stored)
+// where unit u of the plan lies (span_unit)
+__device__ __forceinline__ const uint8_t* span_base(const SpanPlan& sp, uint32_t u) {
   const uint8_t* base = sp.gbase[1];  // (the staged file that comes first has first_unit 0: READ1, or the loop finds it)
 #pragma unroll
   for (int x = 2; x < kBcFiles; ++x) {
@@ -650,20 +593,7 @@ __device__ __forceinline__ bc_u32x4 bc_span_unit(const SpanPlan& sp, uint32_t u)
     const uint8_t* const gx = sp.gbase[x];
     base = u >= sp.first_unit[x] ? static_cast<const uint8_t*>(gx) : static_cast<const uint8_t*>(base);
   }
-  return __builtin_nontemporal_load(reinterpret_cast<const bc_u32x4*>(base + 16ull * u));
-}
-// units from_unit .. of the tile -> s_in, 8 loads in flight per lane
-__device__ __forceinline__ void bc_span_copy(const SpanPlan& sp, uint32_t from_unit, int lane, uint8_t* s_in) {
-  for (uint32_t u0 = from_unit; u0 < sp.units; u0 += 8 * kWave) {
-    bc_u32x4 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = bc_span_unit(sp, u0 + j * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t u = u0 + j * kWave + lane;
-      if (u < sp.units) *reinterpret_cast<bc_u32x4*>(s_in + 16u * u) = v[j];
-    }
-  }
+  return base;
 }
 // the lane's lines: pointers into the staged spans (a file that is not staged: the lengths of its lines, no bytes -
 // pointers that are never followed)
@@ -700,30 +630,13 @@ __device__ __forceinline__ bool bc_stage_tile(const BcParams& P, const TileGeo& 
   SpanPlan sp;
   bc_span_plan<PLAN, MASK>(P, tg, last_lane, in_cap, sp);
   if (!sp.fit) return false;
-  bc_span_copy(sp, 0, lane, s_in);
+  span_copy(sp, 0, lane, s_in);
   bc_span_lines<PLAN, MASK>(P, tg, sp, s_in, L);
   return true;
 }
 
-// The emit kernel requests the first kSpanPf * 64 units of a tile (10 KiB: every tile of the default LDS budget) as
-// straight-line code - a loop makes the compiler wait for every request in flight where the loop begins, the next
-// tile's index among them.
-constexpr int kSpanPf = 10;
-__device__ __forceinline__ void bc_span_fetch(const SpanPlan& sp, int lane, bc_u32x4 (&v)[kSpanPf]) {
-#pragma unroll
-  for (int j = 0; j < kSpanPf; ++j) v[j] = bc_span_unit(sp, (uint32_t)(j * kWave + lane));
-}
-__device__ __forceinline__ void bc_span_land(const SpanPlan& sp, int lane, const bc_u32x4 (&v)[kSpanPf], uint8_t* s_in) {
-#pragma unroll
-  for (int j = 0; j < kSpanPf; ++j) {
-    const uint32_t u = (uint32_t)(j * kWave + lane);
-    if (u < sp.units) *reinterpret_cast<bc_u32x4*>(s_in + 16u * u) = v[j];
-  }
-  bc_span_copy(sp, kSpanPf * kWave, lane, s_in);  // (larger tiles: the rest now)
-}
-
 // Would the records of the iterations held by lanes first_lane .. last_lane fit the input area of ONE emit
-// tile?  The same unit count as bc_stage_tile makes for that tile (the emit kernels stage every input).
+// tile?  The unit count that bc_span_plan makes for that tile (the emit kernels stage every input), by the same rule.
 template <int MASK>
 __device__ __forceinline__ bool bc_emit_tile_fits(const BcParams& P, const TileGeo& tg, int first_lane, int last_lane,
                                                   uint32_t in_cap) {
@@ -737,9 +650,7 @@ __device__ __forceinline__ bool bc_emit_tile_fits(const BcParams& P, const TileG
     const uint64_t e3l = rl64(tg.f[x].e[3], last_lane);
     const uint64_t n = (e3l < f.fv.nbytes ? e3l + 1 : e3l) - s0;
     const uint32_t skew = (uint32_t)((uintptr_t)(f.fv.img + s0) & 15u);
-    if (n > (uint64_t)in_cap) fit = false;
-    else units += (skew + (uint32_t)n + 15u) >> 4;
-    if ((uint64_t)units * 16u + 32u > (uint64_t)in_cap) fit = false;
+    if (!span_fits(skew, n, in_cap, units)) fit = false;
   }
   return fit;
 }
@@ -823,7 +734,7 @@ __global__ __launch_bounds__(kWave, PlanShape<MASK>::waves) void k_bc_plan_tile(
       SpanPlan sp;
       bc_span_plan<true, MASK>(P, cur, (int)Tn - 1, plan_cap, sp);
       const bool fit = !P.has_nul && sp.fit;
-      if (fit) bc_span_copy(sp, 0, lane, s_lds);
+      if (fit) span_copy(sp, 0, lane, s_lds);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       if (fit) {
@@ -1488,13 +1399,9 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
       if (P.emit[2]) tg.off[2] = o2.off[k], tg.sum[2] = o2.sum[k / kScan64Span], tg.olen[2] = o2.len[k];
     }
   };
-  // Three tiles are under way per wavefront: the current tile is written while the spans of the next one (registers)
-  // and the line index of the one after it are in flight.  Every request is made without a branch and nothing is
-  // computed from a loaded value before the tile it belongs to begins - a value that is loaded on one path only is
-  // copied where the paths meet, and an instruction that reads it is a wait for it: the tile behind the last one is the
-  // last one again, a tile that does not fit LDS fetches (and drops) what its clamped plan says.
-  // (The kernel for any set of files, MASK 0, has no registers for this: it copies the spans of a tile when it gets
-  // there.)
+  // tile_walk (fqg_fastq_tile.h) written out - a change of the order is made in both places: the fifteen instantiations sit
+  // at the edge of their registers, and through the template five came out with scratch memory or a spilled register.
+  // (MASK 0 has no registers for three tiles under way: it copies a tile's spans when it gets there.)
   constexpr bool kAhead = MASK != 0;
   const uint64_t stride = gridDim.x;
   auto clamp_tile = [&](uint64_t t) { return t < n_tiles ? t : n_tiles - 1; };
@@ -1507,7 +1414,7 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
       geo_of(clamp_tile(blockIdx.x + stride), nxt);
       SpanPlan sp;
       bc_span_plan<false, MASK>(P, cur, last_lane_of(blockIdx.x), tc.in_cap, sp);
-      bc_span_fetch(sp, lane, pf);
+      span_fetch(sp, lane, pf);
     }
   }
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += stride, cur = kAhead ? nxt : nx2, nxt = nx2) {
@@ -1522,8 +1429,8 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
       bc_span_plan<false, MASK>(P, cur, last_lane_of(tile), tc.in_cap, sp);
       if (!big) {  // (fits: the plan checked)
         if (P.ablate & 8) {
-        } else if (kAhead) bc_span_land(sp, lane, pf, s_in);
-        else bc_span_copy(sp, 0, lane, s_in);
+        } else if (kAhead) span_land(sp, lane, pf, s_in);
+        else span_copy(sp, 0, lane, s_in);
       }
       bc_span_lines<false, MASK>(P, cur, sp, s_in, L);
     }
@@ -1531,7 +1438,7 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
       const uint64_t tn = clamp_tile(tile + stride);
       SpanPlan sp;
       bc_span_plan<false, MASK>(P, nxt, last_lane_of(tn), tc.in_cap, sp);
-      bc_span_fetch(sp, lane, pf);
+      span_fetch(sp, lane, pf);
     }
     geo_of(clamp_tile(tile + (kAhead ? 2 : 1) * stride), nx2);
     if (big) continue;
@@ -1559,27 +1466,19 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
                               : (lpi == 1 ? cur.olen[0]
                                           : (KIND == kEmitBam ? bc_bam_record_len(number, mate1, g, t)
                                                               : bc_sam_line_len(number, bc_sam_flag(se, mate1), g, t)));
-      const unsigned long long where = cur.off[0] + cur.sum[0];
-      const unsigned long long tile_at = rfl64(where);
-      const uint32_t before = __shfl_up(my_len, 1, 64);
-      const uint32_t start = (uint32_t)(where - tile_at) + (mate1 ? 0u : before);
-      const uint32_t total = wave_max32(start + my_len);
-      uint8_t* dst = o0.out + tile_at;
-      const uint32_t skew = (uint32_t)((uintptr_t)dst & 15u);
+      const uint32_t before = __shfl_up(my_len, 1, 64);  // (a second mate: behind the first, whose place it shares)
+      const TileImage im = tile_image(o0.out, cur.off[0] + cur.sum[0], my_len, mate1 ? 0u : before);
       if constexpr (KIND == kEmitBam) {
         BamLaneWriter w;
-        w.p = s_out + skew + start;
+        w.p = s_out + im.skew + im.start;
         if (keep) bc_emit_bam_record(P, number, se, mate1, own, g, t, my_len, w);
         // a byte that refuses the record (what its geometry says against it: the plan)
         bc_report_finding(call, keep, k, keep && w.refused() ? (kBcFindBam << 3) | (mate1 ? 1u : 2u) : 0u);
       } else if (keep && !(P.ablate & 1)) {
-        LaneWriter w{s_out + skew + start};
+        LaneWriter w{s_out + im.skew + im.start};
         bc_emit_sam_line(P, number, se, mate1, own, g, t, w);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (!(P.ablate & 2)) emit_flush(s_out, skew, total, dst, lane);
-      __builtin_amdgcn_wave_barrier();
+      tile_image_flush(im, s_out, lane, !(P.ablate & 2));
     } else {
 #pragma unroll
       for (int which = 1; which <= 2; ++which) {
@@ -1587,20 +1486,12 @@ __global__ __launch_bounds__(kWave, KIND == kEmitBam && MASK == 0x02 ? 3 : 2) vo
         const EmitOut& o = which == 1 ? o1 : o2;
         const bool sliced = bc_slices(P, which);
         const uint32_t my_len = keep ? cur.olen[which] : 0u;
-        const unsigned long long where = cur.off[which] + cur.sum[which];
-        const unsigned long long tile_at = rfl64(where);
-        const uint32_t start = (uint32_t)(where - tile_at);
-        const uint32_t total = wave_max32(start + my_len);
-        uint8_t* dst = o.out + tile_at;
-        const uint32_t skew = (uint32_t)((uintptr_t)dst & 15u);
+        const TileImage im = tile_image(o.out, cur.off[which] + cur.sum[which], my_len);
         if (keep) {
-          LaneWriter w{s_out + skew + start};
+          LaneWriter w{s_out + im.skew + im.start};
           bc_emit_fastq(sliced, P.read_off[which], P.read_size[which], L[which], t, w);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        emit_flush(s_out, skew, total, dst, lane);
-        __builtin_amdgcn_wave_barrier();
+        tile_image_flush(im, s_out, lane);
       }
     }
   }

@@ -10,7 +10,7 @@
 // 16-byte stores.  The decision is recomputed by the emit kernel (a few LDS reads) rather than
 // stored.  Tiles that do not fit LDS (long reads) go through the *_direct paths.
 #include "fqg_device.h"
-#include "fqg_tile.h"
+#include "fqg_fastq_tile.h"
 
 namespace fqg {
 
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_rf_plan_n(BcParams F, RfParams P, ui
 }
 
 // ... and what it decides per EMIT tile - do the tile's input span and its output fit the emit kernel's LDS areas
-// (bc_emit_tile_fits for the one input file): one thread per tile
+// (span_fits for the one input file, as the emit kernel counts what it lands): one thread per tile
 // (behind the scan of the lengths: a tile's output bytes are the difference of two offsets - the sum over its T lengths,
 // read one by one at a stride of T words from lane to lane, was most of this kernel's millisecond per 100 M records)
 __global__ __launch_bounds__(kBlock) void k_rf_tile_flags(BcParams F, BcTile tc, uint64_t n_rec, const uint32_t* __restrict__ len1,
@@ -245,12 +245,8 @@ __global__ __launch_bounds__(kBlock) void k_rf_tile_flags(BcParams F, BcTile tc,
   if (tile < n_tiles) {
     const uint64_t k0 = tile * tc.T, k1 = (k0 + tc.T < n_rec ? k0 + tc.T : n_rec) - 1;
     const uint64_t sum = (off[k1] + span_excl[k1 / kScan64Span] + len1[k1]) - (off[k0] + span_excl[k0 / kScan64Span]);
-    const uint64_t r0 = f.first + k0 * f.step + f.add, r1 = f.first + k1 * f.step + f.add;
-    const uint64_t s0 = r0 == 0 ? 0 : f.fv.line_end[4 * r0 - 1] + 1, e3l = f.fv.line_end[4 * r1 + 3];
-    const uint64_t n = (e3l < f.fv.nbytes ? e3l + 1 : e3l) - s0;
-    const uint32_t skew = (uint32_t)((uintptr_t)(f.fv.img + s0) & 15u);
-    bool fit = n <= (uint64_t)tc.in_cap;
-    if (fit) fit = (uint64_t)((skew + (uint32_t)n + 15u) >> 4) * 16u + 32u <= (uint64_t)tc.in_cap;
+    uint64_t n;
+    const bool fit = frame_span_fits(f.fv, f.first + k0 * f.step + f.add, f.first + k1 * f.step + f.add, tc.in_cap, n);
     big = F.has_nul || !fit || sum + 32 > tc.out_cap;  // (NUL bytes: lines are C strings - the record-by-record kernel, bc_lines)
     tile_big[tile] = big ? 1 : 0;
   }
@@ -265,70 +261,37 @@ __global__ __launch_bounds__(kWave, 2) void k_rf_emit_tile(BcParams F, RfParams 
   uint8_t* s_in = s_lds;
   uint8_t* s_out = s_lds + tc.in_cap;
   const int lane = (int)threadIdx.x;
-  const uint64_t n_tiles = (n_rec + tc.T - 1) / tc.T;
-  auto tile_size = [&](uint64_t tile) {
-    const uint64_t left = n_rec - tile * tc.T;
-    return (uint32_t)(left < (uint64_t)tc.T ? left : (uint64_t)tc.T);
-  };
-  auto geo_of = [&](uint64_t tile, TileGeo& tg) {
-    const uint32_t Tn = tile_size(tile);
-    const uint64_t k = tile * tc.T + ((uint32_t)lane < Tn ? (uint32_t)lane : Tn - 1);
-    tg.big = tile_big[tile];
+  auto geo_of = [&](const TileAt& at, TileGeo& tg) {
+    const uint64_t k = at.tile * tc.T + ((uint32_t)lane < at.Tn ? (uint32_t)lane : at.Tn - 1);
+    tg.big = tile_big[at.tile];
     tg.st = status[k];
     bc_geo_load(F.f[1], k, tg.f[1]);
     tg.off[1] = o.off[k], tg.sum[1] = o.sum[k / kScan64Span];  // (added where it is used, see TileGeo)
   };
-  // three tiles under way per wavefront, every request without a branch (see k_bc_emit_tile)
-  const uint64_t stride = gridDim.x;
-  auto clamp_tile = [&](uint64_t t) { return t < n_tiles ? t : n_tiles - 1; };
-  TileGeo cur, nxt, nx2;
-  bc_u32x4 pf[kSpanPf];
-  if (blockIdx.x < n_tiles) {
-    geo_of(blockIdx.x, cur);
-    geo_of(clamp_tile(blockIdx.x + stride), nxt);
+  auto plan_of = [&](const TileGeo& tg, const TileAt& at) {
     SpanPlan sp;
-    bc_span_plan<false, 0x02>(F, cur, (int)tile_size(blockIdx.x) - 1, tc.in_cap, sp);
-    bc_span_fetch(sp, lane, pf);
-  }
-  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += stride, cur = nxt, nxt = nx2) {
-    const uint32_t Tn = tile_size(tile);
-    const bool valid = (uint32_t)lane < Tn;
-    const bool big = __builtin_amdgcn_readfirstlane((int)cur.big) != 0;
-    BcLine L[kBcFiles][4];
-    {
-      SpanPlan sp;
-      bc_span_plan<false, 0x02>(F, cur, (int)Tn - 1, tc.in_cap, sp);
-      if (!big) bc_span_land(sp, lane, pf, s_in);  // (fits: the plan checked)
-      bc_span_lines<false, 0x02>(F, cur, sp, s_in, L);
-    }
-    {
-      const uint64_t tn = clamp_tile(tile + stride);
-      SpanPlan sp;
-      bc_span_plan<false, 0x02>(F, nxt, (int)tile_size(tn) - 1, tc.in_cap, sp);
-      bc_span_fetch(sp, lane, pf);
-    }
-    geo_of(clamp_tile(tile + 2 * stride), nx2);
-    if (big) continue;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const bool keep = valid && !(cur.st & kRfDiscard);
-    const RfCut c = rf_decide<true>(P, L[1]);
-    const uint32_t my_len = keep ? rf_out_len(L[1], c) : 0u;
-    const unsigned long long where = cur.off[1] + cur.sum[1];
-    const unsigned long long tile_at = rfl64(where);
-    const uint32_t start = (uint32_t)(where - tile_at);
-    const uint32_t total = wave_max32(keep ? start + my_len : 0u);
-    uint8_t* dst = o.out + tile_at;
-    const uint32_t skew = (uint32_t)((uintptr_t)dst & 15u);
+    bc_span_plan<false, 0x02>(F, tg, (int)at.Tn - 1, tc.in_cap, sp);
+    return sp;
+  };
+  auto fetch = [&](const TileGeo& tg, const TileAt& at, bc_u32x4(&pf)[kSpanPf]) { span_fetch(plan_of(tg, at), lane, pf); };
+  using Lines = BcLine[kBcFiles][4];
+  auto stage = [&](const TileGeo& cur, const TileAt& at, bool big, const bc_u32x4(&pf)[kSpanPf], Lines& L) {
+    const SpanPlan sp = plan_of(cur, at);
+    if (!big) span_land(sp, lane, pf, s_in);  // (fits: k_rf_tile_flags checked)
+    bc_span_lines<false, 0x02>(F, cur, sp, s_in, L);
+  };
+  auto work = [&](const TileGeo& cur, const TileAt& at, const Lines& L) {
+    const BcLine(&ln)[4] = L[1];
+    const bool keep = (uint32_t)lane < at.Tn && !(cur.st & kRfDiscard);
+    const RfCut c = rf_decide<true>(P, ln);
+    const TileImage im = tile_image(o.out, cur.off[1] + cur.sum[1], keep ? rf_out_len(ln, c) : 0u);
     if (keep) {
-      LaneWriter w{s_out + skew + start};
-      rf_emit(L[1], c, w);
+      LaneWriter w{s_out + im.skew + im.start};
+      rf_emit(ln, c, w);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    emit_flush(s_out, skew, total, dst, lane);
-    __builtin_amdgcn_wave_barrier();
-  }
+    tile_image_flush(im, s_out, lane);
+  };
+  tile_walk<TileGeo, Lines>(n_rec, tc.T, geo_of, fetch, stage, work);
 }
 
 // records of the tiles that do not fit LDS: one wavefront per record, straight from image to image
@@ -445,21 +408,12 @@ __global__ __launch_bounds__(kBlock) void k_gather_copy(FrameView f, const unsig
 
 // ... of an image with NUL bytes: what GZ_WRITE / gzputs write of a line is the C string (bc_clip_nul) - four pieces per
 // record.  Such images are rare and small: one wavefront per record, byte by byte.
-__device__ __forceinline__ void gather_lines_nul(const FrameView& f, uint64_t r, BcLine ln[4]) {
-  BcFile bf;
-  bf.fv = f;
-  bf.first = 0;
-  bf.step = 1;
-  bf.add = 0;
-  bf.has_nul = 1;
-  bc_lines(bf, r, ln);
-}
 __global__ __launch_bounds__(kBlock) void k_gather_lens_nul(FrameView f, const unsigned long long* __restrict__ list,
                                                             uint64_t n, uint32_t* __restrict__ lens) {
   const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (k >= n) return;
   BcLine ln[4];
-  gather_lines_nul(f, list[k], ln);
+  frame_lines(f, list[k], true, ln);
   lens[k] = ln[0].len + ln[0].nl + ln[1].len + ln[1].nl + ln[2].len + ln[2].nl + ln[3].len + ln[3].nl;
 }
 __global__ __launch_bounds__(kBlock) void k_gather_copy_nul(FrameView f, const unsigned long long* __restrict__ list, uint64_t n,
@@ -470,7 +424,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_copy_nul(FrameView f, const u
   const uint64_t n_waves = (uint64_t)gridDim.x * (kBlock / kWave);
   for (uint64_t k = (uint64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6); k < n; k += n_waves) {
     BcLine ln[4];
-    gather_lines_nul(f, list[k], ln);
+    frame_lines(f, list[k], true, ln);
     uint8_t* dst = out + off_local[k] + off_span[k / kScan64Span];
 #pragma unroll 1
     for (int i = 0; i < 4; ++i) {

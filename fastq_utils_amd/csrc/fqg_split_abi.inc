@@ -33,16 +33,9 @@ int fqg_records_split(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record,
   A.n_rec = n_rec;
   A.has_nul = (frame->flags & kFlagNul) ? 1 : 0;  // lines are C strings then (bc_clip_nul)
   {
-    // the LDS budget of a wavefront is the record filters' (bc_tile_for, FQGPU_BC_LDS); it holds the tile's span and,
+    // the LDS budget of a wavefront is the record filters' (bc_tile_one, FQGPU_BC_LDS); it holds the tile's span and,
     // behind it, the two images - together the span's bytes again
-    BcParams F;
-    memset(&F, 0, sizeof(F));
-    F.f[1].fv = frame->fv;
-    F.f[1].step = 1;
-    F.f[1].present = 1;
-    F.n_inputs = 1;
-    F.emit[1] = 1;
-    const BcTile tc = bc_tile_for(F, 24576u);
+    const BcTile tc = bc_tile_one(frame->fv, 24576u);
     const unsigned budget = tc.in_cap + tc.out_cap;
     const double rec = (double)frame->fv.nbytes / (double)frame->fv.n_records;
     unsigned T = (unsigned)std::max(2.0, std::min(((double)budget - 160.0) / (2.12 * rec + 2.0), 64.0)) & ~1u;
@@ -86,15 +79,9 @@ int fqg_records_split(fqg_ctx* c, const fqg_frame* frame, uint64_t first_record,
   unsigned grid_t = 0;
   {
     ProfScope ps(c, "k_split_emit");
-    if (n_big < n_tiles) {
-      const unsigned lds = A.in_cap + A.out_cap;
-      grid_t = (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)k_split_emit_tile, lds));
-      hipLaunchKernelGGL(k_split_emit_tile, dim3(grid_t), dim3(kWave), lds, c->stream, A);
-    }
-    if (n_big) {  // (16 workgroups per CU where the transform's and the filter's direct paths take 8: kept, the kernel sees the grid)
-      const unsigned grid_e = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 3) / 4, (uint64_t)c->cu_count * 16));
-      hipLaunchKernelGGL(k_split_emit_direct, dim3(grid_e), dim3(kBlock), 0, c->stream, A);
-    }
+    // (16 workgroups per CU where the transform's and the filter's direct paths take 8: kept, the kernel sees the grid)
+    grid_t = launch_tile_pair(c, k_split_emit_tile, n_big < n_tiles, n_tiles, A.in_cap + A.out_cap, k_split_emit_direct, n_big != 0,
+                              n_rec, 16, A);
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());

@@ -11,11 +11,11 @@
 //   k_split_emit_tile   one wavefront per tile: the tile's span of the image lands in LDS with aligned 16-byte loads, every
 //                       lane copies its record inside LDS into the image of its stream (the two images lie behind each
 //                       other in ONE output area: together they hold exactly the span's bytes, however unequal the
-//                       mates), both images leave with aligned 16-byte stores (emit_flush); three tiles under way
+//                       mates), both images leave with aligned 16-byte stores (emit_flush); tile_walk (fqg_fastq_tile.h)
 //   k_split_emit_direct tiles that do not fit (long reads) and images with NUL bytes (lines are C strings there,
 //                       bc_clip_nul): one wavefront per record, image to image
 #include "fqg_device.h"
-#include "fqg_tile.h"
+#include "fqg_fastq_tile.h"
 
 namespace fqg {
 
@@ -32,30 +32,13 @@ struct SplitArgs {
   unsigned long long* n_big;    // tiles that take the direct path
 };
 
-// the four lines of record r as C strings (images with NUL bytes only)
-__device__ __forceinline__ void split_lines_nul(const FrameView& f, uint64_t r, BcLine (&ln)[4]) {
-  uint64_t prev = r == 0 ? ~0ull : f.line_end[4 * r - 1];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint64_t e = f.line_end[4 * r + i];
-    ln[i].p = f.img + prev + 1;
-    ln[i].len = (uint32_t)(e - prev - 1);
-    ln[i].nl = e < f.nbytes ? 1u : 0u;
-    prev = e;
-  }
-  bc_clip_nul(ln[0]);
-  bc_clip_nul(ln[1]);
-  bc_clip_nul(ln[2]);
-  bc_clip_nul(ln[3]);
-}
-
 __global__ __launch_bounds__(kBlock) void k_split_lens(SplitArgs A) {
   for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < A.n_rec; k += (uint64_t)gridDim.x * kBlock) {
     const uint64_t r = A.first + k;
     uint32_t len;
     if (A.has_nul) {
       BcLine ln[4];
-      split_lines_nul(A.fv, r, ln);
+      frame_lines(A.fv, r, true, ln);
       len = ln[0].len + ln[0].nl + ln[1].len + ln[1].nl + ln[2].len + ln[2].nl + ln[3].len + ln[3].nl;
     } else {
       const uint64_t b = r == 0 ? 0 : A.fv.line_end[4 * r - 1] + 1;
@@ -76,12 +59,8 @@ __global__ __launch_bounds__(kBlock) void k_split_tile_flags(SplitArgs A) {
   bool big = false;
   if (tile < n_tiles) {
     const uint64_t k0 = tile * A.T, k1 = (k0 + A.T < A.n_rec ? k0 + A.T : A.n_rec) - 1;
-    const uint64_t r0 = A.first + k0, r1 = A.first + k1;
-    const uint64_t s0 = r0 == 0 ? 0 : A.fv.line_end[4 * r0 - 1] + 1, e3l = A.fv.line_end[4 * r1 + 3];
-    const uint64_t n = (e3l < A.fv.nbytes ? e3l + 1 : e3l) - s0;
-    const uint32_t skew = (uint32_t)((uintptr_t)(A.fv.img + s0) & 15u);
-    bool fit = n <= (uint64_t)A.in_cap && n + kSplitOutSlack <= (uint64_t)A.out_cap;
-    if (fit) fit = (uint64_t)((skew + (uint32_t)n + 15u) >> 4) * 16u + 32u <= (uint64_t)A.in_cap;
+    uint64_t n;
+    const bool fit = frame_span_fits(A.fv, A.first + k0, A.first + k1, A.in_cap, n) && n + kSplitOutSlack <= (uint64_t)A.out_cap;
     big = A.has_nul || !fit;
     A.tile_big[tile] = big ? 1 : 0;
   }
@@ -97,60 +76,13 @@ struct SplitGeo {
   uint8_t big;
   __device__ __forceinline__ uint64_t start() const { return r0 ? 0ull : praw + 1; }
 };
-// the tile's span of the image in 16-byte units aligned on the image ADDRESS
-struct SplitSpan {
-  const uint8_t* gbase;
-  uint64_t s0;
-  uint32_t units, skew;
-};
-__device__ __forceinline__ void split_span(const SplitArgs& A, const SplitGeo& g, int last_lane, SplitSpan& sp) {
-  sp.s0 = rfl64(g.start());
-  const uint64_t e3l = rl64(g.e3, last_lane);
-  const uint64_t n = (e3l < A.fv.nbytes ? e3l + 1 : e3l) - sp.s0;
-  sp.skew = (uint32_t)((uintptr_t)(A.fv.img + sp.s0) & 15u);
-  sp.gbase = A.fv.img + sp.s0 - sp.skew;
-  const uint64_t units = ((uint64_t)sp.skew + n + 15u) >> 4;
-  sp.units = units > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)units;  // (a tile that large is a big one: nothing lands)
-}
-__device__ __forceinline__ bc_u32x4 split_unit(const SplitSpan& sp, uint32_t u) {
-  u = u < sp.units ? u : (sp.units ? sp.units - 1 : 0u);  // clamped: no branch, every load of a round in flight
-  return __builtin_nontemporal_load(reinterpret_cast<const bc_u32x4*>(sp.gbase + 16ull * u));
-}
-__device__ __forceinline__ void split_fetch(const SplitSpan& sp, int lane, bc_u32x4 (&v)[kSpanPf]) {
-#pragma unroll
-  for (int j = 0; j < kSpanPf; ++j) v[j] = split_unit(sp, (uint32_t)(j * kWave + lane));
-}
-__device__ __forceinline__ void split_land(const SplitSpan& sp, int lane, const bc_u32x4 (&v)[kSpanPf], uint8_t* s_in) {
-#pragma unroll
-  for (int j = 0; j < kSpanPf; ++j) {
-    const uint32_t u = (uint32_t)(j * kWave + lane);
-    if (u < sp.units) *reinterpret_cast<bc_u32x4*>(s_in + 16u * u) = v[j];
-  }
-  for (uint32_t u0 = kSpanPf * kWave; u0 < sp.units; u0 += 8 * kWave) {  // (larger tiles: the rest now)
-    bc_u32x4 q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = split_unit(sp, u0 + j * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t u = u0 + j * kWave + lane;
-      if (u < sp.units) *reinterpret_cast<bc_u32x4*>(s_in + 16u * u) = q[j];
-    }
-  }
-}
-
 __global__ __launch_bounds__(kWave, 2) void k_split_emit_tile(SplitArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_lds[];
   uint8_t* s_in = s_lds;
   uint8_t* s_out = s_lds + A.in_cap;
   const int lane = (int)threadIdx.x;
-  const uint64_t n_tiles = (A.n_rec + A.T - 1) / A.T;
-  auto tile_size = [&](uint64_t tile) {
-    const uint64_t left = A.n_rec - tile * A.T;
-    return (uint32_t)(left < (uint64_t)A.T ? left : (uint64_t)A.T);  // (even, >= 2)
-  };
-  auto geo_of = [&](uint64_t tile, SplitGeo& g) {
-    const uint32_t Tn = tile_size(tile);
-    const uint64_t k = tile * A.T + ((uint32_t)lane < Tn ? (uint32_t)lane : Tn - 1);
+  auto geo_of = [&](const TileAt& at, SplitGeo& g) {  // (Tn: even, >= 2)
+    const uint64_t k = at.tile * A.T + ((uint32_t)lane < at.Tn ? (uint32_t)lane : at.Tn - 1);
     const uint64_t r = A.first + k;
     const uint64_t* __restrict__ le = A.fv.line_end + 4 * r;
     g.r0 = r == 0 ? 1u : 0u;
@@ -158,44 +90,19 @@ __global__ __launch_bounds__(kWave, 2) void k_split_emit_tile(SplitArgs A) {
     g.e3 = le[3];
     g.off = A.local[k & 1][k >> 1];
     g.sum = A.sums[k & 1][(k >> 1) / kScan64Span];
-    g.big = A.tile_big[tile];
+    g.big = A.tile_big[at.tile];
   };
-  // three tiles under way per wavefront, every request without a branch (see k_bc_emit_tile)
-  const uint64_t stride = gridDim.x;
-  auto clamp_tile = [&](uint64_t t) { return t < n_tiles ? t : n_tiles - 1; };
-  SplitGeo cur, nxt, nx2;
-  bc_u32x4 pf[kSpanPf];
-  if (blockIdx.x < n_tiles) {
-    geo_of(blockIdx.x, cur);
-    geo_of(clamp_tile(blockIdx.x + stride), nxt);
-    SplitSpan sp;
-    split_span(A, cur, (int)tile_size(blockIdx.x) - 1, sp);
-    split_fetch(sp, lane, pf);
-  }
-  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += stride, cur = nxt, nxt = nx2) {
-    const uint32_t Tn = tile_size(tile);
-    const bool valid = (uint32_t)lane < Tn;
-    const bool big = __builtin_amdgcn_readfirstlane((int)cur.big) != 0;
-    const uint8_t* src;
-    uint32_t len;
-    {
-      SplitSpan sp;
-      split_span(A, cur, (int)Tn - 1, sp);
-      if (!big) split_land(sp, lane, pf, s_in);  // (fits: k_split_tile_flags checked)
-      const uint64_t b = cur.start();
-      len = (uint32_t)((cur.e3 < A.fv.nbytes ? cur.e3 + 1 : cur.e3) - b);
-      src = s_in + sp.skew + (uint32_t)(b - sp.s0);
-    }
-    {
-      const uint64_t tn = clamp_tile(tile + stride);
-      SplitSpan sp;
-      split_span(A, nxt, (int)tile_size(tn) - 1, sp);
-      split_fetch(sp, lane, pf);
-    }
-    geo_of(clamp_tile(tile + 2 * stride), nx2);
-    if (big) continue;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+  auto span = [&](const SplitGeo& g, const TileAt& at) { return span_of(A.fv, g.start(), g.e3, (int)at.Tn - 1); };
+  auto fetch = [&](const SplitGeo& g, const TileAt& at, bc_u32x4(&pf)[kSpanPf]) { span_fetch(span(g, at), lane, pf); };
+  auto stage = [&](const SplitGeo& cur, const TileAt& at, bool big, const bc_u32x4(&pf)[kSpanPf], BcLine& rec) {  // rec: the lane's record in LDS
+    const Span sp = span(cur, at);
+    if (!big) span_land(sp, lane, pf, s_in);  // (fits: k_split_tile_flags checked)
+    const uint64_t b = cur.start();
+    rec.len = (uint32_t)((cur.e3 < A.fv.nbytes ? cur.e3 + 1 : cur.e3) - b);
+    rec.p = s_in + sp.skew + (uint32_t)(b - sp.s0);
+  };
+  auto work = [&](const SplitGeo& cur, const TileAt& at, const BcLine& rec) {
+    const uint32_t Tn = at.Tn, len = rec.len;
     // the images of the two streams: lanes 0, 2, .. write the first, lanes 1, 3, .. the second
     const unsigned long long where = cur.off + cur.sum;
     const unsigned long long at0 = rl64(where, 0), at1 = rl64(where, 1);
@@ -205,17 +112,18 @@ __global__ __launch_bounds__(kWave, 2) void k_split_emit_tile(SplitArgs A) {
     uint8_t* dst1 = A.out[1] + at1;
     const uint32_t skew0 = (uint32_t)((uintptr_t)dst0 & 15u), skew1 = (uint32_t)((uintptr_t)dst1 & 15u);
     const uint32_t base1 = (skew0 + total0 + 15u) & ~15u;
-    if (valid) {
+    if ((uint32_t)lane < Tn) {
       const bool second = (lane & 1) != 0;
       LaneWriter w{s_out + (second ? base1 + skew1 : skew0) + (uint32_t)(where - (second ? at1 : at0))};
-      w.bytes(src, len);
+      w.bytes(rec.p, len);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     emit_flush(s_out, skew0, total0, dst0, lane);
     emit_flush(s_out + base1, skew1, total1, dst1, lane);
     __builtin_amdgcn_wave_barrier();
-  }
+  };
+  tile_walk<SplitGeo, BcLine>(A.n_rec, A.T, geo_of, fetch, stage, work);
 }
 
 // records of the tiles that do not fit LDS, and every record of an image with NUL bytes: one wavefront per record,
@@ -237,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_split_emit_direct(SplitArgs A) {
     uint8_t* dst = A.out[k & 1] + A.local[k & 1][p] + A.sums[k & 1][p / kScan64Span];
     if (A.has_nul) {  // what gzputs writes of a line is the C string: four pieces
       BcLine ln[4];
-      split_lines_nul(A.fv, r, ln);
+      frame_lines(A.fv, r, true, ln);
       const uint32_t m0 = ln[0].len + ln[0].nl, m1 = ln[1].len + ln[1].nl, m2 = ln[2].len + ln[2].nl, m3 = ln[3].len + ln[3].nl;
       split_copy_wave(ln[0].p, dst, m0, lane);
       split_copy_wave(ln[1].p, dst + m0, m1, lane);

@@ -108,6 +108,17 @@ unsigned resident_waves(fqg_ctx* c, const void* kernel, unsigned lds) {
   const unsigned waves = (unsigned)per_cu * (unsigned)c->cu_count;
   return env_cap ? std::min(env_cap, waves) : waves;
 }
+// The launch pair of a tile emitter, both kernels on the same arguments: `tile` on the resident grid for the tiles that fit
+// LDS, `direct` (direct_per_cu workgroups per CU) record by record for those that do not.  -> the tile kernel's grid or 0
+template <class KT, class KD, class... A>
+unsigned launch_tile_pair(fqg_ctx* c, KT tile, bool tiles, uint64_t n_tiles, unsigned lds, KD direct, bool big, uint64_t n_rec,
+                          unsigned direct_per_cu, const A&... args) {
+  const unsigned grid_t = tiles ? (unsigned)std::min<uint64_t>(n_tiles, resident_waves(c, (const void*)tile, lds)) : 0u;
+  const unsigned grid_e = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rec + 3) / 4, (uint64_t)c->cu_count * direct_per_cu));
+  if (tiles) hipLaunchKernelGGL(tile, dim3(grid_t), dim3(kWave), lds, c->stream, args...);
+  if (big) hipLaunchKernelGGL(direct, dim3(grid_e), dim3(kBlock), 0, c->stream, args...);
+  return grid_t;
+}
 
 // the call's counters zeroed on the device; `none`: what first_finding and first_discard start from
 int bcall_reset(fqg_ctx* c, unsigned long long none) {
