@@ -1058,8 +1058,7 @@ int stream_plan_parts(fqg_ctx* c, StreamCall& s) {
 // phase 4: pass 1, part by part (from the second on with the line workers of the part before), and the prefix over
 // each part's newline counts
 void stream_pass1_parts(fqg_ctx* c, const StreamCall& s) {
-  const int workers_env = env_int_early("FQGPU_STREAM_LINE_WORKERS", 1);  // line-worker workgroups per CU (read per call)
-  const unsigned workers = (unsigned)c->cu_count * (unsigned)std::min(std::max(workers_env, 1), 4);
+  const unsigned workers = (unsigned)c->cu_count;  // one line-worker workgroup per CU
   for (uint32_t part = 0; part < s.n_parts; ++part) {
     const uint32_t span_lo = s.part_begin(part), span_hi = s.part_begin(part + 1);
     const uint32_t chunk_lo = span_lo * kScanSpan, chunk_hi = std::min<uint32_t>(s.n_chunks, span_hi * kScanSpan);
@@ -1102,9 +1101,8 @@ int stream_lines(fqg_ctx* c, const StreamCall& s) {
                        (const uint32_t*)c->cinfo.p, s.limit, (uint32_t*)c->redo.p, c->d_cs);
   }
   // the index on demand: when the caller has not said it wants it, and nothing queued by pass 1 needs it (the
-  // queue kernel finds its records through the index).  FQGPU_EAGER_INDEX=1: always in this call (A/B)
-  static const bool eager_index = getenv("FQGPU_EAGER_INDEX") != nullptr;
-  const bool lazy = !s.want_index && !eager_index && c->h_cs->queue_count == 0;
+  // queue kernel finds its records through the index)
+  const bool lazy = !s.want_index && c->h_cs->queue_count == 0;
   // the steps the line workers inside the pass-1 launches have done (the parted pass): the launches below begin behind
   // them, and every line kernel of such a call adds to the context's accumulators, merged at the end
   const bool parted = s.n_parts > 1;
@@ -1124,13 +1122,12 @@ int stream_lines(fqg_ctx* c, const StreamCall& s) {
     // share after the others have finished)
     const uint64_t per_gpu = (uint64_t)c->cu_count * resident_per_cu(c->lines_per_cu, reinterpret_cast<const void*>(k_stream_lines<false>));
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((groups + 3) / 4, per_gpu));
-    static const bool general_only = getenv("FQGPU_LINES_GENERAL") != nullptr;  // (A/B: every step through the general kernel)
     // (more than 64 newlines in an average chunk - reads below 100 bases - or fewer than 32 - reads of kilobases: hardly a
     // step would qualify for the kernel without a search)
     const double nl_per_chunk = (double)s.n_newlines / (double)std::max<uint32_t>(s.n_chunks, 1);
     c->lazy.grid = grid;
     c->lazy.fast = false;
-    if (done_steps == 0 && (general_only || nl_per_chunk > 60.0 || nl_per_chunk < 32.0)) {
+    if (done_steps == 0 && (nl_per_chunk > 60.0 || nl_per_chunk < 32.0)) {
       hipLaunchKernelGGL(k_stream_lines<false>, dim3(grid), dim3(kBlock), 0, c->stream, A, (const uint8_t*)nullptr);
     } else {
       // the steps of ordinary records in the kernel without a search, what it marks in the general one behind it

@@ -36,6 +36,15 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
   return v;  // valid in lane 0
 }
+// minimum and maximum over the 64 lanes, as a butterfly: every lane ends with both
+__device__ __forceinline__ void wave_minmax(uint32_t& mn, uint32_t& mx) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint32_t a = __shfl_xor(mn, d, 64), b = __shfl_xor(mx, d, 64);
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+}
 // inclusive scan across the 64 lanes
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
 #pragma unroll
@@ -404,12 +413,7 @@ __device__ __forceinline__ RecOut validate_record(const FrameView& f, uint64_t r
       break;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t a = __shfl_xor(qmin, d, 64), b = __shfl_xor(qmax, d, 64);
-    qmin = a < qmin ? a : qmin;
-    qmax = b > qmax ? b : qmax;
-  }
+  wave_minmax(qmin, qmax);
   o.qmin = qmin;
   o.qmax = qmax;
   if (space == FQG_SPACE_SEQ && qlen != slen) {
@@ -621,6 +625,13 @@ __device__ __forceinline__ void qrange_accum(const uint4& v, uint32_t qm, QRange
     q.mx_o = pk_max_u16(q.mx_o, __builtin_amdgcn_perm(0u, hi, 0x0C030C01u));
   }
 }
+// the lane's range out of its four packed halves (255 / 0 when no byte was selected)
+__device__ __forceinline__ void qrange_minmax(const QRange& q, uint32_t& qmin, uint32_t& qmax) {
+  qmin = pk_min_u16(q.mn_e, q.mn_o);
+  qmax = pk_max_u16(q.mx_e, q.mx_o);
+  qmin = (qmin & 0xFFFFu) < (qmin >> 16) ? (qmin & 0xFFFFu) : (qmin >> 16);
+  qmax = (qmax & 0xFFFFu) > (qmax >> 16) ? (qmax & 0xFFFFu) : (qmax >> 16);
+}
 
 // The SWAR checks on one 16-byte piece whose bytes, two look-ahead bytes and lines all exist.
 // ABL is an ablation mask for tools/kbench (product code instantiates 0).
@@ -781,17 +792,11 @@ __global__ __launch_bounds__(kBlock) void k_frame_fast_t(const uint8_t* __restri
     line_end[cs->n_newlines] = n;
   if ((ABL & 7u) == 7u) return;
   // ---- fold the quality range: lanes -> wave -> device ----
-  uint32_t qmin = pk_min_u16(q.mn_e, q.mn_o), qmax = pk_max_u16(q.mx_e, q.mx_o);
-  qmin = (qmin & 0xFFFFu) < (qmin >> 16) ? (qmin & 0xFFFFu) : (qmin >> 16);
-  qmax = (qmax & 0xFFFFu) > (qmax >> 16) ? (qmax & 0xFFFFu) : (qmax >> 16);
+  uint32_t qmin, qmax;
+  qrange_minmax(q, qmin, qmax);
   qmin = gq_min < qmin ? gq_min : qmin;
   qmax = gq_max > qmax ? gq_max : qmax;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t a = __shfl_xor(qmin, d, 64), b = __shfl_xor(qmax, d, 64);
-    qmin = a < qmin ? a : qmin;
-    qmax = b > qmax ? b : qmax;
-  }
+  wave_minmax(qmin, qmax);
   if (lane == 0 && qmin <= qmax) {
     // plain reads first: after the first few wavefronts nobody improves the range any more
     if (qmin < cs->qmin_byte) atomicMin(&cs->qmin_byte, qmin);

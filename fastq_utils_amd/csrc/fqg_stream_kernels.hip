@@ -133,12 +133,7 @@ __global__ __launch_bounds__(kBootBlock) void k_stream_boot(const uint8_t* __res
     }
     line += (uint32_t)__builtin_popcountll(bal);
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t a = __shfl_xor(qmin, d, 64), b = __shfl_xor(qmax, d, 64);
-    qmin = a < qmin ? a : qmin;
-    qmax = b > qmax ? b : qmax;
-  }
+  wave_minmax(qmin, qmax);
   if (lane == 0 && qmin <= qmax) {
     atomicMin(&cs->boot_qmin, qmin);
     atomicMax(&cs->boot_qmax, qmax);
@@ -250,440 +245,339 @@ struct Pass1Lds {
   uint16_t slots[kBlock / kWave][kStageCap];
   __attribute__((aligned(16))) uint8_t copy[kBlock / kWave][NAMES ? kCopyRow : (uint32_t)kChunkBytes];
 };
+
+// ------------------------------------------------------------------------------------------
+// The steps of pass 1, in the order of the header comment: each takes what it reads and returns what it makes, and
+// stream_pass1_body below is their sequence.
+// ------------------------------------------------------------------------------------------
+// which chunk the wavefront has, and which lane of it this is
+struct ChunkLane {
+  uint32_t chunk;
+  uint64_t cb, wb;  // the chunk's first byte in the image; the first of the lane's 32 bytes of slice 0
+  bool interior;    // the chunk and the 4 bytes behind it lie inside the image (all but the last one or two chunks)
+  int lane;
+  uint8_t* copy;    // the wave's LDS copy of the chunk, in image order
+};
+
+// WAVE_PACK: the six mark packs of a chunk run on the matrix pipe (pack_marks32_wave, fqg_mark_pack.h): twelve MFMAs
+// where 48 v_dot4 stand.  Every one of them stands where the whole wavefront goes or does not go - a wavefront that is
+// in pass 1 has all 64 lanes (it leaves by chunk), `interior` depends on the chunk alone, and whether a chunk takes the
+// class tests of a typed chunk comes from ballots - so all 64 lanes supply their marks.  The weights depend on the lane
+// alone: one 16-byte load per chunk.
+template <bool WAVE_PACK>
+struct MarkPack {
+  pack_v4i wts = {0, 0, 0, 0};
+  __device__ __forceinline__ explicit MarkPack(int lane) {
+    if (WAVE_PACK) wts = pack_weights(lane);
+  }
+  __device__ __forceinline__ uint32_t operator()(uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3, uint32_t m4, uint32_t m5,
+                                                 uint32_t m6, uint32_t m7) const {
+    if constexpr (WAVE_PACK) return pack_marks32_wave(wts, m0, m1, m2, m3, m4, m5, m6, m7);
+    else return pack_marks32(m0, m1, m2, m3, m4, m5, m6, m7);
+  }
+};
+
+// ---- load and marks, interior form: a chunk that lies inside the image with the 4 bytes behind it ----
+// 16-byte loads, SWAR marks, the LDS copy.  Out: nl = newline bits of the lane's 32 bytes per slice, v = the bytes,
+// tail = the 4 bytes after the chunk (look-ahead of the last lane), prev (NAMES) = the byte in front of the chunk,
+// flags = the image flags the chunk raises.  (The edge form - the last one or two chunks - stands in stream_pass1_body.)
+template <uint32_t ABL, int NAMES, class PACK>
+__device__ __forceinline__ void load_marks_interior(const uint8_t* __restrict__ img, const ChunkLane& c, const PACK& pack,
+                                                    uint32_t (&nl)[kHalves], Piece32 (&v)[kHalves], uint32_t& tail, uint32_t& prev,
+                                                    uint32_t& flags) {
+  tail = *reinterpret_cast<const uint32_t*>(img + c.cb + kChunkBytes);
+  if (NAMES && c.chunk) prev = *reinterpret_cast<const uint32_t*>(img + c.cb - 4) >> 24;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    v[k].a = *reinterpret_cast<const uint4*>(img + c.wb + (uint64_t)k * kHalfBytes);
+    v[k].b = *reinterpret_cast<const uint4*>(img + c.wb + (uint64_t)k * kHalfBytes + 16);
+  }
+  if (!(ABL & 6u)) {
+#pragma unroll
+    for (int k = 0; k < kHalves; ++k) {
+      *reinterpret_cast<uint4*>(&c.copy[k * kHalfBytes + c.lane * kLaneBytes]) = v[k].a;
+      *reinterpret_cast<uint4*>(&c.copy[k * kHalfBytes + c.lane * kLaneBytes + 16]) = v[k].b;
+    }
+  }
+  uint32_t hiacc = 0, badacc = 0;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    hiacc = or3(or3(or3(or3(hiacc, v[k].a.x, v[k].a.y), v[k].a.z, v[k].a.w), v[k].b.x, v[k].b.y), v[k].b.z, v[k].b.w);
+    nl[k] = pack(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc), nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc),
+                   nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc), nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
+  }
+  const bool high = __ballot((hiacc & kH) != 0) != 0;
+  const bool ctrl = __ballot((badacc & kH) != 0) != 0;
+  if (high) flags |= kFlagHigh;  // (the masks above are meaningless then; the host drops this pass)
+  if (ctrl && !high) {
+    // rare: a control byte other than '\n'.  Only NUL and CR change what a line is (C strings,
+    // src/fastq.c:250,317); anything else (a tab in a header ...) is just a byte.
+    uint32_t nul = 0, cr = 0;
+#pragma unroll
+    for (int k = 0; k < kHalves; ++k) {
+      const uint32_t w[8] = {v[k].a.x, v[k].a.y, v[k].a.z, v[k].a.w, v[k].b.x, v[k].b.y, v[k].b.z, v[k].b.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        nul |= eq_bytes(w[j], 0u);
+        cr |= eq_bytes(w[j], 0x0D0D0D0Du);
+      }
+    }
+    if (__ballot(nul != 0)) flags |= kFlagNul;
+    if (__ballot(cr != 0)) flags |= kFlagCr;
+  }
+}
+
+// ---- ranks of the newlines inside the chunk: one packed scan for both slices ----
+struct NlRanks {
+  uint32_t ex[kHalves];  // rank in the chunk of the first newline of the lane's 32 bytes, per slice
+  uint32_t total;        // newlines of the chunk
+  uint32_t staged;       // ... that have a slot in the staging area
+};
+// (a chunk with more newlines than slots raises kFlagStageOverflow in `flags`)
+__device__ __forceinline__ NlRanks rank_newlines(const uint32_t (&nl)[kHalves], uint32_t& flags) {
+  static_assert(kHalves == 2 && kHalves * kHalfBytes == kChunkBytes, "one packed scan covers the two slices");
+  NlRanks r;
+  const uint32_t c01 = __popc(nl[0]) | (__popc(nl[1]) << 16);
+  const uint32_t s01 = wave_scan_incl_dpp(c01);
+  const uint32_t t01 = __builtin_amdgcn_readlane(s01, 63);
+  r.total = (t01 & 0xFFFFu) + (t01 >> 16);
+  r.ex[0] = (s01 & 0xFFFFu) - (c01 & 0xFFFFu);
+  r.ex[1] = (t01 & 0xFFFFu) + (s01 >> 16) - (c01 >> 16);
+  if (r.total > (uint32_t)kStageCap) flags |= kFlagStageOverflow;
+  r.staged = r.total < (uint32_t)kStageCap ? r.total : (uint32_t)kStageCap;
+  return r;
+}
+
+// ---- look-ahead: newline bits of the bytes 1 and 2 further on (funnel shifts over {next lane, this lane}) ----
+struct LookAhead {
+  uint32_t nl2[kHalves];   // the byte two places on is a '\n'
+  uint32_t cand[kHalves];  // a '\n' followed by exactly one byte and another '\n'
+};
+__device__ __forceinline__ LookAhead look_ahead(const uint8_t* __restrict__ img, uint64_t n, const ChunkLane& c,
+                                                const uint32_t (&nl)[kHalves], uint32_t tail) {
+  uint32_t tail_nl = 0;
+  if (c.interior) {
+    tail_nl = ((tail & 0xFFu) == '\n' ? 1u : 0u) | (((tail >> 8) & 0xFFu) == '\n' ? 2u : 0u);
+  } else {
+    for (uint64_t i = 0; i < 2; ++i)
+      if (c.cb + kChunkBytes + i < n && img[c.cb + kChunkBytes + i] == '\n') tail_nl |= 1u << i;
+  }
+  LookAhead la;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    uint32_t nxt = dpp0<0x130, 0xf, 0xf>(nl[k]);  // lane i <- lane i+1
+    const uint32_t first_next = (uint32_t)__builtin_amdgcn_readlane(nl[k + 1 < kHalves ? k + 1 : k], 0);
+    if (c.lane == 63) nxt = k + 1 < kHalves ? first_next : tail_nl;
+    const uint32_t n1 = __builtin_amdgcn_alignbit(nxt, nl[k], 1);
+    la.nl2[k] = __builtin_amdgcn_alignbit(nxt, nl[k], 2);
+    la.cand[k] = nl[k] & la.nl2[k] & ~n1;
+  }
+  return la;
+}
+
+// ---- speculation: the first line of exactly one byte is taken for a "+" line (type 2) ----
+struct Speculation {
+  bool found;   // a line type was speculated
+  uint32_t t0;  // ... for the chunk's first byte
+};
+__device__ __forceinline__ Speculation speculate(const uint32_t (&nl)[kHalves], const uint32_t (&ex)[kHalves],
+                                                 const uint32_t (&cand)[kHalves]) {
+  Speculation sp{false, 0};
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    const uint64_t bal = __ballot(cand[k] != 0);
+    if (!sp.found && bal) {
+      const int l = __builtin_ctzll(bal);
+      const uint32_t cl = (uint32_t)__builtin_amdgcn_readlane(cand[k], l);
+      const uint32_t nll = (uint32_t)__builtin_amdgcn_readlane(nl[k], l);
+      const uint32_t exl = (uint32_t)__builtin_amdgcn_readlane(ex[k], l);
+      const uint32_t j = (uint32_t)__builtin_ctz(cl);
+      const uint32_t a = exl + __popc(nll & ((1u << j) - 1u));  // rank in the chunk of the '\n' in front of the "+"
+      sp.t0 = (1u - a) & 3u;  // the next '\n' (rank a + 1) ends a type-2 line
+      sp.found = true;
+    }
+  }
+  return sp;
+}
+
+// ---- class tests ----
+// The type masks are spans between a lane's first three newlines (fqg_type_spans.h): M1 the bytes of sequence lines, M3
+// those of quality lines (the newline bytes are in neither mask).  False for a chunk with a lane of four or more newlines
+// in 32 bytes - reads under 25 bases: it makes no class tests and queues nothing, it stays kInfoUnknown, and
+// k_stream_chunks sends it to the redo list, where the two-pass kernel repeats the checks exactly.  (The speculation
+// stands: the name capture does not use the masks.)
+__device__ __forceinline__ bool chunk_type_spans(const uint32_t (&nl)[kHalves], const uint32_t (&ex)[kHalves], uint32_t t0,
+                                                 uint32_t (&M1)[kHalves], uint32_t (&M3)[kHalves]) {
+  uint32_t over = 0;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) over |= type_spans32(nl[k], t0 + ex[k], M1[k], M3[k]);
+  return __ballot(over != 0) == 0;
+}
+
+// the range the quality bytes are tested against: the boot range, or the empty range 127 .. 0 - every byte outside - when
+// the boot window gave none or one beyond the 7-bit bytes of the SWAR tests
+struct QBounds {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ QBounds test_bounds(QBounds boot) {
+  if (boot.lo > boot.hi || boot.lo > 127u) {
+    boot.lo = 127u;
+    boot.hi = 0u;
+  }
+  return boot;
+}
+// the exact range of a chunk's quality bytes, over the wavefront, as bits of the chunk info word (none: no byte selected)
+__device__ __forceinline__ uint32_t range_info(const QRange& q) {
+  uint32_t qmin, qmax;
+  qrange_minmax(q, qmin, qmax);
+  wave_minmax(qmin, qmax);
+  return qmin <= qmax ? kInfoRange | ((qmin & 0xFFu) << 8) | ((qmax & 0xFFu) << 16) : 0u;
+}
+
+// A chunk with a speculated type t0 and its masks: bases outside ACGTN on sequence lines are queued as suspect byte
+// positions; quality bytes are tested against the boot range, and a slice with one outside it computes its exact range.
+// Returns the chunk info word.
+template <uint32_t ABL, class PACK>
+__device__ __forceinline__ uint32_t typed_chunk_tests(const ChunkLane& c, const Piece32 (&v)[kHalves], const uint32_t (&M1)[kHalves],
+                                                      const uint32_t (&M3)[kHalves], uint32_t t0, QBounds boot, const PACK& pack,
+                                                      const StreamOut& o, CallState* __restrict__ cs) {
+  const QBounds t = test_bounds(boot);
+  const uint32_t hihb_s = ((t.hi & 0x7Fu) | 0x80u) * 0x01010101u;
+  // (in vector registers: a subtraction that reads an SGPR issues in 4 cycles instead of 2, and a three-operand
+  // instruction cannot hold a literal - the compiler would keep all three in SGPRs)
+  const uint32_t lo_add = in_vgpr((0x80u - t.lo) * 0x01010101u), hihb = in_vgpr(hihb_s), khv = in_vgpr(kH);
+  QRange q{0x00FF00FFu, 0x00FF00FFu, 0u, 0u};
+  bool any_viol = false;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    const uint4 &a = v[k].a, &b = v[k].b;
+    const uint32_t inv = pack(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w), not_acgtn7(b.x), not_acgtn7(b.y),
+                              not_acgtn7(b.z), not_acgtn7(b.w));
+    const uint32_t bad = (ABL & 8u) ? 0u : inv & M1[k];
+    if (bad) queue_suspect(o, cs, c.wb + (uint64_t)k * kHalfBytes + (uint32_t)__builtin_ctz(bad));
+    const uint32_t okq = pack(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
+                              in_range7a(a.w, lo_add, hihb, khv), in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv),
+                              in_range7a(b.z, lo_add, hihb, khv), in_range7a(b.w, lo_add, hihb, khv));
+    const uint32_t qm = (ABL & 16u) ? 0u : M3[k];
+    if (__ballot((qm & ~okq) != 0)) {  // rare: exact range of this slice's quality bytes
+      any_viol = true;
+      qrange_accum(a, qm & 0xFFFFu, q);
+      qrange_accum(b, qm >> 16, q);
+    }
+  }
+  uint32_t info = t0;
+  if (any_viol) info |= range_info(q);
+  return info;
+}
+
+// A chunk without any newline lies inside ONE line (reads of kilobases: most chunks).  There is no type to speculate
+// on, but both kinds of check can be made on all of its bytes, and the rank says later which one counts
+// (chunk_info_redo / chunk_info_range).  A branch of its own in stream_pass1_body: the typed path is the 150 bp path
+// and pays for every instruction.  Returns the chunk info word.
+__device__ __forceinline__ uint32_t one_line_tests(const Piece32 (&v)[kHalves], QBounds boot) {
+  uint32_t info = kInfoOneLine;
+  const QBounds t = test_bounds(boot);
+  const uint32_t lob = t.lo * 0x01010101u, hihb = ((t.hi & 0x7Fu) | 0x80u) * 0x01010101u;
+  uint32_t not_base = 0, outside = 0;
+#pragma unroll
+  for (int k = 0; k < kHalves; ++k) {
+    const uint32_t w[8] = {v[k].a.x, v[k].a.y, v[k].a.z, v[k].a.w, v[k].b.x, v[k].b.y, v[k].b.z, v[k].b.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      not_base |= not_acgtn7(w[j]);
+      outside |= ~in_range7(w[j], lob, hihb) & kH;
+    }
+  }
+  if (__ballot(not_base != 0)) info |= kInfoNotBases;  // (which byte: the repeated check finds it, if the line is a sequence)
+  if (__ballot(outside != 0)) {  // rare: the exact range of the chunk's bytes
+    QRange q{0x00FF00FFu, 0x00FF00FFu, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < kHalves; ++k) {
+      qrange_accum(v[k].a, 0xFFFFu, q);
+      qrange_accum(v[k].b, 0xFFFFu, q);
+    }
+    info |= range_info(q);
+  }
+  return info;
+}
+
+// ---- the chunk's results ----
+__device__ __forceinline__ void write_chunk_results(const StreamOut& o, CallState* __restrict__ cs, const ChunkLane& c, uint32_t total,
+                                                    uint32_t info, uint32_t flags) {
+  if (c.lane == 0) {
+    o.counts[c.chunk] = total;
+    o.cinfo[c.chunk] = info;
+    if (flags) atomicOr(&cs->flags, flags);
+  }
+}
+
+}  // namespace fqg
+#include "fqg_name_capture.h"  // capture_digests, capture_records: behind ChunkLane, NlRanks and Speculation
+namespace fqg {
+
 // block: which workgroup of the pass this is (chunks 4 block .. 4 block + 3), n_chunks: the pass ends in front of it
 template <uint32_t ABL, int NAMES, bool WAVE_PACK>
 __device__ __forceinline__ void stream_pass1_body(const uint8_t* __restrict__ img, uint64_t n, uint32_t n_chunks, const StreamOut& o,
                                                   CallState* __restrict__ cs, const NameCapture& nc, uint32_t block,
                                                   Pass1Lds<NAMES>& lds) {
-  static_assert(kHalves == 2 && kHalves * kHalfBytes == kChunkBytes, "one packed scan covers the two slices");
   static_assert(NAMES == 0 || !(ABL & 7u), "the name capture needs the speculation, the staged entries and the copy");
-  auto& s_slots = lds.slots;
-  auto& s_copy = lds.copy;
   // (the wave index is uniform: telling the compiler keeps chunk-level values in scalar registers)
   const int lane = lane_id(), wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint8_t* const copy = s_copy[wv] + (NAMES ? kCopyFront : 0u);
+  uint8_t* const copy = lds.copy[wv] + (NAMES ? kCopyFront : 0u);
   const uint32_t chunk = block * (kBlock / kWave) + wv;
   if (chunk >= n_chunks) return;
   const uint64_t cb = (uint64_t)chunk * kChunkBytes;
-  const uint64_t wb = cb + (uint64_t)lane * kLaneBytes;
-  const bool interior = cb + kChunkBytes + 4 <= n;
-  // WAVE_PACK: the six mark packs of a chunk run on the matrix pipe (pack_marks32_wave, fqg_mark_pack.h): twelve MFMAs
-  // where 48 v_dot4 stand.  Every one of them stands where the whole wavefront goes or does not go - a wavefront that is
-  // here has all 64 lanes (the return above is by chunk), `interior` depends on the chunk alone, and `found && !dense` comes
-  // from ballots - so all 64 lanes supply their marks.  The weights depend on the lane alone: one 16-byte load per chunk.
-  pack_v4i wts = {0, 0, 0, 0};
-  if (WAVE_PACK) wts = pack_weights(lane);
-  auto pack = [&](uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3, uint32_t m4, uint32_t m5, uint32_t m6, uint32_t m7) {
-    if constexpr (WAVE_PACK) return pack_marks32_wave(wts, m0, m1, m2, m3, m4, m5, m6, m7);
-    else return pack_marks32(m0, m1, m2, m3, m4, m5, m6, m7);
-  };
-  uint32_t nl[kHalves], ex[kHalves];
-  Piece32 v[kHalves];
-  uint32_t flags = 0;
+  const ChunkLane c{chunk, cb, cb + (uint64_t)lane * kLaneBytes, cb + kChunkBytes + 4 <= n, lane, copy};
+  const MarkPack<WAVE_PACK> pack(lane);
+  const QBounds boot{cs->boot_qmin, cs->boot_qmax};
 
-  uint32_t tail = 0;  // the 4 bytes after the chunk (look-ahead of the last lane)
+  uint32_t nl[kHalves];  // newline bits of the lane's 32 bytes, per slice
+  Piece32 v[kHalves];    // the bytes themselves
+  uint32_t tail = 0;     // the 4 bytes after the chunk (look-ahead of the last lane)
   uint32_t prev = '\n';  // NAMES: the byte in front of the chunk (the image starts behind a virtual newline)
-  const uint32_t boot_lo = cs->boot_qmin, boot_hi = cs->boot_qmax;
-  if (interior) {
-    tail = *reinterpret_cast<const uint32_t*>(img + cb + kChunkBytes);
-    if (NAMES && chunk) prev = *reinterpret_cast<const uint32_t*>(img + cb - 4) >> 24;
-#pragma unroll
-    for (int k = 0; k < kHalves; ++k) {
-      v[k].a = *reinterpret_cast<const uint4*>(img + wb + (uint64_t)k * kHalfBytes);
-      v[k].b = *reinterpret_cast<const uint4*>(img + wb + (uint64_t)k * kHalfBytes + 16);
-    }
-    if (!(ABL & 6u)) {
-#pragma unroll
-      for (int k = 0; k < kHalves; ++k) {
-        *reinterpret_cast<uint4*>(&copy[k * kHalfBytes + lane * kLaneBytes]) = v[k].a;
-        *reinterpret_cast<uint4*>(&copy[k * kHalfBytes + lane * kLaneBytes + 16]) = v[k].b;
-      }
-    }
-    uint32_t hiacc = 0, badacc = 0;
-#pragma unroll
-    for (int k = 0; k < kHalves; ++k) {
-      hiacc = or3(or3(or3(or3(hiacc, v[k].a.x, v[k].a.y), v[k].a.z, v[k].a.w), v[k].b.x, v[k].b.y), v[k].b.z, v[k].b.w);
-      nl[k] = pack(nl_marks7(v[k].a.x, badacc), nl_marks7(v[k].a.y, badacc), nl_marks7(v[k].a.z, badacc), nl_marks7(v[k].a.w, badacc),
-                   nl_marks7(v[k].b.x, badacc), nl_marks7(v[k].b.y, badacc), nl_marks7(v[k].b.z, badacc), nl_marks7(v[k].b.w, badacc));
-    }
-    const bool high = __ballot((hiacc & kH) != 0) != 0;
-    const bool ctrl = __ballot((badacc & kH) != 0) != 0;
-    if (high) flags |= kFlagHigh;  // (the masks above are meaningless then; the host drops this pass)
-    if (ctrl && !high) {
-      // rare: a control byte other than '\n'.  Only NUL and CR change what a line is (C strings,
-      // src/fastq.c:250,317); anything else (a tab in a header ...) is just a byte.
-      uint32_t nul = 0, cr = 0;
-#pragma unroll
-      for (int k = 0; k < kHalves; ++k) {
-        const uint32_t w[8] = {v[k].a.x, v[k].a.y, v[k].a.z, v[k].a.w, v[k].b.x, v[k].b.y, v[k].b.z, v[k].b.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          nul |= eq_bytes(w[j], 0u);
-          cr |= eq_bytes(w[j], 0x0D0D0D0Du);
-        }
-      }
-      if (__ballot(nul != 0)) flags |= kFlagNul;
-      if (__ballot(cr != 0)) flags |= kFlagCr;
-    }
-  } else {
-    // the last one or two chunks: bytes may be missing, look-ahead may cross the end of the image
+  uint32_t flags = 0;    // image flags this chunk raises
+  if (c.interior) load_marks_interior<ABL, NAMES>(img, c, pack, nl, v, tail, prev, flags);
+  else {
+    // Load and marks, edge form - the last one or two chunks: bytes may be missing, look-ahead may cross the end of the
+    // image.  (Left here: as a function of its own, however it hands its marks back, these twenty lines cost the 150 bp
+    // path of every pass-1 kernel eight more vector registers and a spill - docs/measurement_history.md.)
     uint32_t bad = 0;
 #pragma unroll
     for (int k = 0; k < kHalves; ++k) {
-      const uint64_t off = wb + (uint64_t)k * kHalfBytes;
+      const uint64_t off = c.wb + (uint64_t)k * kHalfBytes;
       nl[k] = 0;
       v[k].a = v[k].b = make_uint4(0, 0, 0, 0);
       for (uint64_t i = off; i < n && i < off + kLaneBytes; ++i) {
-        const uint32_t c = img[i];
-        if (c == '\n') nl[k] |= 1u << (i - off);
-        else if (c == 0u) bad |= kFlagNul;
-        else if (c == '\r') bad |= kFlagCr;
-        else if (c >= 0x80u) bad |= kFlagHigh;
+        const uint32_t ch = img[i];
+        if (ch == '\n') nl[k] |= 1u << (i - off);
+        else if (ch == 0u) bad |= kFlagNul;
+        else if (ch == '\r') bad |= kFlagCr;
+        else if (ch >= 0x80u) bad |= kFlagHigh;
       }
     }
     if (__ballot((bad & kFlagNul) != 0)) flags |= kFlagNul;
     if (__ballot((bad & kFlagCr) != 0)) flags |= kFlagCr;
     if (__ballot((bad & kFlagHigh) != 0)) flags |= kFlagHigh;
   }
-
-  // ranks of the newlines inside the chunk: one packed scan for both slices
-  const uint32_t c01 = __popc(nl[0]) | (__popc(nl[1]) << 16);
-  const uint32_t s01 = wave_scan_incl_dpp(c01);
-  const uint32_t t01 = __builtin_amdgcn_readlane(s01, 63);
-  const uint32_t total = (t01 & 0xFFFFu) + (t01 >> 16);
-  ex[0] = (s01 & 0xFFFFu) - (c01 & 0xFFFFu);
-  ex[1] = (t01 & 0xFFFFu) + (s01 >> 16) - (c01 >> 16);
-  if (total > (uint32_t)kStageCap) flags |= kFlagStageOverflow;
-
-  // newline bits of the bytes 1 and 2 further on (funnel shifts over {next lane, this lane})
-  uint32_t tail_nl = 0;
-  if (interior) {
-    tail_nl = ((tail & 0xFFu) == '\n' ? 1u : 0u) | (((tail >> 8) & 0xFFu) == '\n' ? 2u : 0u);
-  } else {
-    for (uint64_t i = 0; i < 2; ++i)
-      if (cb + kChunkBytes + i < n && img[cb + kChunkBytes + i] == '\n') tail_nl |= 1u << i;
-  }
-  uint32_t nl2[kHalves], cand[kHalves];
-#pragma unroll
-  for (int k = 0; k < kHalves; ++k) {
-    uint32_t nxt = dpp0<0x130, 0xf, 0xf>(nl[k]);  // lane i <- lane i+1
-    const uint32_t first_next = (uint32_t)__builtin_amdgcn_readlane(nl[k + 1 < kHalves ? k + 1 : k], 0);
-    if (lane == 63) nxt = k + 1 < kHalves ? first_next : tail_nl;
-    const uint32_t n1 = __builtin_amdgcn_alignbit(nxt, nl[k], 1);
-    nl2[k] = __builtin_amdgcn_alignbit(nxt, nl[k], 2);
-    cand[k] = nl[k] & nl2[k] & ~n1;  // a '\n' followed by exactly one byte and another '\n'
-  }
-
-  const uint32_t tot = total < (uint32_t)kStageCap ? total : (uint32_t)kStageCap;
+  const NlRanks r = rank_newlines(nl, flags);
+  const LookAhead la = look_ahead(img, n, c, nl, tail);
 
   uint32_t info = kInfoUnknown;
-  bool found = false;  // a line type was speculated
-  uint32_t t0 = 0;     // ... for the chunk's first byte
-  if (!(ABL & 1u) && interior && !(flags & kFlagHigh)) {
-    // ---- speculation: the first line of exactly one byte is taken for a "+" line (type 2) ----
-#pragma unroll
-    for (int k = 0; k < kHalves; ++k) {
-      const uint64_t bal = __ballot(cand[k] != 0);
-      if (!found && bal) {
-        const int l = __builtin_ctzll(bal);
-        const uint32_t cl = (uint32_t)__builtin_amdgcn_readlane(cand[k], l);
-        const uint32_t nll = (uint32_t)__builtin_amdgcn_readlane(nl[k], l);
-        const uint32_t exl = (uint32_t)__builtin_amdgcn_readlane(ex[k], l);
-        const uint32_t j = (uint32_t)__builtin_ctz(cl);
-        const uint32_t a = exl + __popc(nll & ((1u << j) - 1u));  // rank in the chunk of the '\n' in front of the "+"
-        t0 = (1u - a) & 3u;  // the next '\n' (rank a + 1) ends a type-2 line
-        found = true;
-      }
-    }
-    // The type masks are spans between a lane's first three newlines (fqg_type_spans.h).  A chunk with a lane of four or
-    // more newlines in 32 bytes - reads under 25 bases - makes no class tests here and queues nothing: it stays
-    // kInfoUnknown, and k_stream_chunks sends it to the redo list, where the two-pass kernel repeats the checks exactly.
-    // (`found` and t0 stand: the name capture below does not use the masks.)
+  Speculation sp{false, 0};
+  if (!(ABL & 1u) && c.interior && !(flags & kFlagHigh)) {
+    sp = speculate(nl, r.ex, la.cand);
     uint32_t M1[kHalves], M3[kHalves];
-    bool dense = false;
-    if (found) {
-      uint32_t over = 0;
-#pragma unroll
-      for (int k = 0; k < kHalves; ++k) over |= type_spans32(nl[k], t0 + ex[k], M1[k], M3[k]);  // (the newline bytes are in neither mask)
-      dense = __ballot(over != 0) != 0;
-    }
-    if (found && !dense) {
-      info = t0;
-      uint32_t lo = boot_lo, hi = boot_hi;
-      if (lo > hi || lo > 127u) {
-        lo = 127u;
-        hi = 0u;
-      }
-      const uint32_t hihb_s = ((hi & 0x7Fu) | 0x80u) * 0x01010101u;
-      // (in vector registers: a subtraction that reads an SGPR issues in 4 cycles instead of 2, and a three-operand
-      // instruction cannot hold a literal - the compiler would keep all three in SGPRs)
-      const uint32_t lo_add = in_vgpr((0x80u - lo) * 0x01010101u), hihb = in_vgpr(hihb_s), khv = in_vgpr(kH);
-      QRange q{0x00FF00FFu, 0x00FF00FFu, 0u, 0u};
-      bool any_viol = false;
-#pragma unroll
-      for (int k = 0; k < kHalves; ++k) {
-        const uint4 &a = v[k].a, &b = v[k].b;
-        const uint32_t inv = pack(not_acgtn7(a.x), not_acgtn7(a.y), not_acgtn7(a.z), not_acgtn7(a.w), not_acgtn7(b.x), not_acgtn7(b.y),
-                                  not_acgtn7(b.z), not_acgtn7(b.w));
-        const uint32_t bad = (ABL & 8u) ? 0u : inv & M1[k];
-        if (bad) queue_suspect(o, cs, wb + (uint64_t)k * kHalfBytes + (uint32_t)__builtin_ctz(bad));
-        const uint32_t okq = pack(in_range7a(a.x, lo_add, hihb, khv), in_range7a(a.y, lo_add, hihb, khv), in_range7a(a.z, lo_add, hihb, khv),
-                                  in_range7a(a.w, lo_add, hihb, khv), in_range7a(b.x, lo_add, hihb, khv), in_range7a(b.y, lo_add, hihb, khv),
-                                  in_range7a(b.z, lo_add, hihb, khv), in_range7a(b.w, lo_add, hihb, khv));
-        const uint32_t qm = (ABL & 16u) ? 0u : M3[k];
-        if (__ballot((qm & ~okq) != 0)) {  // rare: exact range of this slice's quality bytes
-          any_viol = true;
-          qrange_accum(a, qm & 0xFFFFu, q);
-          qrange_accum(b, qm >> 16, q);
-        }
-      }
-      if (any_viol) {
-        uint32_t qmin = pk_min_u16(q.mn_e, q.mn_o), qmax = pk_max_u16(q.mx_e, q.mx_o);
-        qmin = (qmin & 0xFFFFu) < (qmin >> 16) ? (qmin & 0xFFFFu) : (qmin >> 16);
-        qmax = (qmax & 0xFFFFu) > (qmax >> 16) ? (qmax & 0xFFFFu) : (qmax >> 16);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-          const uint32_t x = __shfl_xor(qmin, d, 64), y = __shfl_xor(qmax, d, 64);
-          qmin = x < qmin ? x : qmin;
-          qmax = y > qmax ? y : qmax;
-        }
-        if (qmin <= qmax) info |= kInfoRange | ((qmin & 0xFFu) << 8) | ((qmax & 0xFFu) << 16);
-      }
-    } else if (total == 0) {
-      // A chunk without any newline lies inside ONE line (reads of kilobases: most chunks).  There is no type to
-      // speculate on, but both kinds of check can be made on all of its bytes, and the rank says later which one
-      // counts (chunk_info_redo / chunk_info_range).  A branch of its own: the path above is the 150 bp path and
-      // pays for every instruction.
-      info = kInfoOneLine;
-      uint32_t lo = boot_lo, hi = boot_hi;
-      if (lo > hi || lo > 127u) {
-        lo = 127u;
-        hi = 0u;
-      }
-      const uint32_t lob = lo * 0x01010101u, hihb = ((hi & 0x7Fu) | 0x80u) * 0x01010101u;
-      uint32_t not_base = 0, outside = 0;
-#pragma unroll
-      for (int k = 0; k < kHalves; ++k) {
-        const uint32_t w[8] = {v[k].a.x, v[k].a.y, v[k].a.z, v[k].a.w, v[k].b.x, v[k].b.y, v[k].b.z, v[k].b.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          not_base |= not_acgtn7(w[j]);
-          outside |= ~in_range7(w[j], lob, hihb) & kH;
-        }
-      }
-      if (__ballot(not_base != 0)) info |= kInfoNotBases;  // (which byte: the repeated check finds it, if the line is a sequence)
-      if (__ballot(outside != 0)) {  // rare: the exact range of the chunk's bytes
-        QRange q{0x00FF00FFu, 0x00FF00FFu, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < kHalves; ++k) {
-          qrange_accum(v[k].a, 0xFFFFu, q);
-          qrange_accum(v[k].b, 0xFFFFu, q);
-        }
-        uint32_t qmin = pk_min_u16(q.mn_e, q.mn_o), qmax = pk_max_u16(q.mx_e, q.mx_o);
-        qmin = (qmin & 0xFFFFu) < (qmin >> 16) ? (qmin & 0xFFFFu) : (qmin >> 16);
-        qmax = (qmax & 0xFFFFu) > (qmax >> 16) ? (qmax & 0xFFFFu) : (qmax >> 16);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-          const uint32_t x = __shfl_xor(qmin, d, 64), y = __shfl_xor(qmax, d, 64);
-          qmin = x < qmin ? x : qmin;
-          qmax = y > qmax ? y : qmax;
-        }
-        if (qmin <= qmax) info |= kInfoRange | ((qmin & 0xFFu) << 8) | ((qmax & 0xFFu) << 16);
-      }
-    }
+    if (sp.found && chunk_type_spans(nl, r.ex, sp.t0, M1, M3)) info = typed_chunk_tests<ABL>(c, v, M1, M3, sp.t0, boot, pack, o, cs);
+    else if (r.total == 0) info = one_line_tests(v, boot);
   }
 
   if (!(ABL & 2u)) {
-    stage_chunk<ABL>(img, n, cb, chunk, nl, nl2, ex, tot, total <= (uint32_t)kStageCap, s_slots[wv], copy, tail, o.stage, interior);
+    stage_chunk<ABL>(img, n, c.cb, c.chunk, nl, la.nl2, r.ex, r.staged, r.total <= (uint32_t)kStageCap, lds.slots[wv], c.copy, tail,
+                     o.stage, c.interior);
   }
-  if constexpr (NAMES == 2) {
-    // ---- header lines that begin in this chunk -> 16-byte digests: canonical name + hash, four lanes per header ----
-    // The line that starts at v (v = 0: the chunk's first byte, else behind the chunk's v-th newline) has type t0 + v:
-    // headers are every fourth line start from v0 on, so quad q of the wavefront takes the header at v0 + 4 q without a
-    // compaction.  Lane `sub` of a quad looks at name bytes [16 sub, 16 sub + 16) - the bytes behind the '@'.
-    uint32_t hc = kNoCapture;
-    if (found && total <= (uint32_t)kStageCap) {
-      hc = 0;
-      const uint16_t* slots = s_slots[wv];
-      const bool first_is_start = prev == '\n';
-      uint32_t v0 = (0u - t0) & 3u;
-      if (v0 == 0u && !first_is_start) v0 = 4u;
-      const uint32_t sub = (uint32_t)lane & 3u, q = (uint32_t)lane >> 2;
-      const bool casava = nc.fmt == FQG_NAME_CASAVA18;
-      const uint32_t pe_cut = (nc.fmt == FQG_NAME_DEFAULT && nc.is_pe) ? 1u : 0u;
-      for (uint32_t base = 0; v0 + 4u * base <= tot; base += kWave / 4) {
-        const uint32_t j = base + q, vv = v0 + 4u * j;
-        bool is_hdr = vv <= tot;
-        uint32_t at = 0;
-        if (is_hdr && vv > 0) {
-          at = (slots[vv - 1] & 0xFFFu) + 1u;
-          is_hdr = at < (uint32_t)kChunkBytes;
-        }
-        hc += (uint32_t)__builtin_popcountll(__ballot(is_hdr && sub == 0u));
-        if (is_hdr && j < nc.K) {
-          const bool end_known = vv < tot;
-          uint32_t lnm = end_known ? (uint32_t)(slots[vv] & 0xFFFu) - at - 1u : ~0u;  // name bytes in front of the '\n'
-          const bool at_sign = copy[at] == '@';
-          bool ok = true;
-          uint4 x;
-          if (end_known) {
-            __builtin_memcpy(&x, copy + at + 1u + 16u * sub, 16);
-          } else if (cb + at + 1u + kDigestText <= n) {
-            // the line runs into the next chunk (one header in eight at 150 bp): its bytes from the image - the
-            // wavefront next door is loading them anyway - and its length from the '\n' among them, if there is one
-            __builtin_memcpy(&x, img + cb + at + 1u + 16u * sub, 16);
-            const uint32_t m = pack_marks16(eq_bytes(x.x, 0x0A0A0A0Au), eq_bytes(x.y, 0x0A0A0A0Au), eq_bytes(x.z, 0x0A0A0A0Au),
-                                            eq_bytes(x.w, 0x0A0A0A0Au));
-            uint32_t mine = m ? 16u * sub + (uint32_t)__builtin_ctz(m) : ~0u;
-            uint32_t o = dpp0<0xB1, 0xf, 0xf>(mine);  // quad_perm [1,0,3,2]
-            mine = o < mine ? o : mine;
-            o = dpp0<0x4E, 0xf, 0xf>(mine);           // quad_perm [2,3,0,1]
-            lnm = o < mine ? o : mine;
-          } else {
-            x = make_uint4(0, 0, 0, 0);
-            ok = false;
-          }
-          uint32_t nlen = 0, acct = 0;
-          if (casava) {
-            // the name ends at the first blank of the line (src/fastq.c:496-503); "/1" in front of it is dropped
-            const uint32_t m = pack_marks16(eq_bytes(x.x, 0x20202020u), eq_bytes(x.y, 0x20202020u), eq_bytes(x.z, 0x20202020u),
-                                            eq_bytes(x.w, 0x20202020u));
-            uint32_t mine = m ? 16u * sub + (uint32_t)__builtin_ctz(m) : ~0u;
-            uint32_t o = dpp0<0xB1, 0xf, 0xf>(mine);
-            mine = o < mine ? o : mine;
-            o = dpp0<0x4E, 0xf, 0xf>(mine);
-            const uint32_t sp = o < mine ? o : mine;
-            if (sp >= lnm || sp >= kDigestText) ok = false;  // no blank in the line (or none in what the quad sees of it)
-            // the byte two places in front of the blank: with the lane that holds it
-            const uint32_t two = sp - 2u;
-            uint32_t slash = 0;
-            if (ok && sp >= 2u && (two >> 4) == sub) {
-              const uint32_t wsel = (two >> 2) & 3u;
-              const uint32_t wd = wsel == 0u ? x.x : wsel == 1u ? x.y : wsel == 2u ? x.z : x.w;
-              slash = ((wd >> (8u * (two & 3u))) & 0xFFu) == '/' ? 1u : 0u;
-            }
-            slash |= dpp0<0xB1, 0xf, 0xf>(slash);
-            slash |= dpp0<0x4E, 0xf, 0xf>(slash);
-            nlen = acct = ok ? sp - 2u * slash : 0u;
-          } else {
-            // strlen(&hdr[1]) counts the '\n' (src/fastq.c:505-511); a line whose end nobody saw, or one so short that
-            // the name would hold the '\n', is left to the byte-wise path
-            const uint32_t L = lnm + 1u;
-            if (lnm == ~0u || L < 1u + pe_cut) ok = false;
-            const uint32_t l = L - pe_cut;
-            acct = l;
-            nlen = l - 1u;
-            if (nlen > kDigestText) ok = false;
-          }
-          if (nlen > 1023u || acct > 1023u) ok = false;
-          if (!ok) nlen = acct = 0;
-          // the hash: this lane's two words, bytes behind the name zeroed, summed over the quad
-          const uint32_t lo = 16u * sub;
-          const uint32_t k0 = nlen > lo ? nlen - lo : 0u;             // name bytes in this lane's first word and beyond
-          const uint32_t k1 = nlen > lo + 8u ? nlen - lo - 8u : 0u;   // ... in its second word and beyond
-          uint64_t w0 = ((uint64_t)x.y << 32) | x.x, w1 = ((uint64_t)x.w << 32) | x.z;
-          w0 = k0 >= 8u ? w0 : (w0 & ((1ull << (8u * k0)) - 1ull));
-          w1 = k1 >= 8u ? w1 : (w1 & ((1ull << (8u * k1)) - 1ull));
-          // (the keys by selection: sub is one of four; a word counts when it holds a name byte - name_word)
-          const uint32_t a0 = sub == 0u ? name_key_a(0) : sub == 1u ? name_key_a(2) : sub == 2u ? name_key_a(4) : name_key_a(6);
-          const uint32_t b0 = sub == 0u ? name_key_b(0) : sub == 1u ? name_key_b(2) : sub == 2u ? name_key_b(4) : name_key_b(6);
-          const uint32_t a1 = sub == 0u ? name_key_a(1) : sub == 1u ? name_key_a(3) : sub == 2u ? name_key_a(5) : name_key_a(7);
-          const uint32_t b1 = sub == 0u ? name_key_b(1) : sub == 1u ? name_key_b(3) : sub == 2u ? name_key_b(5) : name_key_b(7);
-          uint64_t part = 0;
-          if (k0) part = (uint64_t)((uint32_t)w0 + a0) * (uint64_t)((uint32_t)(w0 >> 32) + b0);
-          if (k1) part += (uint64_t)((uint32_t)w1 + a1) * (uint64_t)((uint32_t)(w1 >> 32) + b1);
-          uint32_t plo = (uint32_t)part, phi = (uint32_t)(part >> 32);
-          uint64_t oth = ((uint64_t)dpp0<0xB1, 0xf, 0xf>(phi) << 32) | dpp0<0xB1, 0xf, 0xf>(plo);
-          part += oth;
-          plo = (uint32_t)part;
-          phi = (uint32_t)(part >> 32);
-          oth = ((uint64_t)dpp0<0x4E, 0xf, 0xf>(phi) << 32) | dpp0<0x4E, 0xf, 0xf>(plo);
-          part += oth;
-          if (sub == 0u) {
-            typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-            u64x2 dg;
-            dg.x = name_fin(name_seed(nlen) + part);
-            dg.y = (unsigned long long)(nlen | (acct << 10) | (vv << 20) | (at_sign ? kDigestAt : 0u) | (ok ? kDigestOk : 0u));
-            *reinterpret_cast<u64x2*>(nc.recs + ((uint64_t)chunk * nc.K + j) * kDigestWords) = dg;
-          }
-        }
-      }
-      if (hc >= kNoCapture) hc = kNoCapture - 1u;
-    }
-    if (lane == 0) nc.hcount[chunk] = (uint16_t)hc;
-  }
-  if constexpr (NAMES == 1) {
-    // ---- header lines that begin in this chunk -> 64-byte records (NameCapture) ----
-    // Line starts: the chunk's first byte when the byte in front of it is a '\n' (v = 0), and the byte behind the
-    // chunk's v-th newline unless that newline is the chunk's last byte; the line that starts at v has type t0 + v.
-    uint32_t hc = kNoCapture;
-    if (found && total <= (uint32_t)kStageCap) {
-      hc = 0;
-      const uint16_t* slots = s_slots[wv];
-      const bool first_is_start = prev == '\n';
-      for (uint32_t base = 0; base <= tot; base += kWave) {
-        const uint32_t vv = base + (uint32_t)lane;
-        bool is_hdr = vv <= tot && ((t0 + vv) & 3u) == 0u && (vv > 0 || first_is_start);
-        uint32_t at = 0;
-        if (is_hdr && vv > 0) {
-          at = (slots[vv - 1] & 0xFFFu) + 1u;
-          is_hdr = at < (uint32_t)kChunkBytes;
-        }
-        const unsigned long long hm = __ballot(is_hdr);
-        const uint32_t j = hc + (uint32_t)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
-        hc += (uint32_t)__builtin_popcountll(hm);
-        if (is_hdr && j < nc.K) {
-          bool end_known = vv < tot, real = false;
-          uint32_t len = (end_known ? (uint32_t)(slots[vv] & 0xFFFu) : (uint32_t)kChunkBytes) - at;
-          unsigned long long w[kNameRecWords];
-          if (end_known || cb + at + kNameRecText + 1 > n) {
-#pragma unroll
-            for (uint32_t k = 0; k < kNameRecWords; ++k) __builtin_memcpy(&w[k], copy + at + 8u * k - 3u, 8);  // byte 3 = the line's first byte
-          } else {
-            // the line runs into the next chunk (one header in eight does at 150 bp): its bytes from the image - the
-            // wavefront next door is loading them anyway - and its length from the '\n' among them, if there is one
-            const uint8_t* g = img + cb + at - 3u;
-            unsigned long long nlm[kNameRecWords];
-#pragma unroll
-            for (uint32_t k = 0; k < kNameRecWords; ++k) {
-              __builtin_memcpy(&w[k], g + 8u * k, 8);
-              const unsigned long long y = w[k] ^ 0x0A0A0A0A0A0A0A0Aull;
-              nlm[k] = ~(((y & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | y | 0x7F7F7F7F7F7F7F7Full);
-            }
-            nlm[0] &= ~0xFFFFFFull;  // (the three bytes in front of the line)
-            real = true;
-            len = kNameRecText + 1;  // at least: no '\n' among the bytes of the record
-#pragma unroll
-            for (int k = (int)kNameRecWords - 1; k >= 0; --k)
-              if (nlm[k]) {
-                len = 8u * (uint32_t)k + ((uint32_t)__builtin_ctzll(nlm[k]) >> 3) - 3u;
-                end_known = true;
-              }
-          }
-          len = len > 1023u ? 1023u : len;
-          const uint32_t meta = len | (vv << 10) | (end_known ? 1u << 19 : 0u) | (((w[0] >> 24) & 0xFFu) == '@' ? 1u << 20 : 0u) |
-                                (real ? 1u << 21 : 0u);
-          w[0] = (w[0] & 0xFFFFFFFF00000000ull) | meta;
-          typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-          u64x2* dst = reinterpret_cast<u64x2*>(nc.recs + ((uint64_t)chunk * nc.K + j) * kNameRecWords);
-#pragma unroll
-          for (uint32_t k = 0; k < kNameRecWords / 2; ++k) {
-            u64x2 x;
-            x.x = w[2 * k];
-            x.y = w[2 * k + 1];
-            dst[k] = x;
-          }
-        }
-      }
-      if (hc >= kNoCapture) hc = kNoCapture - 1u;
-    }
-    if (lane == 0) nc.hcount[chunk] = (uint16_t)hc;
-  }
-  if (lane == 0) {
-    o.counts[chunk] = total;
-    o.cinfo[chunk] = info;
-    if (flags) atomicOr(&cs->flags, flags);
-  }
+  if constexpr (NAMES == 2) capture_digests(img, n, c, nc, lds.slots[wv], prev == '\n', sp, r);
+  if constexpr (NAMES == 1) capture_records(img, n, c, nc, lds.slots[wv], prev == '\n', sp, r);
+  write_chunk_results(o, cs, c, r.total, info, flags);
 }
 
 // WAVE_PACK: for tools/kbench - the launch of its own keeps the v_dot4 packs (alone on the GPU it is 1.7 - 1.9 % slower with the
@@ -828,6 +722,40 @@ struct LinesArgs {
 
 constexpr int kLinesHist = 3072;
 constexpr int kLinesPer = 2;  // records per lane and step: their staged-entry loads are in flight together (4: 1.29 -> 1.41 ms; 6 wavefronts per SIMD instead of 5: no change)
+
+// the wavefront owns records g*64 .. g*64+63 = two whole words of the bitmap: it stores those that hold a suspect
+__device__ __forceinline__ void store_suspect_words(uint32_t* bits, uint64_t g, unsigned long long sm) {
+  const uint64_t w = g * 2;
+  if ((uint32_t)sm) bits[w] = (uint32_t)sm;
+  if ((uint32_t)(sm >> 32)) bits[w + 1] = (uint32_t)(sm >> 32);
+}
+
+// The end of a line kernel's workgroup.  Lane 0 of every wavefront brings the wavefront's counted records and their
+// shortest and longest read (n_ok, min_rl, max_rl): through s_red they become one addition to the accumulator per
+// workgroup.  Then the workgroup's LDS histogram of the lengths below N_HIST goes to A.hist.
+template <int N_HIST>
+__device__ __forceinline__ void lines_workgroup_end(const LinesArgs& A, unsigned long long (&s_red)[3][kBlock / kWave],
+                                                    const uint32_t (&s_hist)[N_HIST], unsigned long long n_ok,
+                                                    unsigned long long min_rl, unsigned long long max_rl) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / kWave; ++w) {
+      n_ok += s_red[0][w];
+      min_rl = s_red[1][w] < min_rl ? s_red[1][w] : min_rl;
+      max_rl = s_red[2][w] > max_rl ? s_red[2][w] : max_rl;
+    }
+    if (n_ok) {
+      atomicAdd(&A.acc->num_rds, n_ok * A.weight);
+      if (min_rl < A.acc->min_rl) atomicMin(&A.acc->min_rl, min_rl);
+      if (max_rl > A.acc->max_rl) atomicMax(&A.acc->max_rl, max_rl);
+    }
+  }
+  for (int i = threadIdx.x; i < N_HIST; i += kBlock) {
+    const uint32_t cc = s_hist[i];
+    if (cc) atomicAdd(&A.hist[i], (unsigned long long)cc * A.weight);
+  }
+}
+
 template <bool TODO>
 __global__ __launch_bounds__(kBlock) void k_stream_lines(LinesArgs A, const uint8_t* __restrict__ todo) {
   __shared__ uint32_t s_hist[kLinesHist];
@@ -898,6 +826,9 @@ __global__ __launch_bounds__(kBlock) void k_stream_lines(LinesArgs A, const uint
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // ---- phase 1a: where the entries are (LDS only, but for lanes outside the window) ----
+    // (not a function of its own: with the window handed over by reference, by value or as LDS pointers the kernel came
+    // out with six more vector registers - five wavefronts per SIMD become four on the marked steps - or eighty more
+    // scalar instructions, docs/measurement_history.md)
     uint64_t at[kLinesPer][5];   // index into stage[] of the entry to fetch
     bool ld[kLinesPer][5];       // ... when there is one
 #pragma unroll
@@ -1051,14 +982,10 @@ __global__ __launch_bounds__(kBlock) void k_stream_lines(LinesArgs A, const uint
           }
         }
       }
-      // the wavefront owns records g*64 .. g*64+63 = two whole words of the bitmap
       const unsigned long long sm = __ballot(sus);
       if (lane == 0 && sm) {
-        const uint64_t w = g * 2;
-        if ((g + 1) * kWave <= A.suspect_cap) {
-          if ((uint32_t)sm) A.suspect_bits[w] = (uint32_t)sm;
-          if ((uint32_t)(sm >> 32)) A.suspect_bits[w + 1] = (uint32_t)(sm >> 32);
-        } else atomicOr(A.flags, kFlagSuspectOverflow);
+        if ((g + 1) * kWave <= A.suspect_cap) store_suspect_words(A.suspect_bits, g, sm);
+        else atomicOr(A.flags, kFlagSuspectOverflow);
       }
     }
   }
@@ -1075,23 +1002,7 @@ __global__ __launch_bounds__(kBlock) void k_stream_lines(LinesArgs A, const uint
     s_red[1][threadIdx.x >> 6] = min_rl;
     s_red[2][threadIdx.x >> 6] = max_rl;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / kWave; ++w) {
-      n_ok += s_red[0][w];
-      min_rl = s_red[1][w] < min_rl ? s_red[1][w] : min_rl;
-      max_rl = s_red[2][w] > max_rl ? s_red[2][w] : max_rl;
-    }
-    if (n_ok) {
-      atomicAdd(&A.acc->num_rds, n_ok * A.weight);
-      if (min_rl < A.acc->min_rl) atomicMin(&A.acc->min_rl, min_rl);
-      if (max_rl > A.acc->max_rl) atomicMax(&A.acc->max_rl, max_rl);
-    }
-  }
-  for (int i = threadIdx.x; i < kLinesHist; i += kBlock) {
-    const uint32_t cc = s_hist[i];
-    if (cc) atomicAdd(&A.hist[i], (unsigned long long)cc * A.weight);
-  }
+  lines_workgroup_end(A, s_red, s_hist, n_ok, min_rl, max_rl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1358,14 +1269,9 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
           }
         }
       }
-      // the wavefront owns records g*64 .. g*64+63 = two whole words of the bitmap
       const unsigned long long sm = (call & kSusAll) ? ~0ull : __ballot(sus);
       if (sm) {
-        if (lane == 0) {
-          const uint64_t w = g * 2;
-          if ((uint32_t)sm) A.suspect_bits[w] = (uint32_t)sm;
-          if ((uint32_t)(sm >> 32)) A.suspect_bits[w + 1] = (uint32_t)(sm >> 32);
-        }
+        if (lane == 0) store_suspect_words(A.suspect_bits, g, sm);
       }
     }
     __builtin_amdgcn_wave_barrier();  // (s_ent is rewritten by the next step)
@@ -1386,23 +1292,7 @@ __device__ __forceinline__ void stream_lines_fast_body(const LinesArgs& A, uint8
     s_red[1][threadIdx.x >> 6] = min_rl;
     s_red[2][threadIdx.x >> 6] = max_rl;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / kWave; ++w) {
-      n_ok += s_red[0][w];
-      min_rl = s_red[1][w] < min_rl ? s_red[1][w] : min_rl;
-      max_rl = s_red[2][w] > max_rl ? s_red[2][w] : max_rl;
-    }
-    if (n_ok) {
-      atomicAdd(&A.acc->num_rds, n_ok * A.weight);
-      if (min_rl < A.acc->min_rl) atomicMin(&A.acc->min_rl, min_rl);
-      if (max_rl > A.acc->max_rl) atomicMax(&A.acc->max_rl, max_rl);
-    }
-  }
-  for (int i = threadIdx.x; i < kLinesFastHist; i += kBlock) {
-    const uint32_t cc = s_hist[i];
-    if (cc) atomicAdd(&A.hist[i], (unsigned long long)cc * A.weight);
-  }
+  lines_workgroup_end(A, s_red, s_hist, n_ok, min_rl, max_rl);
 }
 
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_stream_lines_fast(LinesArgs A, uint8_t* __restrict__ todo) {
